@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the per-walker likelihood hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1] / configs[2], SURVEY.md 8d "cfg2/cfg3"):
 8 passbands (PACS 70/100/160, SPIRE 250/350/500, SCUBA2 850, Bolocam 1.1mm;
@@ -24,7 +24,10 @@ ncclAllGather over RCCL (--exchange rccl; also the automatic fall-back).  Positi
 in HBM for the whole run: there is no host round trip inside the timed region.  `value`
 = walker-likelihood evaluations per second of that real chain = 250 N K / t.
 
-Also measured (rank 0, N = 1, outside the timed region; in the side file, the starred ones on the line too):
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes the
+ensemble the timed region left (DIR/pos.npy, DIR/lnprob.npy, float64).  Everything below needs --full.
+
+Also measured with --full (rank 0, N = 1, outside the timed region; in the side file, the starred ones on the line too):
   boundary *    SURVEY.md 8d metric M1: synchronous likelihood.__call__ on host arrays
                 (PCIe inclusive), median of >= 200 calls, for 125 and 250 rows
   pipelined     independent launches on pre-computed proposals enqueued back to back
@@ -36,9 +39,11 @@ Also measured (rank 0, N = 1, outside the timed region; in the side file, the st
   cfg5          1000 sources x 250 walkers in one launch (BASELINE.json configs[4])
   cpu_baseline * the CPU oracle timed on this box's cores
 
-Prints ONE short JSON line on rank 0 (< 4 KB: the contract's keys, roofline, roofline_hbm,
-boundary_M1, cpu_baseline, cfg5's three numbers) and writes everything measured -- the
-legs listed here in full -- to gpurun_out/bench_full.json.  torch is used only as launcher plumbing
+With N > 1, --full also rehearses and times the exchanges the timed run did not use and the sharded boundary.
+
+Prints ONE short JSON line on rank 0 (< 4 KB: the contract's keys; with --full also roofline, roofline_hbm,
+boundary_M1, cpu_baseline, cfg5's three numbers) and, with --full, writes everything measured -- the
+legs listed here in full -- to the side file FULL_PATH.  torch is used only as launcher plumbing
 (torch.distributed gloo rendezvous + barrier); all device work goes through the C-ABI
 of libmbb_hip.so.  A collective that cannot be set up or does not return is a failure:
 the line says so and the exit status is non-zero.
@@ -578,8 +583,18 @@ def ensemble_crc(pos, lnp):
     return zlib.crc32(np.ascontiguousarray(pos).tobytes()) ^ zlib.crc32(np.ascontiguousarray(lnp).tobytes())
 
 
+def dump_outputs(d, pos, lnp):
+    """--dump-outputs: what the timed steps computed, as a caller of the sampler receives it -- the walkers' positions
+    [walkers, 5] and log-probabilities [walkers] after the last timed step.  The same arguments give the same inputs
+    (walkers(), the sampler's seed), so two builds can be compared file for file."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "pos.npy"), np.ascontiguousarray(pos, dtype=np.float64))
+    np.save(os.path.join(d, "lnprob.npy"), np.ascontiguousarray(lnp, dtype=np.float64))
+
+
 LINE_LIMIT = 4096           # bytes of the ONE line on stdout (round 4's 20.7 KB line was not parsed by the driver)
 FULL_PATH = os.environ.get("MBB_BENCH_FULL") or os.path.join(ROOT, "gpurun_out", "bench_full.json")
+SIDE_FILE = FULL_PATH       # (main() clears it unless --full: a plain run writes no side file and its line names none)
 
 
 def _num(x, sig=6):
@@ -696,7 +711,8 @@ def short_line(full):
     for k, n in (("error", 300), ("extras_error", 160), ("invalid", 120), ("collective", 160), ("hang", 100)):
         if full.get(k):
             out[k] = _txt(full[k], n)
-    out["full"] = _txt(os.path.relpath(FULL_PATH, ROOT), 100)
+    if SIDE_FILE:
+        out["full"] = _txt(os.path.relpath(SIDE_FILE, ROOT), 100)
     return out
 
 
@@ -706,15 +722,16 @@ def emit(obj):
 
 
 def emit_final(full):
-    """What the driver reads: everything measured goes to the side file gpurun_out/bench_full.json, the short
+    """What the driver reads: with --full everything measured goes to the side file SIDE_FILE, the short
     line -- strict JSON, one line, below LINE_LIMIT bytes -- is the last thing on stdout."""
-    try:
-        os.makedirs(os.path.dirname(FULL_PATH), exist_ok=True)
-        with open(FULL_PATH + ".tmp", "w") as f:
-            json.dump(full, f, indent=1, default=str)
-        os.replace(FULL_PATH + ".tmp", FULL_PATH)
-    except OSError as e:
-        sys.stderr.write("bench.py: cannot write %s: %r\n" % (FULL_PATH, e))
+    if SIDE_FILE:
+        try:
+            os.makedirs(os.path.dirname(SIDE_FILE), exist_ok=True)
+            with open(SIDE_FILE + ".tmp", "w") as f:
+                json.dump(full, f, indent=1, default=str)
+            os.replace(SIDE_FILE + ".tmp", SIDE_FILE)
+        except OSError as e:
+            sys.stderr.write("bench.py: cannot write %s: %r\n" % (SIDE_FILE, e))
     if os.environ.get("MBB_BENCH_FULL_LINE"):
         # (the profile scripts' summarizers read legs of the line that are in the side file only: tools/run_profiles.sh)
         sys.stdout.flush()
@@ -743,6 +760,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ensemble the timed steps left (what run_mcmc hands a caller: positions and "
+                         "log-probabilities) to DIR/pos.npy and DIR/lnprob.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the eight regions behind the timed one, every leg of the "
+                         "side file (boundary, rooflines, other forms and sizes, cfg5, fits, configs, CPU baseline; "
+                         "N > 1: the other exchanges and the sharded boundary); the --no-* options below trim it")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-cfg5", action="store_true", help="skip the 250 000-walker launch")
     ap.add_argument("--no-configs", action="store_true", help="skip the per-config objects (cfg1, cfg4)")
@@ -755,7 +779,7 @@ def parse_args(argv=None):
                     help="N > 1, --exchange auto: which exchange is tried first for the timed run -- the one "
                          "expected to be fastest (one launch per run across the ranks, then one launch per "
                          "half-step with peer writes, then RCCL) or the simplest (the reverse).  Whichever is "
-                         "timed, the others are rehearsed afterwards and reported in `exchange_validation`")
+                         "timed, with --full the others are rehearsed afterwards and reported in `exchange_validation`")
     ap.add_argument("--no-validate", action="store_true",
                     help="N > 1: do not rehearse the exchanges the timed run did not use")
     ap.add_argument("--no-sharded-boundary", action="store_true",
@@ -919,7 +943,10 @@ def supervise(args):
 
 
 def main():
+    global SIDE_FILE
     args = parse_args()
+    if not args.full:
+        SIDE_FILE = None
     hook = os.environ.get("MBB_BENCH_RANK_HOOK")
     if hook and (os.environ.get("MBB_BENCH_WORKER") == "1" or (args.gpus == 1 and os.environ.get("MBB_BENCH_WORKER_FAKE_TOP"))):
         # tests only (tests/_fake_bench_rank.py): a stand-in for a rank, so that the supervisor's collecting, merging,
@@ -1201,13 +1228,17 @@ def worker_body(args, rank, world, local_rank, base, fail):
                     ran.append(pre)
                 smp.advance_timed(warmup)
                 first = smp.advance_timed(steps)
-                # (the line's value is that ONE region; eight more of the same right behind it, reported beside it,
-                # say how far the single shot is from the typical one)
-                state["again"] = [smp.advance_timed(steps) for _ in range(8)]
+                if args.full:
+                    # (the line's value is that ONE region; eight more of the same right behind it, reported beside it,
+                    # say how far the single shot is from the typical one -- after the ensemble the timed region left
+                    # has been kept for --dump-outputs)
+                    state["end"] = smp.run_mcmc(None, 0, storechain=False)[:2]
+                    state["again"] = [smp.advance_timed(steps) for _ in range(8)]
                 del scratch
                 # (for the profile summaries: which of the sampler kernel's launches was the timed one, and how many
                 # half-steps they cover together -- runs of fewer than two steps are not launches of that kernel)
-                state["runs"] = {"steps_of_every_run": ran + [warmup, steps] + [steps] * 8, "timed_run": len(ran) + 1}
+                state["runs"] = {"steps_of_every_run": ran + [warmup, steps] + [steps] * len(state.get("again") or []),
+                                 "timed_run": len(ran) + 1}
                 return first
             # (N > 1: the same sharded sampler, PRECONDITION_STEPS untimed steps further first -- the GPUs as a long run leaves
             # them, as at N = 1; a fixed count, the ranks must agree on it)
@@ -1253,6 +1284,8 @@ def worker_body(args, rank, world, local_rank, base, fail):
             return res
         res.update(ok=True, elapsed=elapsed, stream_ms=stream_ms, again=state.get("again"), runs=state.get("runs"),
                    pre_steps=state.get("pre_steps", 0),
+                   # (the ensemble right after the timed steps: --dump-outputs)
+                   end=state["end"] if "end" in state else (pos_end, lnp_end),
                    form=ctx.info("last_kernel_form"),
                    us_per_step=1e6 * elapsed / steps,
                    # which instantiation that was (form 7: last_wpb = pairs of walkers per workgroup)
@@ -1292,6 +1325,8 @@ def worker_body(args, rank, world, local_rank, base, fail):
                              "kernel_form": run["form"], "why": "carried the timed run"}
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *run["end"])
         out = dict(base)
         out.update({"value": nwt * args.steps / elapsed, "ms_per_step": 1e3 * elapsed / args.steps,
                     "mcmc_steps_per_s": args.steps / elapsed,
@@ -1351,7 +1386,7 @@ def worker_body(args, rank, world, local_rank, base, fail):
                       % ("staged," if run["staged"] else "", form, ctx.info("last_grid"), ctx.info("last_threads")))
         out["config"]["sampler_form_short"] = ("form %d: %s" % (form, "one launch per <=4096 steps" if form in (6,) + ONE_LAUNCH_FORMS
                                                                   else "one launch per half-step"))
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # (whatever goes wrong beside the timed region is said on the line; it does not take the
             # measured value with it)
             try:
@@ -1387,7 +1422,8 @@ def worker_body(args, rank, world, local_rank, base, fail):
         # the fused kernel and ONE ncclAllGather of the blocks' log-probabilities gives every rank the whole
         # vector: literally emcee's pool (mbb_fit.py:80-81) replaced.  Host arrays in and out, never `value`.
         hung = None
-        if (world <= ndev or rccl_named) and not args.no_sharded_boundary:
+        asked = args.full and not args.no_sharded_boundary
+        if (world <= ndev or rccl_named) and asked:
             if still_time():
                 try:
                     def bcast(obj):
@@ -1413,12 +1449,12 @@ def worker_body(args, rank, world, local_rank, base, fail):
                 sys.stdout.flush()
                 os._exit(0)             # the measured run was valid; a wedged stream would hang teardown
         elif rank == 0:
-            emit({"_part": "boundary_sharded", "data": {"ok": None, "why": ("not asked for" if args.no_sharded_boundary else
+            emit({"_part": "boundary_sharded", "data": {"ok": None, "why": ("not asked for" if not asked else
                   "skipped: %d ranks share %d device(s), RCCL needs a device per rank" % (world, ndev))}})
         # ---- the exchanges the timed run did not use: the same rehearsal and a short timed run each,
         # outside `value`.  The measured line is already with the supervisor; whatever happens here
         # only adds to it.
-        if not args.no_validate:
+        if args.full and not args.no_validate:
             vsteps = max(50, min(args.steps, 500))
             hung = None
             for m in all_modes:

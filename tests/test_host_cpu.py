@@ -419,8 +419,8 @@ def test_bench_prints_the_short_line_and_the_side_file(world, tmp_path):
                 "MBB_BENCH_RANK_HOOK": os.path.join(ROOT, "tests", "_fake_bench_rank.py")})
     if world == 1:
         env["MBB_BENCH_WORKER_FAKE_TOP"] = "1"
-    pr = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5"], env=env,
-                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    pr = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5", "--full"],
+                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert pr.returncode == 0, pr.stderr.decode()[-2000:]
     out = [ln for ln in pr.stdout.decode().splitlines() if ln.strip()]
     assert len(out) == 1, out
@@ -434,6 +434,32 @@ def test_bench_prints_the_short_line_and_the_side_file(world, tmp_path):
         assert len(d["exchange_validation"]["ipc"]) <= 70
         assert d["boundary_sharded"]["ok"] is True and d["boundary_sharded"]["rows_%d" % (125 * world)] == pytest.approx(31.123, rel=1e-4)
         assert len(full["exchange_validation"]["ipc"]["why"]) > 1000          # the side file keeps the detail
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_plain_bench_writes_the_line_and_no_side_file(world, tmp_path):
+    """Without --full the run prints its one line and leaves nothing behind: no side file, and the line names none."""
+    import json
+    import shutil
+    root = tmp_path / "repo"
+    root.mkdir()
+    shutil.copy(os.path.join(ROOT, "bench.py"), root / "bench.py")
+    shutil.copy(os.path.join(ROOT, "BASELINE.json"), root / "BASELINE.json")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MBB_BENCH_WORKER",
+                                                            "MBB_BENCH_FULL", "MBB_BENCH_FULL_LINE")}
+    env.update({"MBB_BENCH_FAKE_WORKER": "part", "MBB_BENCH_GRACE_S": "5", "PYTHONPATH": ROOT,
+                "MBB_BENCH_RANK_HOOK": os.path.join(ROOT, "tests", "_fake_bench_rank.py")})
+    if world == 1:
+        env["MBB_BENCH_WORKER_FAKE_TOP"] = "1"
+    pr = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5"], env=env,
+                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert pr.returncode == 0, pr.stderr.decode()[-2000:]
+    out = [ln for ln in pr.stdout.decode().splitlines() if ln.strip()]
+    assert len(out) == 1, out
+    d = json.loads(out[0])
+    assert d["value"] == 1.0e6 * world and d["ms_per_step"] == 1.0 and d["steps"] == 20 and d["warmup"] == 5
+    assert "full" not in d
+    assert sorted(p.name for p in root.iterdir()) == ["BASELINE.json", "bench.py"]
 
 
 def test_bench_under_a_launcher_with_the_wrong_world_size_says_so():

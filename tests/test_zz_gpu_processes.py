@@ -34,7 +34,7 @@ def test_bench_with_two_ranks_sharing_this_gpu():
     side = os.path.join(tempfile.mkdtemp(), "bench_full.json")
     env = dict(os.environ, MBB_BENCH_WALKERS_PER_GPU="32", MBB_BENCH_FULL=side)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2",
-                          "--oversubscribe"], capture_output=True, text=True, timeout=300, env=env, cwd=root)
+                          "--oversubscribe", "--full"], capture_output=True, text=True, timeout=300, env=env, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-2000:], out.stderr[-3000:])
     d = json.loads(lines[0])
@@ -49,6 +49,34 @@ def test_bench_with_two_ranks_sharing_this_gpu():
     ev = full["exchange_validation"]
     assert ev["ipc-launches"]["ok"] is True and ev["rccl"]["ok"] is None and ev["ipc"]["ok"] is None, ev
     assert ev["ipc-launches"]["us_per_step"] > 0 and full["value"] == pytest.approx(d["value"], rel=1e-5)
+
+
+def test_bench_dump_outputs_are_the_chain_after_the_timed_steps(mbb, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, a plain run: one line whose steps, warmup and
+    ms_per_step are those of the K timed steps, nothing of --full on it, and DIR holds what a caller of the sampler gets
+    after them -- the positions and lnprob of the bench's walkers and seed after 60 (rehearsal) + W + K steps, bit for bit
+    the chain of one run_mcmc over as many steps."""
+    import json, subprocess, sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    K, W = 7, 3
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MBB_BENCH_WORKER",
+                                                            "MBB_BENCH_WALKERS_PER_GPU", "MBB_BENCH_FULL_LINE")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300, env=env, cwd=root)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-2000:], out.stderr[-3000:])
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["warmup"] == W and d["ms_per_step"] > 0, d
+    assert d["value"] == pytest.approx(bench.NW_PER_GPU * 1e3 / d["ms_per_step"], rel=1e-5)
+    assert not any(k in d for k in ("full", "cpu_baseline", "boundary_M1", "value_median_of_9")), d
+    pos, lnp = np.load(str(tmp_path / "out" / "pos.npy")), np.load(str(tmp_path / "out" / "lnprob.npy"))
+    assert pos.dtype == lnp.dtype == np.float64 and pos.shape == (bench.NW_PER_GPU, 5) and lnp.shape == (bench.NW_PER_GPU,)
+    assert np.all(np.isfinite(lnp))
+    like, _ = bench.make_likelihood(0)
+    s = mbb.DeviceEnsembleSampler(bench.NW_PER_GPU, 5, like, seed=11)
+    want_pos, want_lnp, _ = s.run_mcmc(bench.walkers(1)[:bench.NW_PER_GPU], 60 + W + K, storechain=False)
+    assert np.array_equal(pos, want_pos) and np.array_equal(lnp, want_lnp)
 
 
 def _run_pool_workers(mbb, g_lnl, world, ncalls, env_extra=None):
@@ -203,7 +231,7 @@ def test_bench_rccl_legs_with_two_ranks_sharing_this_gpu():
     side = os.path.join(tempfile.mkdtemp(), "bench_full.json")
     env = dict(os.environ, MBB_BENCH_WALKERS_PER_GPU="32", MBB_BENCH_FULL=side, MBB_RCCL_LIB=_standin_rccl())
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2",
-                          "--oversubscribe", "--exchange", "rccl"], capture_output=True, text=True, timeout=300, env=env, cwd=root)
+                          "--oversubscribe", "--exchange", "rccl", "--full"], capture_output=True, text=True, timeout=300, env=env, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-2000:], out.stderr[-3000:])
     d = json.loads(lines[0])
