@@ -241,9 +241,7 @@ int mbb_event_destroy(mbb_ctx *ctx, void *ev);
  * which needs none of the constructor's merge point, into a buffer in LDS -- and sums the units from the buffer when
  * the constructor is through, when the bands have at least 12 chunks of 64 samples (2: with fewer too); 0: one after
  * the other, as a launch does it; the same results either way.
- * mbb_get_info "serving", "serve_requests", "serve_fallbacks"), "launch_api" (how the likelihood launch of given rows
- * is handed to the runtime: 1, the default, hipModuleLaunchKernel with the argument block as one packed buffer;
- * 0 hipLaunchKernel -- 0.2 us more per call: profiles/r04/boundary_breakdown.txt), "seg_chunks", "pack_tails" (band
+ * mbb_get_info "serving", "serve_requests", "serve_fallbacks"), "seg_chunks", "pack_tails" (band
  * leftovers share chunks; takes effect at the next mbb_set_bands), "stage_tables",
  * "virtual_ranks", "debug", "roof_threads" / "roof_wgs_per_cu" (measurement only: the geometry of
  * mbb_roof_probe), "xchg_spin_max" (polls before a launch waiting for a peer
@@ -261,11 +259,9 @@ int mbb_event_destroy(mbb_ctx *ctx, void *ev);
  * "resident_sampler" (default 1: ensembles beyond that run as ONE launch per 4096 steps as well, a workgroup owning
  * W = ceil(half / CUs) walkers of each half, up to 8; 0: off, the plain train; 2: every eligible ensemble takes it),
  * that run -- "form 9", k_flowa -- constructs every walker's proposal a half-step ahead, for both outcomes of its partner's
- * pending move, beside the quadrature of the half-step before ("resident_ahead", round 4's choice between it and a form
- * with nothing ahead, is accepted and ignored: that form is gone),
+ * pending move, beside the quadrature of the half-step before,
  * "resident_walkers" (walkers per workgroup and half of the resident forms; 0 = the host's choice),
- * "lookahead_rows" / "lookahead_waves" (the sharded one-launch run: 0 = the host's choice of candidates per wave and
- * waves per workgroup among those that work ahead), "sharded_flow_sampler" (default 1: a sharded run with the
+ * "sharded_flow_sampler" (default 1: a sharded run with the
  * one-hop exchange is one launch per 4096 steps on every rank too; 0: one launch per half-step),
  * "flow_spin_log2" (0 = 22: log2 of the polls before a wait -- 63: no polls, the first miss, for tests --
  * inside the one-launch run gives up; mbb_sampler_run then redoes the run as a launch train and

@@ -16,7 +16,7 @@ SRC_HOST = os.path.join(HERE, "csrc", "mbb_host_tables.cpp")      # host-only ta
 SRC_FLOW = os.path.join(HERE, "csrc", "mbb_flow.hip")             # the one-launch sampler kernel, own flags
 SRC_REG = os.path.join(HERE, "csrc", "mbb_registry.cpp")          # host-only: which processes are on which GPU
 # Both device translation units: no contraction of a product and a sum the source keeps apart.  The
-# sampler forms (k_lnlike SMODE 1/2/5/6, k_flowm) are held to one another bit for bit, and the shared
+# sampler forms (k_lnlike SMODE 1/2/6, k_flowm, k_flowa) are held to one another bit for bit, and the shared
 # arithmetic is inlined into each of them: with the compiler free to contract, whether a given a*b+c
 # rounds once or twice depends on the code around it.  Every intended fused multiply-add is an explicit
 # fma() in the source (tools/fma_audit.py lists the kernels whose fp64 fma/mul/add counts differ between
@@ -29,6 +29,7 @@ DEPS = [SRC, SRC_HOST, SRC_FLOW, SRC_REG, os.path.join(HERE, "csrc", "mbb_host_t
         os.path.join(HERE, "csrc", "mbb_walker_consts.inc"),
         os.path.join(HERE, "csrc", "mbb_walker_penalties.inc"),
         os.path.join(HERE, "csrc", "mbb_flow_index.h"),
+        os.path.join(HERE, "csrc", "mbb_lds_plans.hip.h"),
         os.path.join(HERE, "csrc", "mbb_device.hip.h"),
         os.path.join(HERE, "csrc", "mbb_math.hip.h"),
         os.path.join(HERE, "csrc", "mbb_kernels.hip.h"),

@@ -1,6 +1,7 @@
-// mbb_flow_index.h -- index arithmetic of the one-launch look-ahead sampler run (k_lnlike SMODE 5),
-// shared by the kernel and by the host-side model of its hand-over protocol
-// (tests/test_host_cpu.py::test_flow_protocol_model, through the hooks in mbb_host_tables.cpp).
+// mbb_flow_index.h -- index arithmetic of the one-launch sampler runs (k_lnlike SMODE 6, the sharded
+// look-ahead run; k_flowm, form 7, and k_flowa, form 9, below), shared by the kernels and by the host-side
+// models of their hand-over protocols (tests/test_host_cpu.py::test_flow_protocol_model and the two after it,
+// through the hooks in mbb_host_tables.cpp).
 //
 // Half-steps are numbered j = 0, 1, 2, ... over a launch; half h = j & 1 of the ensemble moves in
 // half-step j (h = 0: rows [0, n/2), h = 1: the rest).  Everything a row publishes is filed under

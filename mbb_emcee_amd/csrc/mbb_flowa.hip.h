@@ -12,7 +12,7 @@
 // and when the partner's decision arrives only a selection is left: that candidate's constants go to LDS for the
 // quadrature.  Same draws, same proposal arithmetic (one rounding per coordinate wherever it is formed), same
 // constructor text, same units in the same order, same order of the band sums: the chain is bitwise the launch
-// train's.  The idea is form 5's (k_lnlike SMODE 5, one walker per workgroup, the constructor on workgroups of
+// train's.  The idea is form 5's (k_lnlike SMODE 5 until round 4, one walker per workgroup, the constructor on workgroups of
 // their own); the state and its check words are form 7's (FlowMView).  Twice the constructor work, the quadrature --
 // what bounds a half-step from two walkers per CU on -- once.
 //
@@ -36,16 +36,7 @@
 #pragma once
 #include "mbb_flowm.hip.h"
 
-constexpr int kFaMaxW = 8;      // walkers per workgroup and half
-constexpr int kFaNB = 2;        // hand-over record buffers in LDS: half-step j uses buffer j mod kFaNB
-constexpr int kFaRec = 10;      // doubles per proposal record besides WalkerK: proposal 0..4, (dim-1) ln z, ln u, the two penalties
-
-// dynamic LDS of a k_flowa launch besides the staged passband tables (bytes)
-__host__ __device__ constexpr size_t flowa_lds(size_t nb, size_t npart, bool cov_in_lds, size_t W)
-{
-    return kFaNB * W * (sizeof(WalkerK) + 8 * npart + 8 * kFaRec) + 8 * W * nb + 8 * 2 * W * 8 + 16 * nb +
-           (cov_in_lds ? 8 * nb * nb : 0) + 8 * (nb + 2) + 192 + 64;
-}
+// (kFaMaxW, kFaNB, kFaRec and flowa_lds, the LDS plan: mbb_lds_plans.hip.h)
 
 template <bool OPTHIN, bool NOALPHA, bool STAGE>
 __global__ void __launch_bounds__(1024) k_flowa(const LikeArgs a_val)

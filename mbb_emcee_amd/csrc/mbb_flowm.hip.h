@@ -1,7 +1,7 @@
 // mbb_flowm.hip.h -- k_flowm, the one-launch sampler run with every stage of a half-step working
 // ahead (sampler form 7; single GPU, single ensemble).  Included by mbb_flow.hip only.
 //
-// k_lnlike's one-launch form (SMODE 5) prepares a walker's proposal ahead -- the draw, the SED
+// k_lnlike's one-launch form (SMODE 6; SMODE 5 on one GPU until round 4) prepares a walker's proposal ahead -- the draw, the SED
 // constructor and the penalties, for both outcomes of its partner's pending move -- but its mover
 // waits for that partner's decision BEFORE the passband quadrature: hand-over + quadrature + band
 // sums + accept test are one chain per half-step.  Here the quadrature runs ahead as well.  One
@@ -26,7 +26,7 @@
 // (hand-over + quadrature + band sums) / 2 and (hand-over + constructor + quadrature + band sums) / 3
 // instead of their sum.  The price is twice the quadrature and up to four times the constructor
 // work, on CUs that were waiting.  Measured (tools/probe_flowm.py, probe_chain_flowm.py; the bench
-// workload): 6.2 us per MCMC step against 10.2 for SMODE 5; what a half-step waits for is, in this
+// workload): 6.2 us per MCMC step against 10.2 for round 3's SMODE 5; what a half-step waits for is, in this
 // order, the quadrature (a third), the constructor (a quarter), and the hand-over of the decisions of
 // three half-steps back.
 // Same draws, same arithmetic per candidate, same order of every sum: the chain is bitwise that of
@@ -69,15 +69,7 @@ constexpr int kFmEDone = 8;    // [kFmNB] half-step + 1 of the last record of bu
 constexpr int kFmPen = 16;     // [kFmNB] half-step + 1 of the record of buffer b whose two penalties are there (they follow the
                                // record: the quadrature does not wait for them, the accept test does)
 constexpr int kFmStaged = 12;  //        Q and E waves that have copied their share of the tables to LDS
-constexpr int kFmProp = 16;    // doubles per hand-over record besides WalkerK: proposal 0..4, (dim-1) ln z,
-                               // ln u, the two penalties, the walker's row as it is (9..13)
-// dynamic LDS of a k_flowm launch besides the staged passband tables (bytes)
-// (np = pairs of walkers a workgroup serves: the hand-over records and their control words are per pair)
-__host__ __device__ constexpr size_t flowm_lds(size_t nb, size_t npart, bool cov_in_lds, size_t np = 1)
-{
-    return np * kFmNB * sizeof(WalkerK) + 8 * (np * kFmNB * npart + 2 * nb + np * kFmNB * kFmProp + 2 * nb + (cov_in_lds ? nb * nb : 0)) +
-           8 * (nb + 2) + 8 * (kFmNC * 64) + 128 * np + 32;
-}
+// (kFmProp, the hand-over record, and flowm_lds, the LDS plan: mbb_lds_plans.hip.h)
 
 // The lane number as the compiler cannot see through it: what a C wave derives from it (which item a lane
 // fetches, its offsets and masks) is then derived again for every proposal instead of being kept in
@@ -600,7 +592,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             // partner's partner -- made their last move (number m_s) in half-step j - 2.  Either is put
             // together from what was known before that move was decided: the row as it was, and the
             // proposal it was tested on, whose candidate is the one the decision of ITS partner in
-            // half-step j - 3 says (k_lnlike, SMODE 5, the workgroups that work ahead).
+            // half-step j - 3 says (k_lnlike, SMODE 6, the workgroups that work ahead).
             const int m_s = flow_cnt(hj, j - 1), m_o = flow_cnt(hj ^ 1, j - 1);
             const int m_next = m_s + 1;
             const int g = j - 2;

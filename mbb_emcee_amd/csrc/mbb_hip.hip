@@ -39,7 +39,7 @@ MBB_FLOW_EXT(false, true)
 MBB_FLOW_EXT(true, false)
 MBB_FLOW_EXT(true, true)
 #undef MBB_FLOW_EXT
-// ... and so is k_flowm, sampler form 7 (mbb_flowm.hip.h; only its LDS plan is needed here)
+// ... and so is k_flowm, sampler form 7 (mbb_flowm.hip.h; its LDS plan is in mbb_lds_plans.hip.h)
 template <bool OPTHIN, bool NOALPHA, bool STAGE, int NP>
 __global__ void k_flowm(const LikeArgs a);
 #define MBB_FLOWM_EXT(OT, NA)                                                   \
@@ -61,11 +61,6 @@ MBB_FLOWA_EXT(false, true)
 MBB_FLOWA_EXT(true, false)
 MBB_FLOWA_EXT(true, true)
 #undef MBB_FLOWA_EXT
-static size_t flowa_lds_bytes(size_t nb, size_t npart, bool cov_in_lds, size_t W)        // = flowa_lds() of mbb_flowa.hip.h
-{
-    return 2 * W * (sizeof(WalkerK) + 8 * npart + 8 * 10) + 8 * W * nb + 8 * 2 * W * 8 + 16 * nb +
-           (cov_in_lds ? 8 * nb * nb : 0) + 8 * (nb + 2) + 192 + 64;
-}
 // ... and k_serve, the likelihood of given rows as a kernel that stays resident between boundary calls (mbb_serve.hip.h)
 template <bool OPTHIN, bool NOALPHA, bool STAGE, bool OVL>
 __global__ void k_serve(const LikeArgs a);
@@ -79,19 +74,35 @@ MBB_SERVE_EXT(false, true)
 MBB_SERVE_EXT(true, false)
 MBB_SERVE_EXT(true, true)
 #undef MBB_SERVE_EXT
-constexpr unsigned long long kServeQuitHost = 0xffffull;
 constexpr int kServePasses = 2;               // rows a workgroup of a resident server takes of one request, at most
-static size_t serve_lds_bytes(size_t nb, size_t npart, bool cov_in_lds)                  // = serve_lds() of mbb_serve.hip.h
-{
-    return sizeof(WalkerK) + 8 * npart + 8 * nb + 16 + 16 * nb + (cov_in_lds ? 8 * nb * nb : 0) + 8 * (nb + 2) + 64;
-}
-constexpr int kFrMaxWHost = 8;                  // walkers of each half a workgroup of the resident form may own (mbb_flowa.hip.h)
-constexpr int kFmPropHost = 16;
-static size_t flowm_lds_bytes(size_t nb, size_t npart, bool cov_in_lds, size_t np = 1)   // = flowm_lds() of mbb_flowm.hip.h
-{
-    return np * 4 * sizeof(WalkerK) + 8 * (np * 4 * npart + 2 * nb + np * 4 * kFmPropHost + 2 * nb + (cov_in_lds ? nb * nb : 0)) +
-           8 * (nb + 2) + 8 * (3 * 64) + 128 * np + 32;
-}
+
+// Every variant of the likelihood family that launch_packed starts has ONE slot: its kernel, its module handle and its
+// dynamic-LDS grant are filed under it.  Within a kind of kernel the model comes first -- (opthin ? 2 : 0) | (noalpha ? 1 : 0)
+// -- then the kind's own choices, `sub`:
+//   k_lnlike  2 x (SMODE 0, 1, 2, 6 as 0, 1, 2, 3) + staged      k_flowm, k_flowa  staged
+//   k_serve   2 x overlapped + staged
+enum KernelKind { kLnlike, kFlowm, kFlowa, kServe, kKinds };
+constexpr int kModels = 4;
+constexpr int kKindWidth[kKinds] = {8, 2, 2, 4};
+constexpr int kind_base(int k) { return k == 0 ? 0 : kind_base(k - 1) + kModels * kKindWidth[k - 1]; }
+constexpr int kNumSlots = kind_base(kKinds);
+constexpr int kernel_slot(KernelKind k, int model, int sub) { return kind_base(k) + model * kKindWidth[k] + sub; }
+
+#define MBB_MODELS(V) V(false, false), V(false, true), V(true, false), V(true, true)
+#define MBB_LNLIKE_V(OT, NA)                                                                            \
+    k_lnlike<OT, NA, 0, false>, k_lnlike<OT, NA, 0, true>, k_lnlike<OT, NA, 1, false>, k_lnlike<OT, NA, 1, true>, \
+        k_lnlike<OT, NA, 2, false>, k_lnlike<OT, NA, 2, true>, k_lnlike<OT, NA, 6, false>, k_lnlike<OT, NA, 6, true>
+#define MBB_FLOWM_V(OT, NA) k_flowm<OT, NA, false, 1>, k_flowm<OT, NA, true, 1>
+#define MBB_FLOWA_V(OT, NA) k_flowa<OT, NA, false>, k_flowa<OT, NA, true>
+#define MBB_SERVE_V(OT, NA) \
+    k_serve<OT, NA, false, false>, k_serve<OT, NA, true, false>, k_serve<OT, NA, false, true>, k_serve<OT, NA, true, true>
+static void (*const g_kernel[kNumSlots])(const LikeArgs) = {MBB_MODELS(MBB_LNLIKE_V), MBB_MODELS(MBB_FLOWM_V),
+                                                            MBB_MODELS(MBB_FLOWA_V), MBB_MODELS(MBB_SERVE_V)};
+#undef MBB_MODELS
+#undef MBB_LNLIKE_V
+#undef MBB_FLOWM_V
+#undef MBB_FLOWA_V
+#undef MBB_SERVE_V
 #include "mbb_host_tables.h"
 #include "mbb_registry.h"
 
@@ -241,9 +252,8 @@ struct mbb_ctx {
     unsigned long long buf_gen = 1;   // mbb_boundary_generation: bumped whenever the blocks below are freed and made anew
     double *call_in = nullptr;   // mbb_boundary_buffers: where the caller writes its rows (w_pars or h_pars)
     size_t call_cap = 0;         // ... and the capacity that answer was given for
-    hipFunction_t mod_fn[80] = {};   // launch_api 1: the kernels' module handles, by variant (32 k_lnlike, 8 k_flowm, 8 + 8 k_flowa (slots 40..55), 16 k_serve)
+    hipFunction_t mod_fn[kNumSlots] = {};   // the kernels' module handles, by slot (kernel_slot)
     hipEvent_t *launch_ev = nullptr; // != nullptr: two events to record right before and right behind the next launch
-    long opt_launch_api = 1;     // 1 hipModuleLaunchKernel with a packed argument buffer (-0.2 us per call, profiles/r04/boundary_breakdown.txt); 0 hipLaunchKernel
     double *d_gather = nullptr, *h_gather = nullptr;   // sharded boundary: every rank's lnprob, device / pinned landing place
     size_t gather_cap = 0;
     int large_bar = -1;
@@ -281,16 +291,14 @@ struct mbb_ctx {
     long opt_flow_min_steps = 2;   // runs shorter than this take the launch train (a one-launch run costs
                                    // ~14 us beside its steps: 16.9 us for one step against 15.7)
     long opt_xflow = 1;       // ... also for a sharded ensemble with the one-hop exchange (SMODE 6)
-    long opt_flow = 1;        // 1: ... as ONE launch per run, the half-steps handing over row by row (SMODE 5)
+    long opt_flow = 1;        // 1: ... as ONE launch per run, the half-steps handing over row by row (forms 6, 7, 9)
     long opt_flowm = 1;       // 1: ... with the quadrature of both candidates running ahead too (k_flowm, form 7)
     long opt_flowr = 1;       // 1: ensembles beyond one pair of walkers per CU run as ONE resident launch too, several walkers per
                               // workgroup, the SED constructor a half-step ahead for both outcomes of each partner's pending move
                               // (k_flowa, form 9); 0: off; 2: every eligible ensemble takes it
     long opt_flowr_walkers = 0;   // walkers per workgroup and half of that form (0: the host's choice, ceil(half / CUs))
                               // (ensembles of 258-512 walkers on 256 CUs); 1, 2 force it (testing)
-    long opt_la_waves = 0;
-    long opt_la_rows = 0;     // ... candidates per wave of the workgroups that do so (1, 2 or 4)
-    size_t lds_granted[112] = {};   // dynamic-LDS ceiling already requested, per kernel variant
+    size_t lds_granted[kNumSlots] = {};   // dynamic-LDS ceiling already requested, by slot (kernel_slot)
     long last_wpb = 0, last_threads = 0, last_grid = 0, last_smem = 0, last_smode = 0, last_ahead = 0;
     unsigned long long *d_stamps = nullptr;   // diagnostic build only
     // rccl
@@ -719,6 +727,8 @@ static size_t static_lds(const mbb_ctx *c)
            sizeof(double) * (c->opthin ? 2 : kPolyCDoubles);
 }
 static size_t dynamic_lds_limit(const mbb_ctx *c) { return 160 * 1024 - static_lds(c) - 2048; }
+// The model variant, the first index of every kernel table: (opthin ? 2 : 0) | (noalpha ? 1 : 0)
+static int model_of(const mbb_ctx *c) { return (c->opthin ? 2 : 0) | (c->noalpha ? 1 : 0); }
 
 // Dynamic LDS of a k_lnlike workgroup of `wpb` walkers, without the staged passband tables and without
 // the inverse covariance.
@@ -771,7 +781,7 @@ static void pick_geometry(const mbb_ctx *c, int n, int &wpb, int &threads, bool 
 }
 
 // Look-ahead sampler runs: how the workgroups that work ahead are shaped.  One row of 16 lanes
-// per candidate proposal -- 4 per walker of a half: a row keeps to one half (SMODE 5, 6) --
+// per candidate proposal -- 4 per walker of a half: a row keeps to one half (SMODE 6) --
 // `rows` of them per wave, `aw` such waves per
 // workgroup.  A constructor is one dependent chain and a wave alone on its SIMD runs it fastest,
 // so the candidates are spread as thinly as the CUs the movers leave free allow.
@@ -779,8 +789,7 @@ static void pick_geometry(const mbb_ctx *c, int n, int &wpb, int &threads, bool 
 // one-launch run is then slower than the launch train (480 walkers: 17.7 against 15.8 us per step;
 // 450 walkers, 32 per workgroup: 15.0 against 15.8 -- profiles/r03/walker_sweep.txt), so the host takes
 // the train from there (ensembles above ~454 walkers on 256 CUs).
-static bool lookahead_plan(const mbb_ctx *c, int movers, int threads, int half, int &rows, int &aw, int &n_ahead,
-                           bool *sparse = nullptr)
+static bool lookahead_plan(const mbb_ctx *c, int movers, int threads, int half, int &rows, int &aw, int &n_ahead)
 {
     const int pairs = 4 * half, free_cus = c->cu_count - movers;
     static const int plan[5][2] = {{1, 4}, {2, 4}, {4, 4}, {4, 8}, {4, 16}};
@@ -790,12 +799,8 @@ static bool lookahead_plan(const mbb_ctx *c, int movers, int threads, int half, 
         rows = plan[i][0]; aw = std::min(plan[i][1], threads / 64);
         if ((pairs + rows * aw - 1) / (rows * aw) <= free_cus) { chosen = i; break; }
     }
-    bool worth = chosen < 4;
-    if (sparse) *sparse = chosen <= 1;        // at most 8 candidates per working-ahead workgroup
-    if (c->opt_la_rows > 0) { rows = (int)(c->opt_la_rows == 4 ? 4 : (c->opt_la_rows == 2 ? 2 : 1)); worth = true; }
-    if (c->opt_la_waves > 0) { aw = (int)std::min<long>(c->opt_la_waves, threads / 64); worth = true; }
     n_ahead = (pairs + rows * aw - 1) / (rows * aw);
-    return worth;
+    return chosen < 4;
 }
 
 constexpr long kFlowStrikes = 3, kFlowRest = 16;
@@ -809,53 +814,52 @@ struct SamplerLaunch {
     int s_begin, c_begin, c_count, m_count, nw, step, half, nw_src;
     double stretch_a;
     unsigned long long seed;
-    unsigned long long xseq;      // > 0: one-hop exchange, number of this launch
-    int persist;                  // > 0: this many half-steps in one launch (SMODE 5, 6, form 7)
-    double *spec;                 // != nullptr: the one-launch run's device state
-    bool xflow = false;           // one-launch run of a sharded ensemble (SMODE 6): spec is the FlowX
-    bool merged = false;          // k_flowm (form 7): one workgroup per (pair of walkers, candidate)
-    bool resident = false;        // k_flowa (form 9): a workgroup owns several walkers of each half, every workgroup resident
-    int res_w = 1;                // ... walkers per workgroup and half
-    bool res_ahead = false;       // ... with the constructor a half-step ahead (k_flowa, form 9)
-    unsigned long long serial = 0;   // ... the number of its launch (in its check words and decision words)
+    // The sampler form, as last_kernel_form reports it: 1 the half-step (k_lnlike SMODE 1), 2 the half-step with the
+    // one-hop exchange (SMODE 2), 6 the one-launch run of a sharded ensemble (SMODE 6), 7 k_flowm, 9 k_flowa.
+    int form = 1;
+    int persist;                  // forms 6, 7, 9: this many half-steps in one launch
+    double *spec;                 // forms 6, 7, 9: the one-launch run's device state (form 6: the FlowX)
+    int res_w = 1;                // form 9: walkers per workgroup and half
+    unsigned long long serial = 0;   // forms 7, 9: the number of its launch (in its check words and decision words)
     int parity = 0;               // ... which of the two sets of completion counters it uses
 };
 
-// One launch of a kernel of the likelihood family.  launch_api 1 (default): the module-launch entry with the argument
-// block handed over as ONE packed buffer -- no per-argument marshalling in the runtime (A/B: tools/probe_boundary_breakdown.py,
-// profiles/r04/boundary_breakdown.txt); with c->launch_ev set, the launch that carries the two events itself.
-static int launch_packed(mbb_ctx *c, void (*kern)(const LikeArgs), int fn_slot, int grid, int threads, size_t smem, LikeArgs &a)
+// One launch of the kernel in `slot` (kernel_slot): the module-launch entry with the argument block handed over as ONE
+// packed buffer -- no per-argument marshalling in the runtime, 0.2 us per call less than hipLaunchKernel (A/B:
+// tools/probe_boundary_breakdown.py, profiles/r04/boundary_breakdown.txt); with c->launch_ev set, the launch that carries
+// the two events itself.
+static int launch_packed(mbb_ctx *c, int slot, int grid, int threads, size_t smem, LikeArgs &a)
 {
-    hipEvent_t *ev = c->launch_ev;
-    if (c->opt_launch_api == 1) {
-        hipFunction_t &f = c->mod_fn[fn_slot];
-        if (!f) HIPCHK(hipGetFuncBySymbol(&f, (const void *)kern));
-        size_t sz = sizeof(a);
-        void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        // (hipExtModuleLaunchKernel would take the two events with the launch -- the dispatch's own timestamps, no marker
-        // packets: measured, it costs 8 us MORE of host time per timed region than two hipEventRecord around the launch,
-        // profiles/r04/timed_region.txt)
-        if (ev) HIPCHK(hipEventRecord(ev[0], c->stream));
-        HIPCHK(hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, (unsigned)threads, 1, 1, (unsigned)smem, c->stream, nullptr, extra));
-        if (ev) HIPCHK(hipEventRecord(ev[1], c->stream));
-        return MBB_OK;
+    void (*const kern)(const LikeArgs) = g_kernel[slot];
+    if (static_lds(c) + smem > 60 * 1024) {
+        // beyond 64 KB of LDS per workgroup (static + dynamic) the kernel's dynamic-LDS
+        // ceiling has to be raised: once per context, variant and size, not per launch
+        size_t &g = c->lds_granted[slot];
+        if (smem > g) {
+            const size_t dyn_limit = dynamic_lds_limit(c);
+            size_t want = (smem + 16383) & ~(size_t)16383;
+            if (want > dyn_limit) want = dyn_limit;
+            HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
+            g = want;
+        }
     }
+    hipFunction_t &f = c->mod_fn[slot];
+    if (!f) HIPCHK(hipGetFuncBySymbol(&f, (const void *)kern));
+    hipEvent_t *ev = c->launch_ev;
+    size_t sz = sizeof(a);
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+    // (hipExtModuleLaunchKernel would take the two events with the launch -- the dispatch's own timestamps, no marker
+    // packets: measured, it costs 8 us MORE of host time per timed region than two hipEventRecord around the launch,
+    // profiles/r04/timed_region.txt)
     if (ev) HIPCHK(hipEventRecord(ev[0], c->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), smem, c->stream, a);
-    HIPCHK(hipGetLastError());
+    HIPCHK(hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, (unsigned)threads, 1, 1, (unsigned)smem, c->stream, nullptr, extra));
     if (ev) HIPCHK(hipEventRecord(ev[1], c->stream));
     return MBB_OK;
 }
 
-static int launch_lnlike(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
-                         int32_t *d_status, double *d_mflux, const SamplerLaunch *sl = nullptr)
+// The part of the argument block every kernel of the family reads alike: model, bands, data, limits and priors.
+static void fill_model_args(const mbb_ctx *c, LikeArgs &a)
 {
-    if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
-    if (c->data_nb != c->nb) return fail(MBB_ERR_STATE, "data not set or band count mismatch");
-    if (n <= 0) return MBB_OK;
-    LikeArgs a;
-    a.xargs = nullptr;
-    a.persist = 0; a.spec = nullptr;
     a.nu = c->d_nu; a.lnnu = c->d_lnnu; a.wt = c->d_wt;
     a.poly_b = c->d_poly_b; a.poly_c = c->d_poly_c;
     a.unit_tab = c->d_unit_tab; a.band_rng = c->d_band_rng; a.tail_slot = c->d_tail_slot;
@@ -866,15 +870,38 @@ static int launch_lnlike(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
     for (int i = 0; i < 5; ++i) a.lowlim[i] = c->lowlim[i];
     for (int i = 0; i < 6; ++i) { a.uplim[i] = c->uplim[i]; a.gmean[i] = c->gmean[i]; a.givar[i] = c->givar[i]; }
     a.has_uplim = c->has_uplim; a.has_gprior = c->has_gprior;
+    a.debug = (int)c->opt_debug;
+#ifdef MBB_STAMPS
+    a.stamps = c->d_stamps;
+#endif
+}
+
+// ... and what every sampler form reads of its launch
+static void fill_sampler_args(const SamplerLaunch &sl, LikeArgs &a)
+{
+    a.pos6 = sl.pos6; a.chain6 = sl.chain6; a.nacc = sl.nacc; a.errflag = sl.errflag;
+    a.s_begin = sl.s_begin; a.c_begin = sl.c_begin; a.c_count = sl.c_count; a.nw = sl.nw;
+    a.m_count = sl.m_count;
+    a.step = sl.step; a.half = sl.half; a.stretch_a = sl.stretch_a; a.seed = sl.seed;
+    a.nw_src = sl.nw_src;
+    a.persist = sl.persist;
+}
+
+static int launch_lnlike(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
+                         int32_t *d_status, double *d_mflux, const SamplerLaunch *sl = nullptr)
+{
+    if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
+    if (c->data_nb != c->nb) return fail(MBB_ERR_STATE, "data not set or band count mismatch");
+    if (n <= 0) return MBB_OK;
+    LikeArgs a;
+    fill_model_args(c, a);
+    a.xargs = nullptr;
+    a.persist = 0; a.spec = nullptr;
     a.pars = d_pars; a.n = n; a.lnl = d_lnl; a.status = d_status; a.model_flux = d_mflux;
     int wpb, threads;
     bool mid_staged = false;
     pick_geometry(c, n, wpb, threads, &mid_staged);
     a.wpb = wpb;
-    a.debug = (int)c->opt_debug;
-#ifdef MBB_STAMPS
-    a.stamps = c->d_stamps;
-#endif
     int grid = (n + wpb - 1) / wpb;
     const size_t cov_bytes = c->has_cov ? 8 * (size_t)c->nb * c->nb : 0;
     const size_t smem_base = lnlike_lds_base(c, wpb);
@@ -904,7 +931,7 @@ static int launch_lnlike(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
         a.xargs = nullptr;
         static void (*const ptable[4])(const LikeArgs) = {k_walker_pre<false, false>, k_walker_pre<false, true>,
                                                           k_walker_pre<true, false>, k_walker_pre<true, true>};
-        hipLaunchKernelGGL(ptable[(c->opthin ? 2 : 0) | (c->noalpha ? 1 : 0)], dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
+        hipLaunchKernelGGL(ptable[model_of(c)], dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
         HIPCHK(hipGetLastError());
         c->last_prepass = 1;
     }
@@ -927,154 +954,63 @@ static int launch_lnlike(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
     const size_t smem_total = smem + (stage ? table_bytes + 16 : 0);
     c->last_smem = (long)smem_total;
     c->last_stage = stage ? 1 : 0;
-    void (*kern)(const LikeArgs);
-    int vi_of_kernel = 0;
-    if (sl && sl->resident) {
-        // sampler form 9: ceil(n / W) workgroups of 16 waves, every one resident, W walkers of each half apiece
-        a.pos6 = sl->pos6; a.chain6 = sl->chain6; a.nacc = sl->nacc; a.errflag = sl->errflag;
-        a.s_begin = sl->s_begin; a.c_begin = sl->c_begin; a.c_count = sl->c_count; a.nw = sl->nw;
-        a.m_count = sl->m_count;
-        a.step = sl->step; a.half = sl->half; a.stretch_a = sl->stretch_a; a.seed = sl->seed;
-        a.nw_src = sl->nw_src;
-        a.persist = sl->persist;
-        a.flow_serial = c->flow_serial = sl->serial;
-        a.spec = sl->spec;
-        a.spec_cfg = (int)((c->opt_flow_spin_log2 & 0x3f) << 24) | (sl->parity & 1);
-        a.n_ahead = 0;
-        const int Wr = sl->res_w, wgs = (n + Wr - 1) / Wr, thr = 1024;
-        a.wpb = Wr;
-        auto lds_of = [&](bool cov) { return flowa_lds_bytes(c->nb, c->npart, cov, Wr); };
-        a.cov_in_lds = (c->has_cov && lds_of(true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
-        const size_t sm = lds_of(a.cov_in_lds != 0);
-        const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
-        const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
-        if (sm_total > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
-        if (wgs > c->cu_count || Wr > kFrMaxWHost)
-            return fail(MBB_ERR_ARG, "the one-launch sampler run needs every workgroup resident: too many for this GPU");
-        static void (*const rtable[8])(const LikeArgs) = {
-            k_flowa<false, false, false>, k_flowa<false, false, true>, k_flowa<false, true, false>, k_flowa<false, true, true>,
-            k_flowa<true, false, false>, k_flowa<true, false, true>, k_flowa<true, true, false>, k_flowa<true, true, true>};
-        const int ri = ((c->opthin ? 2 : 0) | (c->noalpha ? 1 : 0)) * 2 + (stg ? 1 : 0);
-        kern = rtable[ri];
-        c->last_wpb = Wr; c->last_threads = thr; c->last_grid = wgs; c->last_smem = (long)sm_total;
-        c->last_stage = stg ? 1 : 0; c->last_smode = 9; c->last_ahead = 0;
-        if (static_lds(c) + sm_total > 60 * 1024) {
-            size_t &g = c->lds_granted[72 + ri];
-            if (sm_total > g) {
-                size_t want = (sm_total + 16383) & ~(size_t)16383;
-                if (want > dyn_limit) want = dyn_limit;
-                HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
-                g = want;
-            }
-        }
-        return launch_packed(c, kern, 40 + ri, wgs, thr, sm_total, a);
-    }
-    if (sl && sl->merged) {
-        // sampler form 7: 2 n workgroups of (quadrature waves + 5), every one resident; its own LDS plan
-        a.pos6 = sl->pos6; a.chain6 = sl->chain6; a.nacc = sl->nacc; a.errflag = sl->errflag;
-        a.s_begin = sl->s_begin; a.c_begin = sl->c_begin; a.c_count = sl->c_count; a.nw = sl->nw;
-        a.m_count = sl->m_count;
-        a.step = sl->step; a.half = sl->half; a.stretch_a = sl->stretch_a; a.seed = sl->seed;
-        a.nw_src = sl->nw_src;
-        a.persist = sl->persist;
-        a.flow_serial = c->flow_serial = sl->serial;
-        a.spec = sl->spec;
-        a.spec_cfg = (int)((c->opt_flow_spin_log2 & 0x3f) << 24) | (sl->parity & 1);
-        a.n_ahead = 0;
-        const int nq = std::min(threads / 64, 11);
-        const int thr = (nq + 5) * 64;
-        const int np = 1;              // (round 3 also had two pairs of walkers per workgroup: superseded by form 9)
-        const int wgs = 2 * n;
-        a.cov_in_lds = (c->has_cov && flowm_lds_bytes(c->nb, c->npart, true, np) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
-        const size_t sm = flowm_lds_bytes(c->nb, c->npart, a.cov_in_lds != 0, np);
-        const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
-        const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
-        if (sm_total > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
-        if (wgs > c->cu_count)
-            return fail(MBB_ERR_ARG, "the one-launch sampler run needs every workgroup resident: too many for this GPU");
-        static void (*const mtable[8])(const LikeArgs) = {
-            k_flowm<false, false, false, 1>, k_flowm<false, false, true, 1>, k_flowm<false, true, false, 1>,
-            k_flowm<false, true, true, 1>, k_flowm<true, false, false, 1>, k_flowm<true, false, true, 1>,
-            k_flowm<true, true, false, 1>, k_flowm<true, true, true, 1>};
-        const int mi = ((c->opthin ? 2 : 0) | (c->noalpha ? 1 : 0)) * 2 + (stg ? 1 : 0);
-        kern = mtable[mi];
-        c->last_wpb = np; c->last_threads = thr; c->last_grid = wgs; c->last_smem = (long)sm_total;
-        c->last_stage = stg ? 1 : 0; c->last_smode = 7; c->last_ahead = 0;
-        if (static_lds(c) + sm_total > 60 * 1024) {
-            size_t &g = c->lds_granted[56 + mi];
-            if (sm_total > g) {
-                size_t want = (sm_total + 16383) & ~(size_t)16383;
-                if (want > dyn_limit) want = dyn_limit;
-                HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
-                g = want;
-            }
-        }
-        return launch_packed(c, kern, 32 + mi, wgs, thr, sm_total, a);
-    }
+    const int form = sl ? sl->form : 0;
     if (sl) {
-        a.pos6 = sl->pos6; a.chain6 = sl->chain6; a.nacc = sl->nacc; a.errflag = sl->errflag;
-        a.s_begin = sl->s_begin; a.c_begin = sl->c_begin; a.c_count = sl->c_count; a.nw = sl->nw;
-        a.m_count = sl->m_count;
-        a.step = sl->step; a.half = sl->half; a.stretch_a = sl->stretch_a; a.seed = sl->seed;
-        a.nw_src = sl->nw_src;
-        if (sl->xseq) a.xargs = c->x.d_args;
-        a.persist = sl->persist;
-        if (sl->spec) {
-            a.xargs = nullptr;
-            a.flow_serial = c->flow_serial = ++g_flow_serial;
-            // first the workgroups that prepare the next half-step -- one row of 16 lanes per
-            // (walker, candidate), `rows` of them per wave, `aw` such waves per workgroup -- then
-            // the movers.  A constructor is one dependent chain: a wave alone on its SIMD runs it
-            // fastest, so the candidates are spread as thinly as the CUs the movers leave free allow.
-            int rows, aw, n_ahead;
-            lookahead_plan(c, grid, threads, sl->m_count, rows, aw, n_ahead);
-            a.spec = sl->spec;
-            a.spec_cfg = (rows << 8) | (aw << 16) | (int)((c->opt_flow_spin_log2 & 0x3f) << 24);
-            a.n_ahead = n_ahead;
-            if (a.n_ahead + grid > c->cu_count)
-                return fail(MBB_ERR_ARG, "the one-launch sampler run needs every workgroup resident: too many for this GPU");
-            grid = a.n_ahead + grid;
-            c->last_grid = grid;
-        }
+        fill_sampler_args(*sl, a);
     } else {
         a.pos6 = nullptr; a.chain6 = nullptr; a.nacc = nullptr; a.errflag = nullptr;
         a.s_begin = a.c_begin = a.c_count = a.m_count = a.nw = a.step = a.half = 0;
         a.stretch_a = 2.0; a.seed = 0;
     }
-    {
-        // forms: 0 the likelihood of given rows, 1 the half-step, 2 the half-step with the one-hop
-        // exchange, 6 the one-launch look-ahead run across the ranks of a sharded ensemble (slot 3).
-        // (Its single-GPU twin, SMODE 5, went in round 4: forms 7 and 9 are faster at every ensemble size.)
-        const int smode = !sl ? 0 : (sl->spec ? 6 : (sl->xseq ? 2 : 1));
-        if (sl && sl->spec && !sl->xflow) return fail(MBB_ERR_STATE, "one-launch run without a form");
-        const int slot = smode == 6 ? 3 : smode;
-        const int vi = ((c->opthin ? 2 : 0) | (c->noalpha ? 1 : 0)) * 8 + slot * 2 + (stage ? 1 : 0);
-        c->last_smode = smode;
-        c->last_ahead = smode == 6 ? a.n_ahead : 0;
-        vi_of_kernel = vi;
-#define MBB_VARIANTS(OT, NA)                                                                        \
-    k_lnlike<OT, NA, 0, false>, k_lnlike<OT, NA, 0, true>, k_lnlike<OT, NA, 1, false>,              \
-        k_lnlike<OT, NA, 1, true>, k_lnlike<OT, NA, 2, false>, k_lnlike<OT, NA, 2, true>,           \
-        k_lnlike<OT, NA, 6, false>, k_lnlike<OT, NA, 6, true>
-        static void (*const table[32])(const LikeArgs) = {
-            MBB_VARIANTS(false, false), MBB_VARIANTS(false, true), MBB_VARIANTS(true, false),
-            MBB_VARIANTS(true, true)};
-#undef MBB_VARIANTS
-        kern = table[vi];
+    if (form == 7 || form == 9) {
+        // the resident sampler forms, every workgroup resident, each with its own LDS plan:
+        //   form 7 (k_flowm): 2 n workgroups of (quadrature waves + 5), one per (walker, candidate)
+        //   form 9 (k_flowa): ceil(n / W) workgroups of 16 waves, W walkers of each half apiece
+        a.flow_serial = c->flow_serial = sl->serial;
+        a.spec = sl->spec;
+        a.spec_cfg = (int)((c->opt_flow_spin_log2 & 0x3f) << 24) | (sl->parity & 1);
+        a.n_ahead = 0;
+        const bool fa = form == 9;
+        const int W = fa ? sl->res_w : 1;   // (round 3 also had two pairs of walkers per k_flowm workgroup: superseded by form 9)
+        const int wgs = fa ? (n + W - 1) / W : 2 * n;
+        const int thr = fa ? 1024 : (std::min(threads / 64, 11) + 5) * 64;
+        auto lds_of = [&](bool cov) { return fa ? flowa_lds(c->nb, c->npart, cov, W) : flowm_lds(c->nb, c->npart, cov); };
+        a.wpb = W;
+        a.cov_in_lds = (c->has_cov && lds_of(true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
+        const size_t sm = lds_of(a.cov_in_lds != 0);
+        const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
+        const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
+        if (sm_total > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
+        if (wgs > c->cu_count || W > kFaMaxW)
+            return fail(MBB_ERR_ARG, "the one-launch sampler run needs every workgroup resident: too many for this GPU");
+        c->last_wpb = W; c->last_threads = thr; c->last_grid = wgs; c->last_smem = (long)sm_total;
+        c->last_stage = stg ? 1 : 0; c->last_smode = form; c->last_ahead = 0;
+        return launch_packed(c, kernel_slot(fa ? kFlowa : kFlowm, model_of(c), stg ? 1 : 0), wgs, thr, sm_total, a);
     }
-    if (static_lds(c) + smem_total > 60 * 1024) {
-        // beyond 64 KB of LDS per workgroup (static + dynamic) the kernel's dynamic-LDS
-        // ceiling has to be raised: once per context, variant and size, not per launch
-        size_t &g = c->lds_granted[vi_of_kernel];
-        if (smem_total > g) {
-            size_t want = (smem_total + 16383) & ~(size_t)16383;
-            if (want > dyn_limit) want = dyn_limit;
-            HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)want));
-            g = want;
-        }
+    // k_lnlike, SMODE = form: 0 the likelihood of given rows, 1 the half-step, 2 the half-step with the one-hop exchange,
+    // 6 the one-launch look-ahead run across the ranks of a sharded ensemble (slot 3; its single-GPU twin went in round 4:
+    // forms 7 and 9 are faster at every ensemble size)
+    if (form == 2) a.xargs = c->x.d_args;
+    if (form == 6) {
+        a.flow_serial = c->flow_serial = ++g_flow_serial;
+        // first the workgroups that prepare the next half-step -- one row of 16 lanes per
+        // (walker, candidate), `rows` of them per wave, `aw` such waves per workgroup -- then
+        // the movers.  A constructor is one dependent chain: a wave alone on its SIMD runs it
+        // fastest, so the candidates are spread as thinly as the CUs the movers leave free allow.
+        int rows, aw, n_ahead;
+        lookahead_plan(c, grid, threads, sl->m_count, rows, aw, n_ahead);
+        a.spec = sl->spec;
+        a.spec_cfg = (rows << 8) | (aw << 16) | (int)((c->opt_flow_spin_log2 & 0x3f) << 24);
+        a.n_ahead = n_ahead;
+        if (a.n_ahead + grid > c->cu_count)
+            return fail(MBB_ERR_ARG, "the one-launch sampler run needs every workgroup resident: too many for this GPU");
+        grid = a.n_ahead + grid;
+        c->last_grid = grid;
     }
-    return launch_packed(c, kern, vi_of_kernel, grid, threads, smem_total, a);
+    c->last_smode = form;
+    c->last_ahead = form == 6 ? a.n_ahead : 0;
+    return launch_packed(c, kernel_slot(kLnlike, model_of(c), (form == 6 ? 3 : form) * 2 + (stage ? 1 : 0)), grid, threads,
+                         smem_total, a);
 }
 
 extern "C" int mbb_lnlike_batch_device(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
@@ -1220,7 +1156,7 @@ static int serve_stop(mbb_ctx *c)
         if (g_dev[c->device].server == c) g_dev[c->device].server = nullptr;
     }
     // a request number the server has not seen, with the row count that means "leave"
-    __atomic_store_n(c->w_door, (++c->srv_seq << 16) | kServeQuitHost, __ATOMIC_RELAXED);
+    __atomic_store_n(c->w_door, (++c->srv_seq << 16) | kServeQuit, __ATOMIC_RELAXED);
     __builtin_ia32_sfence();
     HIPCHK(hipStreamSynchronize(c->stream));
     return MBB_OK;
@@ -1252,27 +1188,15 @@ static int serve_launch(mbb_ctx *c, int n, unsigned long long word, int grid)
 
     LikeArgs a;
     memset(&a, 0, sizeof a);
-    a.nu = c->d_nu; a.lnnu = c->d_lnnu; a.wt = c->d_wt;
-    a.poly_b = c->d_poly_b; a.poly_c = c->d_poly_c;
-    a.unit_tab = c->d_unit_tab; a.band_rng = c->d_band_rng; a.tail_slot = c->d_tail_slot;
-    a.flux = c->d_flux; a.ivar = c->d_ivar; a.invcov = c->has_cov ? c->d_invcov : nullptr;
-    a.nb = c->nb; a.nunit = c->nunit; a.npart = c->npart; a.nchunk = c->nchunk;
-    a.nunorm = kUmToGHz / c->wavenorm;
-    a.lnunorm = log(a.nunorm);
-    for (int i = 0; i < 5; ++i) a.lowlim[i] = c->lowlim[i];
-    for (int i = 0; i < 6; ++i) { a.uplim[i] = c->uplim[i]; a.gmean[i] = c->gmean[i]; a.givar[i] = c->givar[i]; }
-    a.has_uplim = c->has_uplim; a.has_gprior = c->has_gprior;
+    fill_model_args(c, a);
     a.pars = c->w_pars; a.n = n; a.lnl = c->dv_srv; a.status = nullptr; a.model_flux = nullptr;
-    a.wpb = 1; a.debug = (int)c->opt_debug; a.nsrc = 1;
-#ifdef MBB_STAMPS
-    a.stamps = c->d_stamps;
-#endif
+    a.wpb = 1; a.nsrc = 1;
     int wpb, threads;
     pick_geometry(c, 1, wpb, threads);
     const size_t dyn_limit = dynamic_lds_limit(c);
     const size_t table_bytes = (size_t)c->nchunk * 64 * 3 * sizeof(double);
-    a.cov_in_lds = (c->has_cov && serve_lds_bytes(c->nb, c->npart, true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
-    const size_t sm = serve_lds_bytes(c->nb, c->npart, a.cov_in_lds != 0);
+    a.cov_in_lds = (c->has_cov && serve_lds(c->nb, c->npart, true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
+    const size_t sm = serve_lds(c->nb, c->npart, a.cov_in_lds != 0);
     const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
     // The quadrature beside the constructor (mbb_serve.hip.h): every wave but the first keeps both candidates of its own
     // unit's samples in registers
@@ -1289,25 +1213,11 @@ static int serve_launch(mbb_ctx *c, int n, unsigned long long word, int grid)
     a.pos6 = reinterpret_cast<double *>(c->w_door);
     a.seed = word;
     a.persist = (int)std::min<long>(std::max<long>(c->opt_serve_idle_us, 20), 1000000);
-#define MBB_SV(OT, NA) k_serve<OT, NA, false, false>, k_serve<OT, NA, true, false>, k_serve<OT, NA, false, true>, k_serve<OT, NA, true, true>
-    static void (*const stable[16])(const LikeArgs) = {MBB_SV(false, false), MBB_SV(false, true), MBB_SV(true, false), MBB_SV(true, true)};
-#undef MBB_SV
-    const int si = ((c->opthin ? 2 : 0) | (c->noalpha ? 1 : 0)) * 4 + (ovl ? 2 : 0) + (stg ? 1 : 0);
-    void (*kern)(const LikeArgs) = stable[si];
-    if (static_lds(c) + sm_total > 60 * 1024) {
-        size_t &g = c->lds_granted[96 + si];
-        if (sm_total > g) {
-            size_t want = (sm_total + 16383) & ~(size_t)16383;
-            if (want > dyn_limit) want = dyn_limit;
-            HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
-            g = want;
-        }
-    }
     *c->h_gone = 0;
     __atomic_store_n(c->w_door, word, __ATOMIC_RELAXED);
     __builtin_ia32_sfence();
     {
-        int rc = launch_packed(c, kern, 56 + si, grid, threads, sm_total, a);
+        int rc = launch_packed(c, kernel_slot(kServe, model_of(c), (ovl ? 2 : 0) + (stg ? 1 : 0)), grid, threads, sm_total, a);
         if (rc) return rc;
     }
     c->srv_grid = grid;
@@ -1706,7 +1616,7 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double 
     SamplerLaunch sl;
     sl.pos6 = s->d_pos6; sl.errflag = s->d_err; sl.nw = s->rows(); sl.nw_src = nw;
     sl.stretch_a = stretch_a; sl.c_count = half; sl.m_count = p.per;
-    sl.xseq = 0; sl.persist = 0;
+    sl.persist = 0;
     sl.spec = nullptr;
     // A sharded ensemble with the one-hop exchange, one launch per run (k_lnlike SMODE 6): every rank
     // moves its share of each half and prepares their proposals ahead, decisions / rows / words go
@@ -1725,7 +1635,7 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double 
             double *mine = c->x.flow(c->x.rank);
             const FlowView fvl = flow_view(mine, (int)R);
             sl.spec = reinterpret_cast<double *>(c->x.d_flowx);
-            sl.xflow = true;
+            sl.form = 6;
             for (int t0 = 0; t0 < nsteps; t0 += 4096) {
                 const int nt = std::min(4096, nsteps - t0);
                 FlowX fxh;
@@ -1772,17 +1682,16 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double 
     //           (train: 18.9 / 19.1 / 22.4 / 26.0);
     //           (round 4's form 8, k_flowr -- the same ownership, nothing ahead -- existed for 3073-4096 walkers only and was
     //           6 % ahead there, 35.5 against 37.6 us per step at 4096: removed in round 5, form 9 takes those too).
-    bool one_launch = c->opt_lookahead && c->opt_flow && p.shards == 1 && !p.collective && s->nsrc == 1 &&
-                      nsteps >= (int)std::max<long>(1, c->opt_flow_min_steps);
-    const bool merged = one_launch && c->opt_flowm && c->opt_flowr != 2 && 2 * (int)nl <= c->cu_count && wpb_1 == 1;
-    int res_w = c->opt_flowr_walkers > 0 ? (int)std::min<long>(c->opt_flowr_walkers, kFrMaxWHost)
-                                         : ((int)nl + c->cu_count - 1) / c->cu_count;
-    const bool res_fits = res_w >= 1 && res_w <= kFrMaxWHost && ((int)nl + res_w - 1) / res_w <= c->cu_count;
-    const bool resident = one_launch && !merged && c->opt_flowr != 0 && res_fits;
-    const bool res_ahead = true;
-    one_launch = merged || resident;
-    if (one_launch && c->flow_rest > 0) { --c->flow_rest; one_launch = false; }   // resting after give-ups in a row
-    if (one_launch) {
+    const bool one_launch = c->opt_lookahead && c->opt_flow && p.shards == 1 && !p.collective && s->nsrc == 1 &&
+                            nsteps >= (int)std::max<long>(1, c->opt_flow_min_steps);
+    const int res_w = c->opt_flowr_walkers > 0 ? (int)std::min<long>(c->opt_flowr_walkers, kFaMaxW)
+                                               : ((int)nl + c->cu_count - 1) / c->cu_count;
+    const bool res_fits = res_w >= 1 && res_w <= kFaMaxW && ((int)nl + res_w - 1) / res_w <= c->cu_count;
+    int form = 0;                                  // 7 or 9: the run as one launch per 4096 steps
+    if (one_launch && c->opt_flowm && c->opt_flowr != 2 && 2 * (int)nl <= c->cu_count && wpb_1 == 1) form = 7;
+    else if (one_launch && c->opt_flowr != 0 && res_fits) form = 9;
+    if (form && c->flow_rest > 0) { --c->flow_rest; form = 0; }   // resting after give-ups in a row
+    if (form) {
         const size_t R = (size_t)s->rows();
         if (!s->d_spec) {
             // zeroed: the records of a one-launch run are taken by their check words, and freshly
@@ -1790,53 +1699,49 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double 
             HIPCHK(hipMalloc((void **)&s->d_spec, spec_words(R) * sizeof(double)));
             HIPCHK(hipMemsetAsync(s->d_spec, 0, spec_words(R) * sizeof(double), c->stream));
         }
-        {
-            sl.spec = s->d_spec;
-            // what the run starts from, kept so that a run that times out (a workgroup that is not
-            // resident: another process on the GPU) can be redone as a launch train (mbb_sampler_run)
-            // (mbb_sampler_advance_async does not redo anything: no copy there)
-            if (backup) {
-                if (!s->d_bak) HIPCHK(hipMalloc((void **)&s->d_bak, R * 6 * sizeof(double) + R * sizeof(unsigned int)));
-                HIPCHK(hipMemcpyAsync(s->d_bak, s->d_pos6, R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(s->d_bak + R * 6, s->d_nacc, R * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
-            }
-            s->flow_used = backup;
-            if ((merged || resident) && s->spec_form != 7 && s->spec_form != 8) {
-                // forms 7 and 8 find their completion counters cleared by the launch before it (either's); after
-                // another form (or a run that gave up) has used the memory, once from here
-                const FlowMView fvh = flowm_view(s->d_spec, (int)R);
-                HIPCHK(hipMemsetAsync(fvh.done, 0, 2 * kFmRing * 16 * sizeof(unsigned long long), c->stream));
-                s->flowm_parity = 0;
-            }
-            s->spec_form = resident ? 8 : 7;
-            const bool carried = tev && nsteps <= 4096;
-            if (tev && !carried) HIPCHK(hipEventRecord(tev[0], c->stream));
-            for (int t0 = 0; t0 < nsteps; t0 += 4096) {
-                const int nt = std::min(4096, nsteps - t0);
-                // one launch, nothing before or after it: it files the rows it finds and stores the last ones back
-                sl.serial = ++g_flow_serial;
-                sl.parity = s->flowm_parity;
-                s->flowm_parity ^= 1;
-                sl.s_begin = 0; sl.c_begin = half; sl.step = t0; sl.half = 0;
-                sl.persist = 2 * nt;
-                sl.chain6 = store ? s->d_chain6 + ((size_t)t0 * 2 * nl) * 6 : nullptr;
-                sl.nacc = s->d_nacc;
-                sl.seed = s->seed + 0x9E3779B97F4A7C15ull * (s->steps_done + (unsigned long long)t0 + 1ull);
-                sl.merged = merged;
-                sl.resident = resident;
-                sl.res_w = res_w;
-                sl.res_ahead = res_ahead;
-                c->launch_ev = carried ? tev : nullptr;
-                rc = launch_lnlike(c, nullptr, (int)nl, nullptr, nullptr, nullptr, &sl);
-                c->launch_ev = nullptr;
-                if (rc) return rc;
-            }
-            if (tev && !carried) HIPCHK(hipEventRecord(tev[1], c->stream));
-            s->steps_done += (unsigned long long)nsteps;
-            return MBB_OK;
+        sl.spec = s->d_spec;
+        sl.form = form;
+        sl.res_w = res_w;
+        // what the run starts from, kept so that a run that times out (a workgroup that is not
+        // resident: another process on the GPU) can be redone as a launch train (mbb_sampler_run)
+        // (mbb_sampler_advance_async does not redo anything: no copy there)
+        if (backup) {
+            if (!s->d_bak) HIPCHK(hipMalloc((void **)&s->d_bak, R * 6 * sizeof(double) + R * sizeof(unsigned int)));
+            HIPCHK(hipMemcpyAsync(s->d_bak, s->d_pos6, R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(s->d_bak + R * 6, s->d_nacc, R * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
         }
+        s->flow_used = backup;
+        if (s->spec_form != 7 && s->spec_form != 9) {
+            // forms 7 and 9 find their completion counters cleared by the launch before it (either's); after
+            // another form (or a run that gave up) has used the memory, once from here
+            const FlowMView fvh = flowm_view(s->d_spec, (int)R);
+            HIPCHK(hipMemsetAsync(fvh.done, 0, 2 * kFmRing * 16 * sizeof(unsigned long long), c->stream));
+            s->flowm_parity = 0;
+        }
+        s->spec_form = form;
+        const bool carried = tev && nsteps <= 4096;
+        if (tev && !carried) HIPCHK(hipEventRecord(tev[0], c->stream));
+        for (int t0 = 0; t0 < nsteps; t0 += 4096) {
+            const int nt = std::min(4096, nsteps - t0);
+            // one launch, nothing before or after it: it files the rows it finds and stores the last ones back
+            sl.serial = ++g_flow_serial;
+            sl.parity = s->flowm_parity;
+            s->flowm_parity ^= 1;
+            sl.s_begin = 0; sl.c_begin = half; sl.step = t0; sl.half = 0;
+            sl.persist = 2 * nt;
+            sl.chain6 = store ? s->d_chain6 + ((size_t)t0 * 2 * nl) * 6 : nullptr;
+            sl.nacc = s->d_nacc;
+            sl.seed = s->seed + 0x9E3779B97F4A7C15ull * (s->steps_done + (unsigned long long)t0 + 1ull);
+            c->launch_ev = carried ? tev : nullptr;
+            rc = launch_lnlike(c, nullptr, (int)nl, nullptr, nullptr, nullptr, &sl);
+            c->launch_ev = nullptr;
+            if (rc) return rc;
+        }
+        if (tev && !carried) HIPCHK(hipEventRecord(tev[1], c->stream));
+        s->steps_done += (unsigned long long)nsteps;
+        return MBB_OK;
     }
-    sl.spec = nullptr; sl.merged = false; sl.resident = false; sl.persist = 0;
+    sl.spec = nullptr; sl.form = p.xchg ? 2 : 1; sl.persist = 0;
     if (tev && !p.xchg) HIPCHK(hipEventRecord(tev[0], c->stream));
     for (int t = 0; t < nsteps; ++t)
         for (int h = 0; h < 2; ++h) {
@@ -1848,7 +1753,7 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double 
                 sl.nacc = s->d_nacc + ((size_t)r * 2 + h) * nl;
                 // the RNG key advances over the whole life of the sampler, the chain index restarts
                 sl.seed = s->seed + 0x9E3779B97F4A7C15ull * (s->steps_done + (unsigned long long)t + 1ull);
-                sl.xseq = p.xchg ? ++c->x.seq : 0;
+                if (p.xchg) ++c->x.seq;
                 if ((rc = launch_lnlike(c, nullptr, (int)nl, nullptr, nullptr, nullptr, &sl))) return rc;
             }
             if (p.collective && !p.xchg &&
@@ -2355,7 +2260,6 @@ extern "C" int mbb_set_option(mbb_ctx *c, const char *name, long value)
     else if (!strcmp(name, "spin_budget")) c->opt_spin_budget = value < 0 ? 0 : value;
     else if (!strcmp(name, "pack_tails")) c->opt_pack_tails = value;
     else if (!strcmp(name, "bar_params")) c->opt_bar_params = value;
-    else if (!strcmp(name, "launch_api")) c->opt_launch_api = value;
     else if (!strcmp(name, "serve_overlap")) c->opt_serve_overlap = value;
     else if (!strcmp(name, "serve")) { c->opt_serve = value; c->srv_strikes = 0; c->srv_rest = 0; }
     else if (!strcmp(name, "serve_after")) { c->opt_serve_after = value < 1 ? 1 : value; c->srv_need = 0; }
@@ -2372,12 +2276,9 @@ extern "C" int mbb_set_option(mbb_ctx *c, const char *name, long value)
     else if (!strcmp(name, "merged_flow_sampler")) c->opt_flowm = value;
     else if (!strcmp(name, "resident_sampler")) c->opt_flowr = value;
     else if (!strcmp(name, "resident_walkers")) c->opt_flowr_walkers = value;
-    else if (!strcmp(name, "resident_ahead")) { /* (round 4's choice between forms 8 and 9: form 8 is gone, accepted and ignored) */ }
     else if (!strcmp(name, "flow_spin_log2")) c->opt_flow_spin_log2 = value;
     else if (!strcmp(name, "flow_min_steps")) c->opt_flow_min_steps = value;
     else if (!strcmp(name, "sharded_flow_sampler")) c->opt_xflow = value;
-    else if (!strcmp(name, "lookahead_rows")) c->opt_la_rows = value;
-    else if (!strcmp(name, "lookahead_waves")) c->opt_la_waves = value;
     else if (!strcmp(name, "roof_wgs_per_cu")) c->opt_roof_wgs = value;
     else if (!strcmp(name, "roof_threads")) c->opt_roof_threads = value;
     else return fail(MBB_ERR_ARG, "unknown option");

@@ -7,13 +7,14 @@
 // k_sed_integrate  freq_integrate for n rows
 // k_fnu_explicit fnu.pyx's four functions with explicit scalars
 //
-// Included by mbb_hip.hip (the C-ABI / host side) only.
+// Included by mbb_hip.hip (the C-ABI / host side) and mbb_flow.hip (the one-launch kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "mbb_device.hip.h"
 #include "mbb_flow_index.h"
+#include "mbb_lds_plans.hip.h"
 
 using namespace mbbd;
 
@@ -69,8 +70,8 @@ struct LikeArgs {
     // batch
     union {
         const double *pars;   // [n*5]  (SMODE 0)
-        unsigned long long flow_serial;   // SMODE 5: number of this launch in the context's life, in the
-                              // check words of the records (a record left by an earlier run never fits)
+        unsigned long long flow_serial;   // SMODE 6, forms 7, 9: number of this launch in the process's life, in
+                              // the check words of the records (a record left by an earlier run never fits)
     };
     int n;
     int wpb;                  // walkers per block
@@ -95,8 +96,8 @@ struct LikeArgs {
     int step, half;
     // (arguments of variants that never meet share storage, so that the block stays at 480
     // bytes for every variant)
-    int persist;              // SMODE 5, 6, form 7: half-steps in this launch (step = number of the first step)
-    double *spec;             // SMODE 5, 6, form 7: the one-launch run's device state (FlowView / FlowX / FlowMView)
+    int persist;              // SMODE 6, forms 7, 9: half-steps in this launch (step = number of the first step)
+    double *spec;             // SMODE 6, forms 7, 9: the one-launch run's device state (FlowX / FlowMView)
     // ---- independent sources sharing the band tables (cfg5): flux/ivar are
     // [nsrc*nb]; plain mode: source = row / rows_per_src; sampler mode: the state is
     // [nsrc][nw_src][6] and a launch covers nsrc * c_count walkers
@@ -109,12 +110,12 @@ struct LikeArgs {
     // tools/lat_kernarg.hip, profiles/r02/lat_kernarg.txt)
     union {
         const XchgArgs *xargs;
-        // ---- one-launch runs (SMODE 5, 6, form 7): see k_lnlike, k_flowm
+        // ---- one-launch runs (SMODE 6, forms 7, 9): see k_lnlike, k_flowm, k_flowa
         struct {
-            int spec_cfg;     // bit 0: form 7, which of the two sets of completion counters this launch uses;
-                              // bits 8-15: candidates per wave (1, 2 or 4 rows of 16 lanes),
-                              // bits 16-23: waves of a workgroup working ahead that take candidates,
-                              // bits 24-31: SMODE 5, log2 of the polls before a wait gives up (0: 22)
+            int spec_cfg;     // bit 0: forms 7, 9, which of the two sets of completion counters this launch uses;
+                              // bits 8-15: SMODE 6, candidates per wave (1, 2 or 4 rows of 16 lanes),
+                              // bits 16-23: SMODE 6, waves of a workgroup working ahead that take candidates,
+                              // bits 24-31: log2 of the polls before a wait gives up (0: 22)
             int n_ahead;      // workgroups 0 .. n_ahead-1 work ahead (dispatched first: theirs is the
                               // longer path), the rest move walkers
         };
@@ -137,7 +138,7 @@ static_assert(sizeof(LikeArgs) == 480, "the argument block: every launch of ever
 #endif
 // Device state of a one-launch run, one allocation of 8-byte words (nw = state rows).
 // A record: WalkerK (13 words), proposal (5), 4 ln z, ln u, the two penalties = 22 elements.
-// SMODE 5 (FlowView): everything a row publishes is indexed by the number m of the move it
+// SMODE 6 (FlowView): everything a row publishes is indexed by the number m of the move it
 // belongs to, mod kFlowSlots -- a mover more than four half-steps ahead of the slowest waits, so
 // four slots are never overwritten under a reader:
 //   rec   [nw][kFlowSlots][2][kFlowRec]  the proposal records of move m, one per candidate: word
@@ -205,7 +206,7 @@ __device__ __forceinline__ void st_dev(double *p, double v)    // device-scope: 
 }
 
 // ---------------------------------------------------------------------------
-// Role-local view of the kernel arguments (the one-launch sampler kernels: k_lnlike SMODE 5/6, k_flowm).
+// Role-local view of the kernel arguments (the one-launch sampler kernels: k_lnlike SMODE 6, k_flowm, k_flowa).
 // Their workgroups or waves take roles that share one kernel and one 480-byte argument block, and the
 // compiler fetches a by-value kernel argument where the function begins: every field any role touches is
 // then live in scalar registers across the branch to the roles -- far more than the 102 there are -- and
@@ -284,40 +285,35 @@ __device__ __forceinline__ void stretch_draw(int row, int step, int half, unsign
 // sharded run with the one-hop exchange (its own instantiation: carried as run-time
 // branches and extra arguments in the single-GPU sampler kernel it cost that kernel 0.75 us
 // per launch).
-// 5 and 6, the one-launch look-ahead run: a whole run of half-steps in ONE
-// launch, every workgroup resident; the proposals of the NEXT half-step -- draw, SED constructor,
-// penalties -- are prepared while this one is being decided, for both outcomes of each partner's
-// pending move, by workgroups of their own (blockIdx < n_ahead); a mover picks the record its
-// partner's decision points at and starts at the quadrature; a row's half-step starts when the
-// rows it depends on are done (FlowView: per-row words polled with bounded spins, write-through
-// stores, no grid-wide barrier).  6: the same across the ranks of a sharded ensemble.  Bitwise the
-// chain of SMODE 1; 9.9 us per step against 15.6.
+// 6, the one-launch look-ahead run of a sharded ensemble: a whole run of
+// half-steps in ONE launch per rank, every workgroup resident; the proposals of the NEXT half-step --
+// draw, SED constructor, penalties -- are prepared while this one is being decided, for both outcomes
+// of each partner's pending move, by workgroups of their own (blockIdx < n_ahead); a mover picks the
+// record its partner's decision points at and starts at the quadrature; a row's half-step starts when
+// the rows it depends on are done, on whatever GPU (FlowView: per-row words polled with bounded spins,
+// system-scope stores into every rank's copy, no grid-wide barrier).  Bitwise the chain of SMODE 1.
 // (Rounds 1-2 also had SMODE 3, a one-launch run behind a grid-wide hand-off, and SMODE 4, the
 // look-ahead as extra workgroups of every launch of a train: both measured slower than what
-// replaced them -- profiles/r02/persistent_sampler.txt, lookahead_notes.txt -- and removed in round 3.)
+// replaced them -- profiles/r02/persistent_sampler.txt, lookahead_notes.txt -- and removed in round 3.
+// Round 4 removed the single-GPU twin of SMODE 6: forms 7 and 9, k_flowm and k_flowa, are faster.)
 template <bool OPTHIN, bool NOALPHA, int SMODE, bool STAGE>
 __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
 {
-    static_assert(SMODE == 0 || SMODE == 1 || SMODE == 2 || SMODE == 5 || SMODE == 6, "no such sampler form");
-    constexpr bool SAMPLER = SMODE != 0, XCHG = SMODE == 2, XF = SMODE == 6, FLOW = SMODE == 5 || XF;
+    static_assert(SMODE == 0 || SMODE == 1 || SMODE == 2 || SMODE == 6, "no such sampler form");
+    // FLOW: SMODE 6, the one-launch run of a sharded ensemble
+    constexpr bool SAMPLER = SMODE != 0, XCHG = SMODE == 2, FLOW = SMODE == 6;
     // The one-launch forms have two kinds of workgroups (movers, and those that work ahead) in one kernel:
     // they read the argument block through role-local views (see MBB_ROLE_ARGS); the others take it by value.
     CLikeArgs *const ka = MBB_KERNARGS();
     auto &a = *[&]() { if constexpr (FLOW) return role_args(ka); else return &a_val; }();
-    // SMODE 6, the one-launch run of a sharded ensemble: this rank's copy of the run's state and
-    // its peers'; words and rows that cross GPUs are read and written at system scope
-    const FlowX *const fx = XF ? reinterpret_cast<const FlowX *>(a.spec) : nullptr;
-    const int npeer = XF ? fx->n : 1, xrank = XF ? fx->rank : 0;
-    auto peer_view = [&](int pr) { return flow_view(XF ? fx->base[pr] : a.spec, a.nw); };
-    auto fl_ld = [&](const double *q) { if constexpr (XF) return ld_sys(q); else return ld_dev(q); };
-    auto fl_st = [&](double *q, double v) { if constexpr (XF) st_sys(q, v); else st_dev(q, v); };
-    auto fl_ldw = [&](const unsigned long long *q) {
-        if constexpr (XF) return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        else return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    // SMODE 6: this rank's copy of the run's state and its peers'; words and rows that cross GPUs are
+    // read and written at system scope (ld_sys, st_sys, and these two for the words)
+    const FlowX *const fx = FLOW ? reinterpret_cast<const FlowX *>(a.spec) : nullptr;
+    const int npeer = FLOW ? fx->n : 1, xrank = FLOW ? fx->rank : 0;
+    auto peer_view = [&](int pr) { return flow_view(fx->base[pr], a.nw); };
+    auto fl_ldw = [&](const unsigned long long *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
     auto fl_stw = [&](unsigned long long *q, unsigned long long v) {
-        if constexpr (XF) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        else __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     };
     extern __shared__ __align__(16) unsigned char smem_raw[];
     __shared__ __align__(16) double s_tab[kExp2N];                     // 2^(j/256) for the sample loop
@@ -346,7 +342,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
     double *s_lnnu = s_nu + (STAGE ? a.nchunk * 64 : 0);
     double *s_wt = s_lnnu + (STAGE ? a.nchunk * 64 : 0);
     const int w0 = (FLOW ? (int)blockIdx.x - a.n_ahead : (int)blockIdx.x) * W;
-    // SMODE 5: polls before a wait gives up and ends the run with error 9 (~1.5 us each)
+    // SMODE 6: polls before a wait gives up and ends the run with error 9 (~1.5 us each)
     // (taken from the argument block where it is needed, not kept in registers across the chains; once
     // the error flag is up, every wait notices within a few polls and the run drains)
 #define MBB_FLOW_SPIN_LIMIT (1ll << (((a.spec_cfg >> 24) & 0x3f) ? ((a.spec_cfg >> 24) & 0x3f) : 22))
@@ -403,7 +399,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
             const bool active = wave < aw && (lane >> 4) < rpw && pair < 4 * a.m_count;
             const int loc = pair >> 2, cand = pair & 1;
             if (wave >= aw) return;                           // nothing is shared, spare waves leave
-            // SMODE 5: half-step j of the run is prepared as soon as the rows it starts from are
+            // half-step j of the run is prepared as soon as the rows it starts from are
             // there -- the state as of the start of half-step j - 1 -- while j - 1 is still moving
             const FlowView fv = peer_view(xrank);
             const int nj = a.persist;
@@ -469,15 +465,13 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                     }
                     return v;
                 };
-                // A row's last proposal comes from its record where that is on this GPU (always the
-                // walker's own; its partner's partner's unless the run is sharded): the candidate its
-                // mover took is the one the earlier decision of ITS partner says.  A row of another
-                // rank's has no record here: its proposal is formed again from the row it was
+                // The walker's own last proposal comes from its record: the candidate its mover took is
+                // the one the earlier decision of ITS partner says.  Its partner's partner may be another
+                // rank's row, which has no record here: that proposal is formed again from the row it was
                 // proposed from, which has to have landed.
-                constexpr bool rec_r = true, rec_p = !XF;
                 // (1) what was settled a half-step or more ago, one lane of the row each:
-                //  0, 1: for the two rows, that earlier decision (record) or the landing of the row the
-                //        move m_s was proposed from
+                //  0   : for the walker, that earlier decision (record);  1: for its partner's partner, the
+                //        landing of the row the move m_s was proposed from
                 //  2   : the partner's row before its pending move;  3, 4: the two rows before move m_s
                 const unsigned long long *w1 = fv.seq;
                 unsigned long long n1 = 0;
@@ -488,11 +482,11 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                     const unsigned long long nold = (unsigned long long)flow_seq(hj, m_s - 1);
                     switch (l16) {
                     case 0:
-                        w1 = rec_r ? fv.mseq + (size_t)(ob + qr) * kFlowSlots + (m_q % kFlowSlots) : fv.seq + (ob + qr);
-                        n1 = nq; sh1 = rec_r ? 1 : 0; watch1 = m_s > 0 && m_q > 0; break;
+                        w1 = fv.mseq + (size_t)(ob + qr) * kFlowSlots + (m_q % kFlowSlots);
+                        n1 = nq; sh1 = 1; watch1 = m_s > 0 && m_q > 0; break;
                     case 1:
-                        w1 = rec_p ? fv.mseq + (size_t)(ob + qp) * kFlowSlots + (m_q % kFlowSlots) : fv.seq + (ob + qp);
-                        n1 = nq; sh1 = rec_p ? 1 : 0; watch1 = c1 && m_s > 0 && m_q > 0; break;
+                        w1 = fv.seq + (ob + qp);
+                        n1 = nq; sh1 = 0; watch1 = c1 && m_s > 0 && m_q > 0; break;
                     case 2: w1 = fv.seq + prow; n1 = (unsigned long long)flow_seq(hj ^ 1, m_o); watch1 = m_o > 0; break;
                     case 3: w1 = fv.seq + rown; n1 = nold; watch1 = m_s > 1; break;
                     case 4: w1 = fv.seq + pprow; n1 = nold; watch1 = c1 && m_s > 1; break;
@@ -500,8 +494,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                     }
                 }
                 const unsigned long long v1 = spin(w1, n1, watch1, sh1);
-                const int cr = (rec_r && m_s > 0 && m_q > 0) ? (int)(__shfl(v1, base + 0) & 1ull) : 0;
-                const int cp = (rec_p && m_s > 0 && m_q > 0) ? (int)(__shfl(v1, base + 1) & 1ull) : 0;
+                const int cr = (m_s > 0 && m_q > 0) ? (int)(__shfl(v1, base + 0) & 1ull) : 0;
                 // the rows -> this row's corner of LDS (the polynomial table's place), an element or
                 // two per lane: [0,5) the walker's row as it was, [5,10) the row its last move was
                 // proposed from, [10,20) the same two for the partner's partner, [20,25) the partner
@@ -511,12 +504,10 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                     if (active) {
                         const int so = (m_s > 0 ? m_s - 1 : 0) % kFlowSlots, sq = m_q % kFlowSlots;
                         const double *o_r = fv.st + ((size_t)so * a.nw + rown) * 8, *o_p = fv.st + ((size_t)so * a.nw + pprow) * 8;
-                        // the proposal of move m_s: elements 13..17 of the record (each with its check
-                        // word), or the row it was proposed from
-                        const double *n_r = rec_r ? fv.rec + (((size_t)rown * kFlowSlots + (m_s % kFlowSlots)) * 2 + cr) * kFlowRec + 26
-                                                  : fv.st + ((size_t)sq * a.nw + ob + qr) * 8;
-                        const double *n_p = rec_p ? fv.rec + (((size_t)pprow * kFlowSlots + (m_s % kFlowSlots)) * 2 + cp) * kFlowRec + 26
-                                                  : fv.st + ((size_t)sq * a.nw + ob + qp) * 8;
+                        // the proposal of move m_s: for the walker, elements 13..17 of the record (each with
+                        // its check word); for its partner's partner, the row it was proposed from
+                        const double *n_r = fv.rec + (((size_t)rown * kFlowSlots + (m_s % kFlowSlots)) * 2 + cr) * kFlowRec + 26;
+                        const double *n_p = fv.st + ((size_t)sq * a.nw + ob + qp) * 8;
                         const double *sp = fv.st + ((size_t)(m_o % kFlowSlots) * a.nw + prow) * 8;
                         const unsigned long long tag_g = (a.flow_serial << 32) | (unsigned long long)(g + 1);
 #pragma unroll
@@ -524,7 +515,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                             const int e = l16 + 16 * t;
                             if (e < 25) {
                                 const int grp = e / 5, i = e - 5 * grp;
-                                const bool from_rec = (grp == 1 && rec_r) || (grp == 3 && rec_p);
+                                const bool from_rec = grp == 1;
                                 const double *src = grp == 0 ? o_r : (grp == 1 ? n_r : (grp == 2 ? o_p : (grp == 3 ? n_p : sp)));
                                 const bool want = grp == 0 || grp == 4 || (grp == 1 && m_s > 0) || (grp == 2 && c1) || (grp == 3 && c1 && m_s > 0);
                                 double v = 0.0;
@@ -534,7 +525,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                                                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                     bad = bad || (chk ^ (unsigned long long)__double_as_longlong(v)) != tag_g;
                                 } else if (want) {
-                                    v = fl_ld(src + i);
+                                    v = ld_sys(src + i);
                                 }
                                 scr[e] = v;
                             }
@@ -546,14 +537,12 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                     if (tries > MBB_FLOW_SPIN_LIMIT) { atomicMax(a.errflag, 9); break; }
                     __builtin_amdgcn_s_sleep(1);
                 }
-                // a proposal that did not come from a record is formed now, in place of the row it
-                // was proposed from: after the decisions only a selection is left
+                // the partner's partner's proposal, which did not come from a record, is formed now, in
+                // place of the row it was proposed from: after the decisions only a selection is left
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 if (active && m_s > 0 && l16 < 10) {
-                    const int i = l16 < 5 ? l16 : l16 - 5, o = l16 < 5 ? 0 : 10;
-                    if ((l16 < 5 && !rec_r) || (l16 >= 5 && c1 && !rec_p))
-                        scr[o + 5 + i] = stretch_q(scr[o + 5 + i], scr[o + i], l16 < 5 ? zr : zq);
+                    if (l16 >= 5 && c1) scr[10 + l16] = stretch_q(scr[10 + l16], scr[5 + l16], zq);   // elements [15, 20)
                 }
                 // (2) the decisions of half-step j - 2 (lanes 0, 1): the hand-off this chain waits for
                 const unsigned long long *w2 = fv.mseq + (size_t)(l16 == 0 ? rown : pprow) * kFlowSlots + (m_s % kFlowSlots);
@@ -731,7 +720,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
 
     // FLOW: a.persist half-steps in this launch; otherwise one pass with the launch's values
     const int niter = FLOW ? a.persist : 1;
-    // SMODE 5, wave 0: the workgroup's two walkers (one of each half) as they are, element l in
+    // FLOW, wave 0: the workgroup's two walkers (one of each half) as they are, element l in
     // lane l < 8 -- nobody else writes them; and the row whose word is still to be published
     double own_half[2] = {0.0, 0.0};
     int pend_row = -1, pend_it = 0;
@@ -758,7 +747,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
             double r0 = 0.0, r1 = 0.0, flag = 0.0;
             {
                 STAMP(11);
-                // SMODE 5: this half-step starts when both candidates of the walker's record are
+                // this half-step starts when both candidates of the walker's record are
                 // there and its partner's move of the half-step before is decided (and nobody is
                 // more than four half-steps behind: the state slots and the records are reused)
                 double zz, u3;
@@ -771,13 +760,13 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                 // lane 23 the lag guard.  When all of it is there already, that is one round trip.
                 const unsigned long long tag = (a.flow_serial << 32) | (unsigned long long)(it + 1);
                 const unsigned long long need_p = (unsigned long long)flow_seq(L_half ^ 1, m_par);
-                // lane 23: this GPU's count of half-step it - kFlowLag (the lag guard); a sharded run
-                // besides: lanes 24 ..: the other ranks' words for that half-step (whichever of a
-                // rank's movers completes a half-step last tells them), lanes 40 .. (first half-step):
-                // every peer has set up its copy of this run
+                // lane 23: this GPU's count of half-step it - kFlowLag (the lag guard); lanes 24 ..: the
+                // other ranks' words for that half-step (whichever of a rank's movers completes a
+                // half-step last tells them), lanes 40 .. (first half-step): every peer has set up its
+                // copy of this run
                 const int gl = lane - 24, sl = lane - 40;
-                const bool guard = XF && gl >= 0 && gl < npeer && gl != xrank && it >= kFlowLag;
-                const bool started = XF && it == 0 && sl >= 0 && sl < npeer;
+                const bool guard = gl >= 0 && gl < npeer && gl != xrank && it >= kFlowLag;
+                const bool started = it == 0 && sl >= 0 && sl < npeer;
                 const unsigned long long need_g =
                     started ? fx->run : (guard ? (unsigned long long)(it - kFlowLag + 1)
                                                : (unsigned long long)a.n * (unsigned long long)(((it - kFlowLag) >> 3) + 1));
@@ -811,21 +800,16 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                         // and the loads above came after those stores; the explicit wait costs nothing
                         // then.  Its word, for the workgroups that work ahead from that row.
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        if (XF) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");     // across GPUs: a full release
-                        if (XF && lane < npeer) fl_stw(peer_view(lane).seq + pend_row, (unsigned long long)(pend_it + 1));
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");     // across GPUs: a full release
+                        if (lane < npeer) fl_stw(peer_view(lane).seq + pend_row, (unsigned long long)(pend_it + 1));
                         if (lane == 0) {
-                            if (!XF) fl_stw(fv.seq + pend_row, (unsigned long long)(pend_it + 1));
-                            if constexpr (XF) {
-                                if (cnt_it >= 0 && cnt_seen + 1 == (unsigned long long)a.n * (unsigned long long)((cnt_it >> 3) + 1))
-                                    for (int pr = 0; pr < npeer; ++pr)
-                                        if (pr != xrank)
-                                            fl_stw(peer_view(pr).pub + xrank * 8 + (cnt_it & 7), (unsigned long long)(cnt_it + 1));
-                                cnt_seen = __hip_atomic_fetch_add(fv.done + (pend_it & 7) * 16, 1ull, __ATOMIC_RELAXED,
-                                                                  __HIP_MEMORY_SCOPE_AGENT);
-                                cnt_it = pend_it;
-                            } else {
-                                __hip_atomic_fetch_add(fv.done + (pend_it & 7) * 16, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
+                            if (cnt_it >= 0 && cnt_seen + 1 == (unsigned long long)a.n * (unsigned long long)((cnt_it >> 3) + 1))
+                                for (int pr = 0; pr < npeer; ++pr)
+                                    if (pr != xrank)
+                                        fl_stw(peer_view(pr).pub + xrank * 8 + (cnt_it & 7), (unsigned long long)(cnt_it + 1));
+                            cnt_seen = __hip_atomic_fetch_add(fv.done + (pend_it & 7) * 16, 1ull, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT);
+                            cnt_it = pend_it;
                         }
                         pend_row = -1;
                     }
@@ -839,7 +823,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                     __builtin_amdgcn_s_sleep(1);
                 }
                 if (it < 2) {
-                    if (lane < 8) own_reg = fl_ld(fv.st + (size_t)row * 8 + lane);
+                    if (lane < 8) own_reg = ld_sys(fv.st + (size_t)row * 8 + lane);
                 } else {
                     own_reg = L_half ? own_half[1] : own_half[0];
                 }
@@ -1203,22 +1187,10 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                                                    __HIP_MEMORY_SCOPE_SYSTEM);
                     }
                 } else if (FLOW) {
-                    // the decision first -- all the partner's next mover waits for --, then the row
-                    // as it is after this half-step, write-through, to its next slot (every rank's
-                    // copy in a sharded run); the row's own word follows at the start of the next
-                    // half-step, when the stores have landed.  pos6 is brought up to date once, when
+                    // the decision and the row as it is after this half-step go to every rank's copy of
+                    // the run's state below, a lane per rank; the row's own word follows at the start of
+                    // the next half-step, when the stores have landed.  pos6 is brought up to date once, when
                     // the launch has ended (k_flow_finish); counts and chain are for the host: plain stores.
-                    const FlowView fv = peer_view(xrank);
-                    const int m_new = flow_cnt(L_half, it) + 1;
-                    if constexpr (!XF)
-                        fl_stw(fv.mseq + (size_t)row * kFlowSlots + (m_new % kFlowSlots),
-                               2ull * (unsigned long long)(it + 1) + (accept ? 1ull : 0ull));
-                    if constexpr (!XF) {
-                        double *dst = fv.st + ((size_t)(m_new % kFlowSlots) * a.nw + row) * 8;
-#pragma unroll
-                        for (int i = 0; i < 5; ++i) fl_st(dst + i, accept ? q[i] : old5[i]);
-                        fl_st(dst + 5, accept ? r : q[6]);
-                    }                                          // (a sharded run: below, a lane per rank)
                     if (accept) atomicAdd(&L_nacc[w], 1u);
                     if (L_chain6) {
                         double *crow = L_chain6 + (size_t)w * 6;
@@ -1249,12 +1221,11 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
         if constexpr (FLOW) {
             // the walker as it is now stays in this wave's registers for its next half-step
             const int acc_u = __builtin_amdgcn_readfirstlane(flow_accept);
-            if constexpr (XF) {
-                // the decision, into every rank's copy at once (lane pr stores to rank pr)
-                if (lane < npeer)
-                    fl_stw(peer_view(lane).mseq + (size_t)row_first * kFlowSlots + ((flow_cnt(L_half, it) + 1) % kFlowSlots),
-                           2ull * (unsigned long long)(it + 1) + (acc_u ? 1ull : 0ull));
-            }
+            // the decision first -- all the partner's next mover waits for --, into every rank's copy at
+            // once (lane pr stores to rank pr)
+            if (lane < npeer)
+                fl_stw(peer_view(lane).mseq + (size_t)row_first * kFlowSlots + ((flow_cnt(L_half, it) + 1) % kFlowSlots),
+                       2ull * (unsigned long long)(it + 1) + (acc_u ? 1ull : 0ull));
             const double r_u = __shfl(flow_r, 0);
             double nv = own_reg;
             if (acc_u) {
@@ -1264,7 +1235,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                 nv = lane < 6 ? t : nv;
             }
             if (L_half) own_half[1] = nv; else own_half[0] = nv;
-            if constexpr (XF) {
+            {
                 // the row as it is now into every rank's copy: lane pr stores to rank pr, an
                 // instruction per element instead of one per element and rank
                 const int m_new = flow_cnt(L_half, it) + 1;
@@ -1272,7 +1243,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
 #pragma unroll
                 for (int e = 0; e < 6; ++e) {
                     const double ve = __shfl(nv, e);
-                    if (lane < npeer) fl_st(dst + e, ve);
+                    if (lane < npeer) st_sys(dst + e, ve);
                 }
             }
             pend_row = row_first;
@@ -1288,7 +1259,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
 #undef PIN
 }
 
-// SMODE 5: slot 0 of the state from the sampler's rows (accept flags clear), all words zero.
+// SMODE 6: slot 0 of the state from the sampler's rows (accept flags clear), all words zero.
 static __global__ void k_flow_init(const double *pos6, double *spec, int nw)
 {
     const FlowView fv = flow_view(spec, nw);
@@ -1301,7 +1272,7 @@ static __global__ void k_flow_init(const double *pos6, double *spec, int nw)
     for (int k = i; k < nwords; k += gridDim.x * blockDim.x) fv.seq[k] = 0ull;
 }
 
-// SMODE 5, 6, when a launch of `nhalf` half-steps has ended: the sampler's rows from the slots
+// SMODE 6, when a launch of `nhalf` half-steps has ended: the sampler's rows from the slots
 // the last moves went to (every row is in this GPU's copy, whoever moved it).
 static __global__ void k_flow_finish(double *pos6, double *spec, int nw, int nhalf)
 {

@@ -33,13 +33,7 @@
 #pragma once
 #include "mbb_kernels.hip.h"
 
-constexpr unsigned long long kServeQuit = 0xffffull;           // the request's row count that means "leave"
-
-// dynamic LDS of a k_serve launch besides the staged passband tables (bytes)
-__host__ __device__ constexpr size_t serve_lds(size_t nb, size_t npart, bool cov_in_lds)
-{
-    return sizeof(WalkerK) + 8 * npart + 8 * nb + 16 + 16 * nb + (cov_in_lds ? 8 * nb * nb : 0) + 8 * (nb + 2) + 64;
-}
+// (kServeQuit and serve_lds, the LDS plan: mbb_lds_plans.hip.h)
 
 // Arguments (LikeArgs fields of variants that never meet share storage): pars = the parameter block, lnl = the pinned
 // result records [row]{lnl, status as a 64-bit integer}, pos6 = the doorbell (one 8-byte word: request number << 16 | rows), seed = the request the

@@ -1,5 +1,6 @@
 """A host-side model of the hand-over protocol of the one-launch look-ahead sampler run (k_lnlike
-SMODE 5), used by tests/test_host_cpu.py.  It restates WHO waits for WHAT and
+SMODE 6) with every record on one GPU -- the form it had as SMODE 5, its single-GPU
+twin until round 4 --, used by tests/test_host_cpu.py.  It restates WHO waits for WHAT and
 who reads and writes which slot -- with the kernel's own index arithmetic (mbb_flow_index.h, through
 the C hook) -- and runs the actors in random or adversarial order, every publication delayed at
 random.  Each slot remembers the number of the move whose data it holds; a read that finds another

@@ -1,5 +1,5 @@
 """A host-side model of the hand-over protocol of sampler form 7 (k_flowm, mbb_flowm.hip.h; DESIGN.md
-section 9, "Every stage ahead"), used by tests/test_host_cpu.py.  Like _flow_model.py for SMODE 5 it
+section 9, "Every stage ahead"), used by tests/test_host_cpu.py.  Like _flow_model.py for SMODE 6 it
 restates WHO waits for WHAT and who reads and writes which slot, with the kernel's own index arithmetic
 (mbb_flow_index.h through the C hooks), and runs the actors in random or adversarial order with every
 store to memory landing at a random later time.  Every slot remembers the move whose data it holds --

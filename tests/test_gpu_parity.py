@@ -1245,11 +1245,16 @@ def test_boundary_fast_path_equals_the_general_path(mbb, g_lnl):
     like._has_uplim[0] = False; like._dirty = True
     assert np.array_equal(like(allp[:125]), want[:125], equal_nan=True)
     # switched host-path options: still right, whichever way it goes
-    for opt, val in (("zero_copy", 0), ("zero_copy", 1), ("bar_params", 0), ("bar_params", 1), ("spin_wait", 0), ("spin_wait", 2),
-                     ("launch_api", 1), ("launch_api", 0)):
+    for opt, val in (("zero_copy", 0), ("zero_copy", 1), ("bar_params", 0), ("bar_params", 1), ("spin_wait", 0), ("spin_wait", 2)):
         ctx.set_option(opt, val)
         for _ in range(3):
             assert np.array_equal(like(allp[:125]), want[:125], equal_nan=True), (opt, val)
+    # the options of retired launch paths and sampler forms are gone: asked for, they are an error, and nothing changes
+    from mbb_emcee_amd._native import NativeError
+    for gone in ("launch_api", "resident_ahead", "lookahead_rows", "lookahead_waves"):
+        with pytest.raises(NativeError, match="unknown option"):
+            ctx.set_option(gone, 0)
+    assert np.array_equal(like(allp[:125]), want[:125], equal_nan=True)
     # a pickled copy builds its own context and buffers
     twin = pickle.loads(pickle.dumps(like))
     assert twin._fast is None and np.array_equal(twin(allp[:125]), want[:125], equal_nan=True)
@@ -1920,7 +1925,6 @@ def test_resident_sampler_form_for_large_ensembles_equals_the_launch_train(mbb, 
     state and the counts are bitwise the launch train's, whatever the number of walkers per workgroup (the
     host's choice, a forced one, a last workgroup that owns fewer; up to the eight of 4096 walkers: round 4's form 8,
     which took 3073-4096, is gone)."""
-    ahead = 1
     like = _cfg2_like(mbb, g_lnl)
     ctx = like.context
     p0 = np.array([12.0, 1.8, 600.0, 3.0, 40.0]) * (1.0 + 0.02 * np.random.RandomState(nw).normal(size=(nw, 5)))
@@ -1930,15 +1934,15 @@ def test_resident_sampler_form_for_large_ensembles_equals_the_launch_train(mbb, 
         s = mbb.DeviceEnsembleSampler(nw, 5, like, seed=nw + 1)
         a = s.run_mcmc(p0, 9)
         if resident:
-            assert ctx.info("last_kernel_form") == (9 if ahead else 8) and ctx.info("flow_fallbacks") == 0
+            assert ctx.info("last_kernel_form") == 9 and ctx.info("flow_fallbacks") == 0
             assert ctx.info("last_wpb") == (W or -(-(nw // 2) // ctx.info("cu_count")))
         b = s.run_mcmc(None, 6, storechain=False)
         s.advance_async(5); ctx.sync()
         c = s.run_mcmc(None, 4)
         out.append((a[0], a[1], b[0], b[1], c[0], c[1], s.chain.copy(), s.lnprobability.copy(), s.naccepted.copy()))
-        assert ctx.info("last_kernel_form") == ((9 if ahead else 8) if resident else 1)
+        assert ctx.info("last_kernel_form") == (9 if resident else 1)
     for x, y in zip(*out):
-        assert np.array_equal(x, y), (nw, W, ahead)
+        assert np.array_equal(x, y), (nw, W)
     assert out[0][6].shape == (nw, 13, 5) and 0.1 < out[0][8].mean() / 24 < 0.9
     lnl_close(out[1][5], like(out[1][4]))
 

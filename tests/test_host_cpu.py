@@ -823,7 +823,7 @@ def test_dustmass_identities():
 
 
 def test_flow_protocol_model():
-    """The hand-over protocol of the one-launch look-ahead sampler run (k_lnlike SMODE 5), restated
+    """The hand-over protocol of the one-launch look-ahead sampler run (k_lnlike SMODE 6, one GPU), restated
     on the host with the kernel's own index arithmetic (mbb_flow_index.h) and run in random and in
     adversarial order: with the lag guard no slot is ever reused under a reader and every run
     completes; a stalled worker stops what depends on it and nothing else goes wrong; without the

@@ -6,7 +6,7 @@ float64[n] out through likelihood.__call__, what an external sampler such as emc
 
 Layers, each timed over many calls (medians, us): likelihood.__call__ (Python: asarray, shape checks,
 _sync_device, raise_for_status) > Context.lnlike_batch (ctypes marshalling, numpy allocations) >
-mbb_lnlike_batch (C: parameter rows into device memory through the BAR + sentinels | hipLaunchKernel |
+mbb_lnlike_batch (C: parameter rows into device memory through the BAR + sentinels | hipModuleLaunchKernel |
 watching the result slots in pinned memory) > the kernel itself (HIP events around back-to-back launches on
 device-resident rows)."""
 import os, sys, time
@@ -31,10 +31,9 @@ def main():
         p = np.ascontiguousarray(walkers(1)[:n])
         row = p[0].copy()
         res = {}
-        # interleaved A/B of how the launch is handed to the runtime (option launch_api), three rounds each
+        # interleaved A/B of a launch per call (1) and the served boundary (2: no launch per call), three rounds each
         for rnd in range(3):
-            for api in (0, 1, 2):                     # 2: the served boundary (no launch per call)
-                ctx.set_option("launch_api", 1 if api == 2 else api)
+            for api in (1, 2):
                 ctx.set_option("serve", 1 if api == 2 else 0)
                 call, call90 = med_us((lambda: like(p)) if n > 1 else (lambda: like(row)), reps=1500)
                 ph = []
@@ -43,7 +42,7 @@ def main():
                     ph.append((ctx.info("last_prep_ns"), ctx.info("last_launch_ns"), ctx.info("last_wait_ns")))
                 prep, launch, wait = (np.median(np.array(ph), axis=0) / 1e3)
                 res.setdefault(api, []).append((call, call90, prep, launch, wait))
-        ctx.set_option("launch_api", 1); ctx.set_option("serve", 0)
+        ctx.set_option("serve", 0)
         old, _ = med_us(lambda: ctx.lnlike_batch(p))            # round 3's binding: two allocations, three addresses, memcpy in and out
         dp = ctx.alloc(p.nbytes); dp.upload(p)
         dl, ds = ctx.alloc(n * 8), ctx.alloc(n * 4)
@@ -52,11 +51,11 @@ def main():
         ctx.record(e0); ctx.lnlike_repeat_device(dp, n, dl, ds, 1000); ctx.record(e1); ctx.sync()
         kern = ctx.elapsed_ms(e0, e1)
         print("rows %d%s" % (n, "  (one row: what emcee calls per walker without vectorize)" if n == 1 else ""))
-        for api in (0, 1, 2):
+        for api in (1, 2):
             call, call90, prep, launch, wait = np.median(np.array(res[api]), axis=0)
             c_total = prep + launch + wait
-            print("  %s" % ("launch per call, hipLaunchKernel" if api == 0 else "launch per call, hipModuleLaunchKernel with a packed argument buffer"
-                            if api == 1 else "served: a kernel resident between the calls, rung through the BAR (the default in a loop of calls)"))
+            print("  %s" % ("launch per call, hipModuleLaunchKernel with a packed argument buffer" if api == 1
+                            else "served: a kernel resident between the calls, rung through the BAR (the default in a loop of calls)"))
             print("    likelihood.__call__            %6.2f us  (p90 %.2f)   rounds: %s" % (call, call90, " ".join("%.2f" % r[0] for r in res[api])))
             print("      Python + ctypes around the C call %5.2f us  (checks, rows written into the BAR block, the call, the copy out)" % (call - c_total))
             print("      inside mbb_lnlike_call       %6.2f us" % c_total)
@@ -65,7 +64,7 @@ def main():
             print("        %s %5.2f us   (the launched kernel alone: %.2f us, events, back to back)"
                   % ("launch latency + kernel + poll    " if api < 2 else "doorbell + evaluation + poll       ", wait, kern))
         print("  round 3's binding (Context.lnlike_batch: copies in and out, status array) %6.2f us" % old)
-        best = min(np.median(np.array(res[a]), axis=0)[0] for a in (0, 1, 2))
+        best = min(np.median(np.array(res[a]), axis=0)[0] for a in (1, 2))
         print("  => %.3g evals/s at the boundary" % (n / (best * 1e-6)), flush=True)
     ctx.set_option("serve", 1)
 

@@ -22,7 +22,7 @@ def make(opts):
 
 
 FORMS = {"plain": {"lookahead_sampler": 0, "flow_sampler": 0},
-         "form9": {"lookahead_sampler": 1, "flow_sampler": 1, "resident_sampler": 2, "resident_ahead": 1},
+         "form9": {"lookahead_sampler": 1, "flow_sampler": 1, "resident_sampler": 2},
          "form7": {"lookahead_sampler": 1, "flow_sampler": 1, "merged_flow_sampler": 1, "flow_spin_log2": SPIN}}
 res = {}
 for name, opts in FORMS.items():
