@@ -246,7 +246,7 @@ int mbb_event_destroy(mbb_ctx *ctx, void *ev);
  * "virtual_ranks", "debug", "roof_threads" / "roof_wgs_per_cu" (measurement only: the geometry of
  * mbb_roof_probe), "xchg_spin_max" (polls before a launch waiting for a peer
  * gives up); the forms of the single-GPU sampler, same chains bit for bit (which one a run takes by default, and
- * what each costs: sampler_enqueue in mbb_hip.hip, profiles/r04/walker_sweep.txt):
+ * what each costs: plan_sampler_run in mbb_hip.hip, profiles/r04/walker_sweep.txt):
  * "lookahead_sampler" (default 1; 0: the plain train of one launch per half-step),
  * "flow_sampler" (default 1: one launch per 4096 steps, every workgroup resident, rows handed over through check
  * words instead of a launch boundary; 0: the plain train as well),

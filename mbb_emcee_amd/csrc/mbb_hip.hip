@@ -253,7 +253,6 @@ struct mbb_ctx {
     double *call_in = nullptr;   // mbb_boundary_buffers: where the caller writes its rows (w_pars or h_pars)
     size_t call_cap = 0;         // ... and the capacity that answer was given for
     hipFunction_t mod_fn[kNumSlots] = {};   // the kernels' module handles, by slot (kernel_slot)
-    hipEvent_t *launch_ev = nullptr; // != nullptr: two events to record right before and right behind the next launch
     double *d_gather = nullptr, *h_gather = nullptr;   // sharded boundary: every rank's lnprob, device / pinned landing place
     size_t gather_cap = 0;
     int large_bar = -1;
@@ -265,7 +264,7 @@ struct mbb_ctx {
     WalkerK *d_sed_wk = nullptr;
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
-    long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_lnlike)
+    long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
     double *d_pre = nullptr;                   // ... its records
     size_t pre_cap = 0;                        // (doubles)
     long opt_zero_copy = 1;   // host path: kernel reads/writes pinned host memory (26 vs 34 us per call)
@@ -280,7 +279,6 @@ struct mbb_ctx {
                               // 2 watch the result slots in pinned memory (zero-copy batches <= 8192 rows)
     long last_stage = 0;
     long opt_lookahead = 1;   // single-GPU sampler runs prepare the next half-step's proposals ahead of the decisions they depend on
-    unsigned long long flow_serial = 0;   // one-launch sampler runs started on this context
     long opt_serve_overlap = 1;    // the served kernel starts a row's quadrature beside its constructor (0: one after the other)
     long opt_flow_spin_log2 = 0;   // one-launch run: log2 of the polls before a wait gives up (0: the kernel's 22)
     hipEvent_t ev_timed[2] = {nullptr, nullptr};   // mbb_sampler_advance_timed
@@ -780,55 +778,34 @@ static void pick_geometry(const mbb_ctx *c, int n, int &wpb, int &threads, bool 
     if (threads < 16 * wpb) threads = ((16 * wpb + 63) / 64) * 64;
 }
 
-// Look-ahead sampler runs: how the workgroups that work ahead are shaped.  One row of 16 lanes
-// per candidate proposal -- 4 per walker of a half: a row keeps to one half (SMODE 6) --
-// `rows` of them per wave, `aw` such waves per
-// workgroup.  A constructor is one dependent chain and a wave alone on its SIMD runs it fastest,
-// so the candidates are spread as thinly as the CUs the movers leave free allow.
-// Returns false when only the densest packing (64 candidates per workgroup) would fit: measured, the
-// one-launch run is then slower than the launch train (480 walkers: 17.7 against 15.8 us per step;
-// 450 walkers, 32 per workgroup: 15.0 against 15.8 -- profiles/r03/walker_sweep.txt), so the host takes
-// the train from there (ensembles above ~454 walkers on 256 CUs).
-static bool lookahead_plan(const mbb_ctx *c, int movers, int threads, int half, int &rows, int &aw, int &n_ahead)
+// Look-ahead sampler runs: how the workgroups that work ahead are shaped.  One row of 16 lanes per candidate proposal
+// -- 4 per walker of a half: a row keeps to one half (SMODE 6) -- `rows` of them per wave, `aw` such waves per workgroup.
+// A constructor is one dependent chain and a wave alone on its SIMD runs it fastest, so the candidates are spread as
+// thinly as the CUs the movers leave free allow.  Where even the densest packing (64 candidates per workgroup) leaves
+// them too few, the run takes the launch train (plan_sampler_run); measured, the one-launch run is slower than the train
+// there anyway (480 walkers: 17.7 against 15.8 us per step; 450 walkers, 32 per workgroup: 15.0 against 15.8 --
+// profiles/r03/walker_sweep.txt).
+static void lookahead_plan(const mbb_ctx *c, int movers, int threads, int half, int &rows, int &aw, int &n_ahead)
 {
     const int pairs = 4 * half, free_cus = c->cu_count - movers;
     static const int plan[5][2] = {{1, 4}, {2, 4}, {4, 4}, {4, 8}, {4, 16}};
     rows = 1; aw = 4;
-    int chosen = 4;
     for (int i = 0; i < 5; ++i) {
         rows = plan[i][0]; aw = std::min(plan[i][1], threads / 64);
-        if ((pairs + rows * aw - 1) / (rows * aw) <= free_cus) { chosen = i; break; }
+        if ((pairs + rows * aw - 1) / (rows * aw) <= free_cus) break;
     }
     n_ahead = (pairs + rows * aw - 1) / (rows * aw);
-    return chosen < 4;
 }
 
 constexpr long kFlowStrikes = 3, kFlowRest = 16;
 constexpr long kServeRest = 4096;            // boundary calls the served path rests for after three lost servers in a row
 static std::atomic<unsigned long long> g_flow_serial{0};   // one-launch sampler runs started in this process (their check words)
 
-struct SamplerLaunch {
-    double *pos6, *chain6;
-    unsigned int *nacc;
-    int *errflag;
-    int s_begin, c_begin, c_count, m_count, nw, step, half, nw_src;
-    double stretch_a;
-    unsigned long long seed;
-    // The sampler form, as last_kernel_form reports it: 1 the half-step (k_lnlike SMODE 1), 2 the half-step with the
-    // one-hop exchange (SMODE 2), 6 the one-launch run of a sharded ensemble (SMODE 6), 7 k_flowm, 9 k_flowa.
-    int form = 1;
-    int persist;                  // forms 6, 7, 9: this many half-steps in one launch
-    double *spec;                 // forms 6, 7, 9: the one-launch run's device state (form 6: the FlowX)
-    int res_w = 1;                // form 9: walkers per workgroup and half
-    unsigned long long serial = 0;   // forms 7, 9: the number of its launch (in its check words and decision words)
-    int parity = 0;               // ... which of the two sets of completion counters it uses
-};
-
 // One launch of the kernel in `slot` (kernel_slot): the module-launch entry with the argument block handed over as ONE
 // packed buffer -- no per-argument marshalling in the runtime, 0.2 us per call less than hipLaunchKernel (A/B:
-// tools/probe_boundary_breakdown.py, profiles/r04/boundary_breakdown.txt); with c->launch_ev set, the launch that carries
-// the two events itself.
-static int launch_packed(mbb_ctx *c, int slot, int grid, int threads, size_t smem, LikeArgs &a)
+// tools/probe_boundary_breakdown.py, profiles/r04/boundary_breakdown.txt).  ev: null, or two events to record right
+// before and right behind the launch.
+static int launch_packed(mbb_ctx *c, int slot, int grid, int threads, size_t smem, LikeArgs &a, hipEvent_t *ev)
 {
     void (*const kern)(const LikeArgs) = g_kernel[slot];
     if (static_lds(c) + smem > 60 * 1024) {
@@ -845,7 +822,6 @@ static int launch_packed(mbb_ctx *c, int slot, int grid, int threads, size_t sme
     }
     hipFunction_t &f = c->mod_fn[slot];
     if (!f) HIPCHK(hipGetFuncBySymbol(&f, (const void *)kern));
-    hipEvent_t *ev = c->launch_ev;
     size_t sz = sizeof(a);
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
     // (hipExtModuleLaunchKernel would take the two events with the launch -- the dispatch's own timestamps, no marker
@@ -876,48 +852,57 @@ static void fill_model_args(const mbb_ctx *c, LikeArgs &a)
 #endif
 }
 
-// ... and what every sampler form reads of its launch
-static void fill_sampler_args(const SamplerLaunch &sl, LikeArgs &a)
+// What a k_lnlike launch of n walkers -- of given rows (launch_rows) or of a sampler form (launch_sampler) -- is shaped
+// by: walkers per workgroup and workgroup size (pick_geometry), grid, dynamic LDS with the inverse covariance in it when
+// that fits beside everything else, and the passband tables staged there too or not.  Fills the argument block but for
+// what the kind of launch adds, and the launch's mbb_get_info "last_*" values.
+struct LnlikeShape { int wpb, threads, grid; bool stage; size_t smem; };
+static int lnlike_shape(mbb_ctx *c, int n, LnlikeShape &g, LikeArgs &a)
 {
-    a.pos6 = sl.pos6; a.chain6 = sl.chain6; a.nacc = sl.nacc; a.errflag = sl.errflag;
-    a.s_begin = sl.s_begin; a.c_begin = sl.c_begin; a.c_count = sl.c_count; a.nw = sl.nw;
-    a.m_count = sl.m_count;
-    a.step = sl.step; a.half = sl.half; a.stretch_a = sl.stretch_a; a.seed = sl.seed;
-    a.nw_src = sl.nw_src;
-    a.persist = sl.persist;
+    bool mid_staged = false;
+    pick_geometry(c, n, g.wpb, g.threads, &mid_staged);
+    g.grid = (n + g.wpb - 1) / g.wpb;
+    const size_t cov_bytes = c->has_cov ? 8 * (size_t)c->nb * c->nb : 0;
+    const size_t smem_base = lnlike_lds_base(c, g.wpb);
+    const size_t dyn_limit = dynamic_lds_limit(c);
+    const bool cov_in_lds = c->has_cov && smem_base + cov_bytes <= std::min<size_t>(64 * 1024, dyn_limit);
+    const size_t smem = smem_base + (cov_in_lds ? cov_bytes : 0);
+    if (smem > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
+    // LDS staging of the passband tables.  Measured (profiles/r01/ab_stage.txt, interleaved A/B): in the latency regime
+    // (one walker per workgroup, the copy hides under the prologue) it is 1.5 % faster; with many walkers per workgroup it
+    // is 4-5 % slower than reading the tables through L2, because 60 KB of LDS per workgroup caps residency at two per CU.
+    const size_t table_bytes = (size_t)c->nchunk * 64 * 3 * sizeof(double);
+    g.stage = ((g.wpb == 1 && n <= c->cu_count) || mid_staged) && smem + table_bytes + 16 <= dyn_limit;
+    if (c->opt_stage == 0) g.stage = false;
+    if (c->opt_stage == 1) g.stage = smem + table_bytes + 16 <= dyn_limit;
+    g.smem = smem + (g.stage ? table_bytes + 16 : 0);
+    if (c->nsrc > 1 && n % c->nsrc != 0) return fail(MBB_ERR_ARG, "row count must be a multiple of the number of sources");
+    memset(&a, 0, sizeof a);
+    fill_model_args(c, a);
+    a.n = n; a.wpb = g.wpb; a.cov_in_lds = cov_in_lds ? 1 : 0; a.nsrc = c->nsrc;
+    a.rows_per_src = c->nsrc > 1 ? n / c->nsrc : 0;
+    a.stretch_a = 2.0;
+    c->last_wpb = g.wpb; c->last_threads = g.threads; c->last_grid = g.grid; c->last_smem = (long)g.smem;
+    c->last_stage = g.stage ? 1 : 0; c->last_prepass = 0;
+    return MBB_OK;
 }
 
-static int launch_lnlike(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
-                         int32_t *d_status, double *d_mflux, const SamplerLaunch *sl = nullptr)
+// The likelihood of n given rows: k_lnlike SMODE 0, after k_walker_pre for big batches
+static int launch_rows(mbb_ctx *c, const double *d_pars, int n, double *d_lnl, int32_t *d_status, double *d_mflux)
 {
     if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
     if (c->data_nb != c->nb) return fail(MBB_ERR_STATE, "data not set or band count mismatch");
     if (n <= 0) return MBB_OK;
+    LnlikeShape g;
     LikeArgs a;
-    fill_model_args(c, a);
-    a.xargs = nullptr;
-    a.persist = 0; a.spec = nullptr;
-    a.pars = d_pars; a.n = n; a.lnl = d_lnl; a.status = d_status; a.model_flux = d_mflux;
-    int wpb, threads;
-    bool mid_staged = false;
-    pick_geometry(c, n, wpb, threads, &mid_staged);
-    a.wpb = wpb;
-    int grid = (n + wpb - 1) / wpb;
-    const size_t cov_bytes = c->has_cov ? 8 * (size_t)c->nb * c->nb : 0;
-    const size_t smem_base = lnlike_lds_base(c, wpb);
-    // the inverse covariance goes to LDS when it fits beside everything else
-    const size_t dyn_limit = dynamic_lds_limit(c);
-    a.cov_in_lds = (c->has_cov && smem_base + cov_bytes <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
-    const size_t smem = smem_base + (a.cov_in_lds ? cov_bytes : 0);
-    if (smem > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
-    c->last_wpb = wpb; c->last_threads = threads; c->last_grid = grid;
-    a.nsrc = c->nsrc;
+    int rc = lnlike_shape(c, n, g, a);
+    if (rc) return rc;
+    a.pars = d_pars; a.lnl = d_lnl; a.status = d_status; a.model_flux = d_mflux;
     // Big batches of given rows: gate, constructor and penalties by a pass of their own with a LANE per walker (k_walker_pre)
     // -- where a launch is bound by the number of instructions it issues, a row of 16 lanes per walker spends a quarter of
     // them on the constructors (cfg5's 250 000 rows: 1.31 -> 1.0x ms).  Option "prepass": -1 auto (from 64 walkers per CU),
     // 0 never, 1 always.
-    c->last_prepass = 0;
-    if (!sl && (c->opt_prepass > 0 || (c->opt_prepass < 0 && (long)n >= 64L * c->cu_count))) {
+    if (c->opt_prepass > 0 || (c->opt_prepass < 0 && (long)n >= 64L * c->cu_count)) {
         const size_t need = (size_t)n * kPreWords;
         if (need > c->pre_cap) {
             size_t cap = c->pre_cap ? c->pre_cap : 16384 * (size_t)kPreWords;
@@ -928,89 +913,14 @@ static int launch_lnlike(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
             c->pre_cap = cap;
         }
         a.spec = c->d_pre;
-        a.xargs = nullptr;
         static void (*const ptable[4])(const LikeArgs) = {k_walker_pre<false, false>, k_walker_pre<false, true>,
                                                           k_walker_pre<true, false>, k_walker_pre<true, true>};
         hipLaunchKernelGGL(ptable[model_of(c)], dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
         HIPCHK(hipGetLastError());
         c->last_prepass = 1;
     }
-    a.rows_per_src = 0;
-    a.nw_src = 0;
-    if (c->nsrc > 1) {
-        if (n % c->nsrc != 0)
-            return fail(MBB_ERR_ARG, "row count must be a multiple of the number of sources");
-        a.rows_per_src = n / c->nsrc;
-    }
-    // LDS staging of the passband tables.  Measured (profiles/r01/ab_stage.txt,
-    // interleaved A/B): in the latency regime (one walker per workgroup, the copy
-    // hides under the prologue) it is 1.5 % faster; with many walkers per
-    // workgroup it is 4-5 % slower than reading the tables through L2, because
-    // 60 KB of LDS per workgroup caps residency at two workgroups per CU.
-    const size_t table_bytes = (size_t)c->nchunk * 64 * 3 * sizeof(double);
-    bool stage = ((wpb == 1 && n <= c->cu_count) || mid_staged) && smem + table_bytes + 16 <= dyn_limit;
-    if (c->opt_stage == 0) stage = false;
-    if (c->opt_stage == 1) stage = smem + table_bytes + 16 <= dyn_limit;
-    const size_t smem_total = smem + (stage ? table_bytes + 16 : 0);
-    c->last_smem = (long)smem_total;
-    c->last_stage = stage ? 1 : 0;
-    const int form = sl ? sl->form : 0;
-    if (sl) {
-        fill_sampler_args(*sl, a);
-    } else {
-        a.pos6 = nullptr; a.chain6 = nullptr; a.nacc = nullptr; a.errflag = nullptr;
-        a.s_begin = a.c_begin = a.c_count = a.m_count = a.nw = a.step = a.half = 0;
-        a.stretch_a = 2.0; a.seed = 0;
-    }
-    if (form == 7 || form == 9) {
-        // the resident sampler forms, every workgroup resident, each with its own LDS plan:
-        //   form 7 (k_flowm): 2 n workgroups of (quadrature waves + 5), one per (walker, candidate)
-        //   form 9 (k_flowa): ceil(n / W) workgroups of 16 waves, W walkers of each half apiece
-        a.flow_serial = c->flow_serial = sl->serial;
-        a.spec = sl->spec;
-        a.spec_cfg = (int)((c->opt_flow_spin_log2 & 0x3f) << 24) | (sl->parity & 1);
-        a.n_ahead = 0;
-        const bool fa = form == 9;
-        const int W = fa ? sl->res_w : 1;   // (round 3 also had two pairs of walkers per k_flowm workgroup: superseded by form 9)
-        const int wgs = fa ? (n + W - 1) / W : 2 * n;
-        const int thr = fa ? 1024 : (std::min(threads / 64, 11) + 5) * 64;
-        auto lds_of = [&](bool cov) { return fa ? flowa_lds(c->nb, c->npart, cov, W) : flowm_lds(c->nb, c->npart, cov); };
-        a.wpb = W;
-        a.cov_in_lds = (c->has_cov && lds_of(true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
-        const size_t sm = lds_of(a.cov_in_lds != 0);
-        const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
-        const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
-        if (sm_total > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
-        if (wgs > c->cu_count || W > kFaMaxW)
-            return fail(MBB_ERR_ARG, "the one-launch sampler run needs every workgroup resident: too many for this GPU");
-        c->last_wpb = W; c->last_threads = thr; c->last_grid = wgs; c->last_smem = (long)sm_total;
-        c->last_stage = stg ? 1 : 0; c->last_smode = form; c->last_ahead = 0;
-        return launch_packed(c, kernel_slot(fa ? kFlowa : kFlowm, model_of(c), stg ? 1 : 0), wgs, thr, sm_total, a);
-    }
-    // k_lnlike, SMODE = form: 0 the likelihood of given rows, 1 the half-step, 2 the half-step with the one-hop exchange,
-    // 6 the one-launch look-ahead run across the ranks of a sharded ensemble (slot 3; its single-GPU twin went in round 4:
-    // forms 7 and 9 are faster at every ensemble size)
-    if (form == 2) a.xargs = c->x.d_args;
-    if (form == 6) {
-        a.flow_serial = c->flow_serial = ++g_flow_serial;
-        // first the workgroups that prepare the next half-step -- one row of 16 lanes per
-        // (walker, candidate), `rows` of them per wave, `aw` such waves per workgroup -- then
-        // the movers.  A constructor is one dependent chain: a wave alone on its SIMD runs it
-        // fastest, so the candidates are spread as thinly as the CUs the movers leave free allow.
-        int rows, aw, n_ahead;
-        lookahead_plan(c, grid, threads, sl->m_count, rows, aw, n_ahead);
-        a.spec = sl->spec;
-        a.spec_cfg = (rows << 8) | (aw << 16) | (int)((c->opt_flow_spin_log2 & 0x3f) << 24);
-        a.n_ahead = n_ahead;
-        if (a.n_ahead + grid > c->cu_count)
-            return fail(MBB_ERR_ARG, "the one-launch sampler run needs every workgroup resident: too many for this GPU");
-        grid = a.n_ahead + grid;
-        c->last_grid = grid;
-    }
-    c->last_smode = form;
-    c->last_ahead = form == 6 ? a.n_ahead : 0;
-    return launch_packed(c, kernel_slot(kLnlike, model_of(c), (form == 6 ? 3 : form) * 2 + (stage ? 1 : 0)), grid, threads,
-                         smem_total, a);
+    c->last_smode = 0; c->last_ahead = 0;
+    return launch_packed(c, kernel_slot(kLnlike, model_of(c), g.stage ? 1 : 0), g.grid, g.threads, g.smem, a, nullptr);
 }
 
 extern "C" int mbb_lnlike_batch_device(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
@@ -1019,7 +929,7 @@ extern "C" int mbb_lnlike_batch_device(mbb_ctx *c, const double *d_pars, int n, 
     int rc = use(c);
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!d_pars || !d_lnl))) return fail(MBB_ERR_ARG, "bad batch buffers");
-    return launch_lnlike(c, d_pars, n, d_lnl, d_status, d_mflux);
+    return launch_rows(c, d_pars, n, d_lnl, d_status, d_mflux);
 }
 
 extern "C" int mbb_lnlike_repeat_device(mbb_ctx *c, const double *d_pars, int n, double *d_lnl,
@@ -1029,7 +939,7 @@ extern "C" int mbb_lnlike_repeat_device(mbb_ctx *c, const double *d_pars, int n,
     if (rc) return rc;
     if (n <= 0 || reps <= 0 || !d_pars || !d_lnl) return fail(MBB_ERR_ARG, "bad batch buffers");
     for (int r = 0; r < reps; ++r)
-        if ((rc = launch_lnlike(c, d_pars, n, d_lnl, d_status, nullptr))) return rc;
+        if ((rc = launch_rows(c, d_pars, n, d_lnl, d_status, nullptr))) return rc;
     return MBB_OK;
 }
 
@@ -1056,7 +966,7 @@ static int lnlike_zero_copy(mbb_ctx *c, int n, bool push, bool model_flux, long 
         for (int i = 0; i < n; ++i) { hl[i] = kLnlSentinel; c->h_status[i] = kStatusSentinel; }
     }
     const long t_b = now_ns();
-    if ((rc = launch_lnlike(c, dp, n, dl, ds, df))) return rc;
+    if ((rc = launch_rows(c, dp, n, dl, ds, df))) return rc;
     const long t_c = now_ns();
     bool seen = false;
     if (watch) {
@@ -1101,7 +1011,7 @@ extern "C" int mbb_lnlike_batch(mbb_ctx *c, const double *pars, int n, double *l
         if ((rc = lnlike_zero_copy(c, n, push, model_flux != nullptr, t_a))) return rc;
     } else {
         HIPCHK(hipMemcpyAsync(c->d_pars, c->h_pars, nbytes, hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_lnlike(c, c->d_pars, n, c->d_lnl, c->d_status,
+        if ((rc = launch_rows(c, c->d_pars, n, c->d_lnl, c->d_status,
                                 model_flux ? c->d_mflux : nullptr))) return rc;
         HIPCHK(hipMemcpyAsync(c->h_lnl, c->d_lnl, (size_t)n * sizeof(double),
                               hipMemcpyDeviceToHost, c->stream));
@@ -1162,7 +1072,7 @@ static int serve_stop(mbb_ctx *c)
     return MBB_OK;
 }
 
-// Start a server with the request in the launch itself.  The argument block is launch_lnlike's, filled in here for
+// Start a server with the request in the launch itself.  The argument block is launch_rows', filled in here for
 // the fields k_serve reads.
 // How many workgroups a server of this context is started with: a row each for the widest call so far, in eights -- not
 // one per CU: what it does not hold is there for the launches and the servers of other processes (two pool workers of 125
@@ -1217,7 +1127,8 @@ static int serve_launch(mbb_ctx *c, int n, unsigned long long word, int grid)
     __atomic_store_n(c->w_door, word, __ATOMIC_RELAXED);
     __builtin_ia32_sfence();
     {
-        int rc = launch_packed(c, kernel_slot(kServe, model_of(c), (ovl ? 2 : 0) + (stg ? 1 : 0)), grid, threads, sm_total, a);
+        int rc = launch_packed(c, kernel_slot(kServe, model_of(c), (ovl ? 2 : 0) + (stg ? 1 : 0)), grid, threads, sm_total, a,
+                               nullptr);
         if (rc) return rc;
     }
     c->srv_grid = grid;
@@ -1422,7 +1333,7 @@ struct mbb_sampler_state {
     unsigned int *d_nacc = nullptr;      // [shards][2][nsrc*per], launch-local order
     int *d_err = nullptr;
     double *d_bak = nullptr;             // one-launch run: the rows and counts it started from (R x 6 doubles, R counts)
-    bool flow_used = false;              // the last enqueue took the one-launch form
+    bool backup_kept = false;            // the last run kept d_bak, a copy of what it started from to redo it from
     bool unchecked = false;              // an asynchronous advance was enqueued and its error flag not looked at yet
     bool lost = false;                   // such an advance gave up: the rows are no state of the chain until set again
     double *d_spec = nullptr;            // one-launch run: its device state (FlowView or FlowMView, spec_words(rows))
@@ -1591,158 +1502,185 @@ static int allgather_bytes(mbb_ctx *c, void *base, size_t bytes_per_rank)
     return MBB_OK;
 }
 
-// (tev: two events for mbb_sampler_advance_timed, recorded on the stream right before the run's first launch and right
-// behind its last)
-static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stretch_a, bool store, bool backup = true,
-                           hipEvent_t *tev = nullptr)
-{
-    s->flow_used = false;
+// How a sampler run goes, decided here alone and once per run: its shards, the walkers of a launch and the form -- the
+// first of these whose conditions hold ("Which form a run takes", has what each costs):
+//   6  a sharded ensemble with the one-hop exchange, ONE launch per 4096 steps on every rank (k_lnlike SMODE 6): options
+//      "lookahead_sampler", "flow_sampler" and "sharded_flow_sampler" on, one source, a step at least, one walker per
+//      workgroup, the movers and the workgroups that work ahead of them all resident, the rows in the exchange buffer;
+//   7  k_flowm, ONE launch per 4096 steps, every workgroup resident (as form 9; both need "lookahead_sampler" and
+//      "flow_sampler" on, one shard, no collective, one source, "flow_min_steps" steps): "merged_flow_sampler" on,
+//      "resident_sampler" not 2, up to two walkers per CU, one walker per workgroup;
+//   9  k_flowa: "resident_sampler" not 0, and res_w walkers of each half per workgroup fit;
+//   2, 1  the launch train, one k_lnlike launch per half-step and shard, with and without the exchange.
+// Forms 7 and 9 rest for kFlowRest runs after kFlowStrikes give-ups in a row: such a run takes the train (`resting`,
+// counted down by sampler_enqueue).  one_launch_ok false rules out 6, 7 and 9 as option "flow_sampler" 0 does: the redo
+// of a run that gave up (sampler_run).
+struct RunPlan {
     ShardPlan p;
-    int rc = shard_plan(c, s, p);
+    int nl = 0;                          // walkers per launch
+    int form = 1;                        // 1, 2, 6, 7 or 9, as last_kernel_form reports it
+    bool resting = false;                // form 7 or 9 held back by give-ups in a row: one of the runs flow_rest counts
+    int res_w = 1;                       // form 9: walkers per workgroup and half
+    int rows = 0, aw = 0, n_ahead = 0;   // form 6: the workgroups that work ahead (lookahead_plan)
+};
+
+static int plan_sampler_run(const mbb_ctx *c, const mbb_sampler_state *s, int nsteps, bool one_launch_ok, RunPlan &rp)
+{
+    int rc = shard_plan(c, s, rp.p);
     if (rc) return rc;
-    const int nw = s->nw, half = nw / 2;
-    const size_t nl = (size_t)s->nsrc * p.per;              // walkers per launch
-    if (p.xchg && tev) HIPCHK(hipEventRecord(tev[0], c->stream));
-    if (p.xchg) {
-        // the kernel's view of the exchange for this run, in stream order before its launches
-        // (pageable source: staged by the runtime before the call returns)
-        XchgArgs xa;
-        memset(&xa, 0, sizeof xa);
-        for (int r = 0; r < c->x.n; ++r) { xa.xpos[r] = c->x.pos6(r); xa.xflag[r] = c->x.flags(r); }
-        xa.xcount = c->x.count(); xa.xn = c->x.n; xa.xrank = c->x.rank;
-        xa.xseq0 = c->x.seq; xa.xspin_max = c->x.spin_max;
-        HIPCHK(hipMemcpyAsync(c->x.d_args, &xa, sizeof xa, hipMemcpyHostToDevice, c->stream));
-    }
-    SamplerLaunch sl;
-    sl.pos6 = s->d_pos6; sl.errflag = s->d_err; sl.nw = s->rows(); sl.nw_src = nw;
-    sl.stretch_a = stretch_a; sl.c_count = half; sl.m_count = p.per;
-    sl.persist = 0;
-    sl.spec = nullptr;
-    // A sharded ensemble with the one-hop exchange, one launch per run (k_lnlike SMODE 6): every rank
-    // moves its share of each half and prepares their proposals ahead, decisions / rows / words go
-    // into every rank's copy of the run's state (behind the rows in the exchange buffer) at system
-    // scope, and a row's half-step starts when the rows it depends on are done, on whatever GPU.
-    // Around the launch: set up this rank's copy, tell the peers (a mover's first store into a
-    // peer's copy waits for that peer's word), launch, tell the peers the launch has ended, wait
-    // for theirs (no store of theirs is in flight any more), bring the rows up to date.
-    {
-        int wpb_x = 0, thr_x = 0, la_rows, la_aw, la_ahead;
-        pick_geometry(c, (int)nl, wpb_x, thr_x);
-        lookahead_plan(c, (int)nl, thr_x, p.per, la_rows, la_aw, la_ahead);
-        if (p.xchg && c->opt_lookahead && c->opt_flow && c->opt_xflow && s->nsrc == 1 && nsteps > 0 && wpb_x == 1 &&
-            la_ahead + (int)nl <= c->cu_count && (size_t)s->rows() <= c->x.cap_rows) {
-            const size_t R = (size_t)s->rows();
-            double *mine = c->x.flow(c->x.rank);
-            const FlowView fvl = flow_view(mine, (int)R);
-            sl.spec = reinterpret_cast<double *>(c->x.d_flowx);
-            sl.form = 6;
-            for (int t0 = 0; t0 < nsteps; t0 += 4096) {
-                const int nt = std::min(4096, nsteps - t0);
-                FlowX fxh;
-                memset(&fxh, 0, sizeof fxh);
-                for (int r = 0; r < c->x.n; ++r) fxh.base[r] = c->x.flow(r);
-                fxh.n = c->x.n; fxh.rank = c->x.rank; fxh.run = ++c->x.flow_run;
-                HIPCHK(hipMemcpyAsync(c->x.d_flowx, &fxh, sizeof fxh, hipMemcpyHostToDevice, c->stream));
-                hipLaunchKernelGGL(k_flow_init, dim3((unsigned)((R * 8 + 255) / 256)), dim3(256), 0, c->stream,
-                                   s->d_pos6, mine, (int)R);
-                hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx, (int)R, 0, fxh.run,
-                                   (const int *)nullptr);
-                HIPCHK(hipGetLastError());
-                sl.s_begin = c->x.rank * p.per; sl.c_begin = half; sl.step = t0; sl.half = 0;
-                sl.persist = 2 * nt;
-                sl.chain6 = store ? s->d_chain6 + ((((size_t)c->x.rank * nsteps + t0) * 2) * nl) * 6 : nullptr;
-                sl.nacc = s->d_nacc + (size_t)c->x.rank * 2 * nl;
-                sl.seed = s->seed + 0x9E3779B97F4A7C15ull * (s->steps_done + (unsigned long long)t0 + 1ull);
-                if ((rc = launch_lnlike(c, nullptr, (int)nl, nullptr, nullptr, nullptr, &sl))) return rc;
-                hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx, (int)R, 1, fxh.run,
-                                   (const int *)s->d_err);
-                hipLaunchKernelGGL(k_flow_wait_end, dim3(1), dim3(64), 0, c->stream, fvl.endf, c->x.n, c->x.rank, fxh.run,
-                                   c->x.spin_max, s->d_err);
-                hipLaunchKernelGGL(k_flow_finish, dim3((unsigned)((R * 6 + 255) / 256)), dim3(256), 0, c->stream,
-                                   s->d_pos6, mine, (int)R, 2 * nt);
-                HIPCHK(hipGetLastError());
-            }
-            s->steps_done += (unsigned long long)nsteps;
-            if (tev) HIPCHK(hipEventRecord(tev[1], c->stream));
-            return MBB_OK;
-        }
-    }
-    int wpb_1 = 0, thr_1 = 0;
-    pick_geometry(c, (int)nl, wpb_1, thr_1);
-    // Options "lookahead_sampler" / "flow_sampler" (default 1) -- one GPU, one ensemble, every workgroup resident: the run
-    // is ONE launch per 4096 steps, rows handed over through check words instead of a launch boundary; chains are bitwise
-    // those of the plain launch train, which is what several sources, very short runs and ensembles beyond 8 walkers per CU
-    // and half take.  Which form (profiles/r04/walker_sweep.txt, us per MCMC step, cfg2 bands):
-    //   form 7 (k_flowm): a workgroup per (pair of walkers, candidate), quadrature and constructor ahead of the decisions
-    //           they depend on -- while each has a CU of its own: 6.0-6.3 up to 256 walkers;
-    //   form 9 (k_flowa): a workgroup owns W = ceil(half / CUs) walkers of each half, the constructor a half-step ahead
-    //           for both outcomes of the partner's pending move, a walker's quadrature starting when ITS partner has decided
-    //           -- 8.4-8.9 from 258 to 512 walkers (round 3's forms there, removed this round: form 5 9.6-10.2 up to 340,
-    //           form 7 with two pairs per workgroup 11.5 up to 512), 10.7-11.3 up to 1000, 15.6 at 1500, 18.6 at 2000
-    //           (train: 18.9 / 19.1 / 22.4 / 26.0);
-    //           (round 4's form 8, k_flowr -- the same ownership, nothing ahead -- existed for 3073-4096 walkers only and was
-    //           6 % ahead there, 35.5 against 37.6 us per step at 4096: removed in round 5, form 9 takes those too).
-    const bool one_launch = c->opt_lookahead && c->opt_flow && p.shards == 1 && !p.collective && s->nsrc == 1 &&
-                            nsteps >= (int)std::max<long>(1, c->opt_flow_min_steps);
-    const int res_w = c->opt_flowr_walkers > 0 ? (int)std::min<long>(c->opt_flowr_walkers, kFaMaxW)
-                                               : ((int)nl + c->cu_count - 1) / c->cu_count;
-    const bool res_fits = res_w >= 1 && res_w <= kFaMaxW && ((int)nl + res_w - 1) / res_w <= c->cu_count;
-    int form = 0;                                  // 7 or 9: the run as one launch per 4096 steps
-    if (one_launch && c->opt_flowm && c->opt_flowr != 2 && 2 * (int)nl <= c->cu_count && wpb_1 == 1) form = 7;
-    else if (one_launch && c->opt_flowr != 0 && res_fits) form = 9;
-    if (form && c->flow_rest > 0) { --c->flow_rest; form = 0; }   // resting after give-ups in a row
-    if (form) {
-        const size_t R = (size_t)s->rows();
-        if (!s->d_spec) {
-            // zeroed: the records of a one-launch run are taken by their check words, and freshly
-            // allocated memory may hold those of another sampler's run
-            HIPCHK(hipMalloc((void **)&s->d_spec, spec_words(R) * sizeof(double)));
-            HIPCHK(hipMemsetAsync(s->d_spec, 0, spec_words(R) * sizeof(double), c->stream));
-        }
-        sl.spec = s->d_spec;
-        sl.form = form;
-        sl.res_w = res_w;
-        // what the run starts from, kept so that a run that times out (a workgroup that is not
-        // resident: another process on the GPU) can be redone as a launch train (mbb_sampler_run)
-        // (mbb_sampler_advance_async does not redo anything: no copy there)
-        if (backup) {
-            if (!s->d_bak) HIPCHK(hipMalloc((void **)&s->d_bak, R * 6 * sizeof(double) + R * sizeof(unsigned int)));
-            HIPCHK(hipMemcpyAsync(s->d_bak, s->d_pos6, R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(s->d_bak + R * 6, s->d_nacc, R * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
-        }
-        s->flow_used = backup;
-        if (s->spec_form != 7 && s->spec_form != 9) {
-            // forms 7 and 9 find their completion counters cleared by the launch before it (either's); after
-            // another form (or a run that gave up) has used the memory, once from here
-            const FlowMView fvh = flowm_view(s->d_spec, (int)R);
-            HIPCHK(hipMemsetAsync(fvh.done, 0, 2 * kFmRing * 16 * sizeof(unsigned long long), c->stream));
-            s->flowm_parity = 0;
-        }
-        s->spec_form = form;
-        const bool carried = tev && nsteps <= 4096;
-        if (tev && !carried) HIPCHK(hipEventRecord(tev[0], c->stream));
-        for (int t0 = 0; t0 < nsteps; t0 += 4096) {
-            const int nt = std::min(4096, nsteps - t0);
-            // one launch, nothing before or after it: it files the rows it finds and stores the last ones back
-            sl.serial = ++g_flow_serial;
-            sl.parity = s->flowm_parity;
-            s->flowm_parity ^= 1;
-            sl.s_begin = 0; sl.c_begin = half; sl.step = t0; sl.half = 0;
-            sl.persist = 2 * nt;
-            sl.chain6 = store ? s->d_chain6 + ((size_t)t0 * 2 * nl) * 6 : nullptr;
-            sl.nacc = s->d_nacc;
-            sl.seed = s->seed + 0x9E3779B97F4A7C15ull * (s->steps_done + (unsigned long long)t0 + 1ull);
-            c->launch_ev = carried ? tev : nullptr;
-            rc = launch_lnlike(c, nullptr, (int)nl, nullptr, nullptr, nullptr, &sl);
-            c->launch_ev = nullptr;
-            if (rc) return rc;
-        }
-        if (tev && !carried) HIPCHK(hipEventRecord(tev[1], c->stream));
-        s->steps_done += (unsigned long long)nsteps;
+    const ShardPlan &p = rp.p;
+    const int nl = rp.nl = s->nsrc * p.per;
+    int wpb, threads;
+    pick_geometry(c, nl, wpb, threads);
+    lookahead_plan(c, nl, threads, p.per, rp.rows, rp.aw, rp.n_ahead);
+    const bool flow = one_launch_ok && c->opt_lookahead && c->opt_flow && s->nsrc == 1;
+    if (flow && p.xchg && c->opt_xflow && nsteps > 0 && wpb == 1 && rp.n_ahead + nl <= c->cu_count &&
+        (size_t)s->rows() <= c->x.cap_rows) {
+        rp.form = 6;
         return MBB_OK;
     }
-    sl.spec = nullptr; sl.form = p.xchg ? 2 : 1; sl.persist = 0;
-    if (tev && !p.xchg) HIPCHK(hipEventRecord(tev[0], c->stream));
+    const bool resident = flow && p.shards == 1 && !p.collective && nsteps >= (int)std::max<long>(1, c->opt_flow_min_steps);
+    rp.res_w = c->opt_flowr_walkers > 0 ? (int)std::min<long>(c->opt_flowr_walkers, kFaMaxW) : (nl + c->cu_count - 1) / c->cu_count;
+    const bool res_fits = rp.res_w >= 1 && rp.res_w <= kFaMaxW && (nl + rp.res_w - 1) / rp.res_w <= c->cu_count;
+    if (resident && c->opt_flowm && c->opt_flowr != 2 && 2 * nl <= c->cu_count && wpb == 1) rp.form = 7;
+    else if (resident && c->opt_flowr != 0 && res_fits) rp.form = 9;
+    else rp.form = p.xchg ? 2 : 1;
+    rp.resting = rp.form >= 7 && c->flow_rest > 0;
+    if (rp.resting) rp.form = 1;           // (forms 7 and 9 have no exchange)
+    return MBB_OK;
+}
+
+// What changes from one launch of a sampler run to the next (the form and its shape: RunPlan)
+struct SamplerLaunch {
+    double *pos6, *chain6;
+    unsigned int *nacc;
+    int *errflag;
+    int s_begin, c_begin, c_count, m_count, nw, step, half, nw_src;
+    double stretch_a;
+    unsigned long long seed;
+    int persist = 0, parity = 0;         // forms 6, 7, 9: half-steps in this launch; 7, 9: its set of completion counters
+    double *spec = nullptr;              // forms 6, 7, 9: the run's device state (form 6: the FlowX)
+    unsigned long long serial = 0;       // ... the number of the launch (in its check words and decision words)
+};
+
+// The RNG key of step t of a run: it advances over the whole life of the sampler, the chain index restarts
+static unsigned long long step_key(const mbb_sampler_state *s, int t)
+{
+    return s->seed + 0x9E3779B97F4A7C15ull * (s->steps_done + (unsigned long long)t + 1ull);
+}
+
+// One launch of sampler form rp.form.  ev: null, or two events to record right before and right behind it.
+static int launch_sampler(mbb_ctx *c, const RunPlan &rp, const SamplerLaunch &sl, hipEvent_t *ev)
+{
+    if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
+    if (c->data_nb != c->nb) return fail(MBB_ERR_STATE, "data not set or band count mismatch");
+    const int n = rp.nl, form = rp.form;
+    LnlikeShape g;
+    LikeArgs a;
+    int rc = lnlike_shape(c, n, g, a);
+    if (rc) return rc;
+    a.pos6 = sl.pos6; a.chain6 = sl.chain6; a.nacc = sl.nacc; a.errflag = sl.errflag;
+    a.s_begin = sl.s_begin; a.c_begin = sl.c_begin; a.c_count = sl.c_count; a.m_count = sl.m_count; a.nw = sl.nw;
+    a.step = sl.step; a.half = sl.half; a.stretch_a = sl.stretch_a; a.seed = sl.seed; a.nw_src = sl.nw_src;
+    a.persist = sl.persist; a.spec = sl.spec; a.flow_serial = sl.serial;   // (forms 1, 2: serial 0, the null `pars`)
+    const int spin = (int)((c->opt_flow_spin_log2 & 0x3f) << 24);
+    if (form == 7 || form == 9) {
+        // the resident sampler forms, every workgroup resident (plan_sampler_run), each with its own LDS plan:
+        //   form 7 (k_flowm): 2 n workgroups of (quadrature waves + 5), one per (walker, candidate)
+        //   form 9 (k_flowa): ceil(n / W) workgroups of 16 waves, W walkers of each half apiece
+        a.spec_cfg = spin | (sl.parity & 1);
+        const bool fa = form == 9;
+        const int W = fa ? rp.res_w : 1;   // (round 3 also had two pairs of walkers per k_flowm workgroup: superseded by form 9)
+        const int wgs = fa ? (n + W - 1) / W : 2 * n;
+        const int thr = fa ? 1024 : (std::min(g.threads / 64, 11) + 5) * 64;
+        const size_t dyn_limit = dynamic_lds_limit(c), table_bytes = (size_t)c->nchunk * 64 * 3 * sizeof(double);
+        auto lds_of = [&](bool cov) { return fa ? flowa_lds(c->nb, c->npart, cov, W) : flowm_lds(c->nb, c->npart, cov); };
+        a.wpb = W;
+        a.cov_in_lds = (c->has_cov && lds_of(true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
+        const size_t sm = lds_of(a.cov_in_lds != 0);
+        const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
+        const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
+        if (sm_total > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
+        c->last_wpb = W; c->last_threads = thr; c->last_grid = wgs; c->last_smem = (long)sm_total;
+        c->last_stage = stg ? 1 : 0; c->last_smode = form; c->last_ahead = 0;
+        return launch_packed(c, kernel_slot(fa ? kFlowa : kFlowm, model_of(c), stg ? 1 : 0), wgs, thr, sm_total, a, ev);
+    }
+    // k_lnlike, SMODE = form: 1 the half-step, 2 the half-step with the one-hop exchange, 6 the one-launch look-ahead run
+    // across the ranks of a sharded ensemble (slot 3; its single-GPU twin went in round 4: forms 7 and 9 are faster at every
+    // ensemble size).  Form 6 dispatches first the n_ahead workgroups that prepare the next half-step -- one row of 16 lanes
+    // per (walker, candidate), `rows` of them per wave, `aw` such waves per workgroup (lookahead_plan) -- then the movers.
+    int grid = g.grid;
+    if (form == 2) a.xargs = c->x.d_args;
+    if (form == 6) {
+        a.spec_cfg = (rp.rows << 8) | (rp.aw << 16) | spin;
+        a.n_ahead = rp.n_ahead;
+        c->last_grid = grid += rp.n_ahead;
+    }
+    c->last_smode = form; c->last_ahead = form == 6 ? rp.n_ahead : 0;
+    return launch_packed(c, kernel_slot(kLnlike, model_of(c), (form == 6 ? 3 : form) * 2 + (g.stage ? 1 : 0)), grid, g.threads,
+                         g.smem, a, ev);
+}
+
+// Forms 6, 7 and 9: one launch per 4096 steps.
+// Form 6, a sharded ensemble with the one-hop exchange: every rank moves its share of each half and prepares their
+// proposals ahead, decisions / rows / words go into every rank's copy of the run's state (behind the rows in the exchange
+// buffer) at system scope, and a row's half-step starts when the rows it depends on are done, on whatever GPU.  Around
+// each launch: set up this rank's copy, tell the peers (a mover's first store into a peer's copy waits for that peer's
+// word), launch, tell the peers the launch has ended, wait for theirs (no store of theirs is in flight any more), bring
+// the rows up to date.  Forms 7 and 9: the launch alone -- it files the rows it finds and stores the last ones back.
+static int run_one_launch(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, SamplerLaunch &sl, int nsteps, bool store,
+                          hipEvent_t *ev)
+{
+    const size_t R = (size_t)s->rows(), nl = (size_t)rp.nl;
+    const bool sharded = rp.form == 6;
+    const int rank = sharded ? c->x.rank : 0;
+    double *const mine = sharded ? c->x.flow(rank) : nullptr;   // form 6: this rank's copy of the run's state
+    sl.spec = sharded ? reinterpret_cast<double *>(c->x.d_flowx) : s->d_spec;
+    for (int t0 = 0; t0 < nsteps; t0 += 4096) {
+        const int nt = std::min(4096, nsteps - t0);
+        FlowX fxh;
+        if (sharded) {
+            memset(&fxh, 0, sizeof fxh);
+            for (int r = 0; r < c->x.n; ++r) fxh.base[r] = c->x.flow(r);
+            fxh.n = c->x.n; fxh.rank = rank; fxh.run = ++c->x.flow_run;
+            HIPCHK(hipMemcpyAsync(c->x.d_flowx, &fxh, sizeof fxh, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_flow_init, dim3((unsigned)((R * 8 + 255) / 256)), dim3(256), 0, c->stream,
+                               s->d_pos6, mine, (int)R);
+            hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx, (int)R, 0, fxh.run,
+                               (const int *)nullptr);
+            HIPCHK(hipGetLastError());
+        } else {
+            sl.parity = s->flowm_parity;
+            s->flowm_parity ^= 1;
+        }
+        sl.serial = ++g_flow_serial;
+        sl.s_begin = rank * rp.p.per; sl.c_begin = s->nw / 2; sl.step = t0; sl.half = 0;
+        sl.persist = 2 * nt;
+        sl.chain6 = store ? s->d_chain6 + (((size_t)rank * nsteps + t0) * 2 * nl) * 6 : nullptr;
+        sl.nacc = s->d_nacc + (size_t)rank * 2 * nl;
+        sl.seed = step_key(s, t0);
+        int rc = launch_sampler(c, rp, sl, ev);
+        if (rc) return rc;
+        if (sharded) {
+            hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx, (int)R, 1, fxh.run,
+                               (const int *)s->d_err);
+            hipLaunchKernelGGL(k_flow_wait_end, dim3(1), dim3(64), 0, c->stream, flow_view(mine, (int)R).endf, c->x.n, rank,
+                               fxh.run, c->x.spin_max, s->d_err);
+            hipLaunchKernelGGL(k_flow_finish, dim3((unsigned)((R * 6 + 255) / 256)), dim3(256), 0, c->stream,
+                               s->d_pos6, mine, (int)R, 2 * nt);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return MBB_OK;
+}
+
+// Forms 1 and 2: the launch train, one launch per half-step and shard
+static int run_train(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, SamplerLaunch &sl, int nsteps, bool store)
+{
+    const ShardPlan &p = rp.p;
+    const size_t nl = (size_t)rp.nl;
+    const int half = s->nw / 2;
+    int rc;
     for (int t = 0; t < nsteps; ++t)
         for (int h = 0; h < 2; ++h) {
             const int hb = h ? half : 0;
@@ -1751,16 +1689,14 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double 
                 sl.step = t; sl.half = h;
                 sl.chain6 = store ? s->d_chain6 + ((((size_t)r * nsteps + t) * 2 + h) * nl) * 6 : nullptr;
                 sl.nacc = s->d_nacc + ((size_t)r * 2 + h) * nl;
-                // the RNG key advances over the whole life of the sampler, the chain index restarts
-                sl.seed = s->seed + 0x9E3779B97F4A7C15ull * (s->steps_done + (unsigned long long)t + 1ull);
+                sl.seed = step_key(s, t);
                 if (p.xchg) ++c->x.seq;
-                if ((rc = launch_lnlike(c, nullptr, (int)nl, nullptr, nullptr, nullptr, &sl))) return rc;
+                if ((rc = launch_sampler(c, rp, sl, nullptr))) return rc;
             }
             if (p.collective && !p.xchg &&
                 (rc = allgather_bytes(c, s->d_pos6 + (size_t)hb * 6, (size_t)p.per * 6 * sizeof(double))))
                 return rc;
         }
-    s->steps_done += (unsigned long long)nsteps;
     if (p.xchg) {
         // the stream is done only when every peer's last launch has landed here too; chain
         // and acceptance counts stay per rank (the caller gathers them if it wants them)
@@ -1772,28 +1708,74 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double 
         if (store && (rc = allgather_bytes(c, s->d_chain6, (size_t)nsteps * 2 * nl * 6 * sizeof(double)))) return rc;
         if ((rc = allgather_bytes(c, s->d_nacc, 2 * nl * sizeof(unsigned int)))) return rc;
     }
-    if (tev) HIPCHK(hipEventRecord(tev[1], c->stream));
     return MBB_OK;
 }
 
-// Advance nsteps stretch-move steps entirely on the device: 2 nsteps dependent
-// launches on the context's stream, no host round trip in between.
-// chain [nsrc*nw][nsteps][5] and lnprob [nsrc*nw][nsteps] (emcee's layout per
-// source, results.py:154-155) may be NULL; pos_out [nsrc*nw*5], lnprob_out,
-// naccepted [nsrc*nw] (running totals).
-extern "C" int mbb_sampler_run(mbb_ctx *c, void *sp, int nsteps, double stretch_a, double *chain,
-                               double *lnprob, double *pos_out, double *lnprob_out,
-                               double *naccepted)
+// Put the run rp plans on the stream.  backup: forms 7 and 9 keep what the run starts from, so that a run that times out
+// (a workgroup that is not resident: another process on the GPU) can be redone as a launch train (sampler_run).  tev: two
+// events for mbb_sampler_advance_timed, recorded right before the run's first stream work and right behind its last --
+// by the launch itself when the run is one launch of form 7 or 9.
+static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, int nsteps, double stretch_a, bool store,
+                           bool backup, hipEvent_t *tev)
 {
-    int rc = use(c);
+    s->backup_kept = false;
+    if (rp.resting) --c->flow_rest;
+    if (rp.form >= 7) {
+        const size_t R = (size_t)s->rows();
+        if (!s->d_spec) {
+            // zeroed: the records of a one-launch run are taken by their check words, and freshly
+            // allocated memory may hold those of another sampler's run
+            HIPCHK(hipMalloc((void **)&s->d_spec, spec_words(R) * sizeof(double)));
+            HIPCHK(hipMemsetAsync(s->d_spec, 0, spec_words(R) * sizeof(double), c->stream));
+        }
+        if (backup) {
+            if (!s->d_bak) HIPCHK(hipMalloc((void **)&s->d_bak, R * 6 * sizeof(double) + R * sizeof(unsigned int)));
+            HIPCHK(hipMemcpyAsync(s->d_bak, s->d_pos6, R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(s->d_bak + R * 6, s->d_nacc, R * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+        }
+        s->backup_kept = backup;
+        if (s->spec_form != 7 && s->spec_form != 9) {
+            // forms 7 and 9 find their completion counters cleared by the launch before it (either's); after
+            // another form (or a run that gave up) has used the memory, once from here
+            const FlowMView fvh = flowm_view(s->d_spec, (int)R);
+            HIPCHK(hipMemsetAsync(fvh.done, 0, 2 * kFmRing * 16 * sizeof(unsigned long long), c->stream));
+            s->flowm_parity = 0;
+        }
+        s->spec_form = rp.form;
+    }
+    const bool carried = tev && rp.form >= 7 && nsteps <= 4096;
+    if (tev && !carried) HIPCHK(hipEventRecord(tev[0], c->stream));
+    if (rp.p.xchg) {
+        // the kernel's view of the exchange for this run, in stream order before its launches
+        // (pageable source: staged by the runtime before the call returns)
+        XchgArgs xa;
+        memset(&xa, 0, sizeof xa);
+        for (int r = 0; r < c->x.n; ++r) { xa.xpos[r] = c->x.pos6(r); xa.xflag[r] = c->x.flags(r); }
+        xa.xcount = c->x.count(); xa.xn = c->x.n; xa.xrank = c->x.rank;
+        xa.xseq0 = c->x.seq; xa.xspin_max = c->x.spin_max;
+        HIPCHK(hipMemcpyAsync(c->x.d_args, &xa, sizeof xa, hipMemcpyHostToDevice, c->stream));
+    }
+    SamplerLaunch sl;
+    sl.pos6 = s->d_pos6; sl.errflag = s->d_err; sl.nw = s->rows(); sl.nw_src = s->nw;
+    sl.stretch_a = stretch_a; sl.c_count = s->nw / 2; sl.m_count = rp.p.per;
+    const int rc = rp.form >= 6 ? run_one_launch(c, s, rp, sl, nsteps, store, carried ? tev : nullptr)
+                                : run_train(c, s, rp, sl, nsteps, store);
     if (rc) return rc;
-    mbb_sampler_state *s = (mbb_sampler_state *)sp;
-    if (!s || nsteps < 0 || !(stretch_a > 1.0)) return fail(MBB_ERR_ARG, "bad sampler arguments");
-    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
-    ShardPlan p;
-    if ((rc = shard_plan(c, s, p))) return rc;
+    if (tev && !carried) HIPCHK(hipEventRecord(tev[1], c->stream));
+    s->steps_done += (unsigned long long)nsteps;
+    return MBB_OK;
+}
+
+// mbb_sampler_run once its arguments are checked (one_launch_ok: plan_sampler_run)
+static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stretch_a, double *chain, double *lnprob,
+                       double *pos_out, double *lnprob_out, double *naccepted, bool one_launch_ok)
+{
+    RunPlan rp;
+    int rc = plan_sampler_run(c, s, nsteps, one_launch_ok, rp);
+    if (rc) return rc;
+    const ShardPlan &p = rp.p;
     const int R = s->rows(), nw = s->nw, half = nw / 2;
-    const size_t nl = (size_t)s->nsrc * p.per;
+    const size_t nl = (size_t)rp.nl;
     const bool store = (chain || lnprob) && nsteps > 0;
     if ((rc = sampler_check_pending(c, s))) return rc;
     if (store && (size_t)nsteps * R * 6 > s->chain_cap) {
@@ -1813,7 +1795,7 @@ extern "C" int mbb_sampler_run(mbb_ctx *c, void *sp, int nsteps, double stretch_
         }
         s->chain_cap = (size_t)nsteps * R * 6;
     }
-    if ((rc = sampler_enqueue(c, s, nsteps, stretch_a, store))) return rc;
+    if ((rc = sampler_enqueue(c, s, rp, nsteps, stretch_a, store, true, nullptr))) return rc;
     std::vector<double> rows((size_t)R * 6);
     std::vector<unsigned int> nacc(R);
     int err = 0;
@@ -1850,7 +1832,7 @@ extern "C" int mbb_sampler_run(mbb_ctx *c, void *sp, int nsteps, double stretch_
     if (err) {
         HIPCHK(hipMemset(s->d_err, 0, sizeof(int)));
         if (err == 8) return fail(MBB_ERR_RCCL, "the exchange timed out: a peer did not post its launch");
-        if (err == 9 && s->flow_used && s->d_bak) {
+        if (err == 9 && s->backup_kept) {
             // The one-launch run gave up waiting (not every workgroup was resident): back to the state it
             // started from and the same steps as a train of launches -- the same chain.  The next run takes
             // the one-launch form again; kFlowStrikes give-ups in a row rest it for kFlowRest runs.
@@ -1861,11 +1843,7 @@ extern "C" int mbb_sampler_run(mbb_ctx *c, void *sp, int nsteps, double stretch_
             s->spec_form = 0;
             ++c->flow_fallbacks;
             if (++c->flow_strikes >= kFlowStrikes) { c->flow_strikes = 0; c->flow_rest = kFlowRest; }
-            const long keep = c->opt_flow;
-            c->opt_flow = 0;                                   // (this redo only)
-            rc = mbb_sampler_run(c, sp, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted);
-            c->opt_flow = keep;
-            return rc;
+            return sampler_run(c, s, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted, false);
         }
         if (err == 9) {
             // (a sharded run: nothing was kept to redo it from)
@@ -1878,7 +1856,7 @@ extern "C" int mbb_sampler_run(mbb_ctx *c, void *sp, int nsteps, double stretch_
                 std::to_string(err) + ")";
         return MBB_ERR_ARG;
     }
-    if (s->flow_used) c->flow_strikes = 0;                  // a one-launch run that went through
+    if (s->backup_kept) c->flow_strikes = 0;                // a one-launch run that went through
     if (direct && via_pinned) {
         const size_t cells = (size_t)R * nsteps;
         if (chain) memcpy(chain, s->h_chain, cells * 5 * sizeof(double));
@@ -1906,6 +1884,23 @@ extern "C" int mbb_sampler_run(mbb_ctx *c, void *sp, int nsteps, double stretch_
     return MBB_OK;
 }
 
+// Advance nsteps stretch-move steps entirely on the device: 2 nsteps dependent
+// launches on the context's stream, no host round trip in between.
+// chain [nsrc*nw][nsteps][5] and lnprob [nsrc*nw][nsteps] (emcee's layout per
+// source, results.py:154-155) may be NULL; pos_out [nsrc*nw*5], lnprob_out,
+// naccepted [nsrc*nw] (running totals).
+extern "C" int mbb_sampler_run(mbb_ctx *c, void *sp, int nsteps, double stretch_a, double *chain,
+                               double *lnprob, double *pos_out, double *lnprob_out,
+                               double *naccepted)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    mbb_sampler_state *s = (mbb_sampler_state *)sp;
+    if (!s || nsteps < 0 || !(stretch_a > 1.0)) return fail(MBB_ERR_ARG, "bad sampler arguments");
+    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
+    return sampler_run(c, s, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted, true);
+}
+
 // Measurement helper: enqueue nsteps steps without storing a chain and without
 // synchronising (HIP events around the call time the dependent launch train).
 extern "C" int mbb_sampler_advance_async(mbb_ctx *c, void *sp, int nsteps, double stretch_a)
@@ -1916,7 +1911,9 @@ extern "C" int mbb_sampler_advance_async(mbb_ctx *c, void *sp, int nsteps, doubl
     if (!s || nsteps < 0) return fail(MBB_ERR_ARG, "bad sampler arguments");
     if (s->lost) return sampler_check_pending(c, s);
     s->unchecked = true;
-    return sampler_enqueue(c, s, nsteps, stretch_a, false, false);
+    RunPlan rp;
+    if ((rc = plan_sampler_run(c, s, nsteps, true, rp))) return rc;
+    return sampler_enqueue(c, s, rp, nsteps, stretch_a, false, false, nullptr);
 }
 
 // Measurement helper: the same enqueue between the host clock and two events, in one call -- the harness
@@ -1936,7 +1933,9 @@ extern "C" int mbb_sampler_advance_timed(mbb_ctx *c, void *sp, int nsteps, doubl
         HIPCHK(hipEventCreate(&c->ev_timed[1]));
     }
     const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = sampler_enqueue(c, s, nsteps, stretch_a, false, false, c->ev_timed))) return rc;
+    RunPlan rp;
+    if ((rc = plan_sampler_run(c, s, nsteps, true, rp))) return rc;
+    if ((rc = sampler_enqueue(c, s, rp, nsteps, stretch_a, false, false, c->ev_timed))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     const auto t1 = std::chrono::steady_clock::now();
     *wall_s = std::chrono::duration<double>(t1 - t0).count();
@@ -2455,7 +2454,7 @@ extern "C" int mbb_lnlike_allgather_device(mbb_ctx *c, const double *d_pars, int
     int rc = use(c);
     if (rc) return rc;
     if (n <= 0 || !d_pars || !d_lnl || !d_all) return fail(MBB_ERR_ARG, "bad batch buffers");
-    if ((rc = launch_lnlike(c, d_pars, n, d_lnl, d_status, nullptr))) return rc;
+    if ((rc = launch_rows(c, d_pars, n, d_lnl, d_status, nullptr))) return rc;
     return mbb_allgather_f64(c, d_lnl, d_all, n);
 }
 
@@ -2504,7 +2503,7 @@ extern "C" int mbb_lnlike_allgather(mbb_ctx *c, const double *pars, int n, doubl
     if (c->opt_zero_copy) HIPCHK(hipHostGetDevicePointer((void **)&ds, c->h_status, 0));
     else ds = c->d_status;
     double *mine = c->d_gather + (size_t)rank * n;
-    if ((rc = launch_lnlike(c, dp, n, mine, ds, nullptr))) return rc;
+    if ((rc = launch_rows(c, dp, n, mine, ds, nullptr))) return rc;
     if ((rc = mbb_allgather_f64(c, mine, c->d_gather, n))) return rc;
     HIPCHK(hipMemcpyAsync(c->h_gather, c->d_gather, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (!c->opt_zero_copy)

@@ -3,7 +3,7 @@
 
     python tools/sweep_walkers.py [sizes ...]
 
-For every ensemble size: the form the host chooses (mbb_hip.hip, sampler_enqueue), and -- where they are
+For every ensemble size: the form the host chooses (mbb_hip.hip, plan_sampler_run), and -- where they are
 eligible -- each of the forms (7, 9, the launch train) forced through the options: us per MCMC step by HIP events on the stream,
 evals/s = walkers / that.  The cut-overs between the forms (form 7 up to 2 walkers per CU, form 9 up to eight
 walkers per CU and half, the launch train beyond) are then read off the curve.
