@@ -163,6 +163,65 @@ int mbb_sampler_advance_async(mbb_ctx *ctx, void *sampler, int nsteps, double st
 int mbb_sampler_advance_timed(mbb_ctx *ctx, void *sampler, int nsteps, double stretch_a, double *wall_s,
                               float *stream_ms);
 
+/* ---- posterior summaries of a chain, computed where the chain is ---------- */
+/* Replaces: what mbb_results makes of a chain (results.py): _parcen_internal (:314-369: mean and
+ * numpy.percentile of the flattened chain, optionally clipped to [lowlim, uplim]) behind par_cen, peaklambda_cen,
+ * lir_cen and dustmass_cen (:397-431, :507-532, :600-625, :699-724); par_lowlim / par_uplim (:433-493); the best
+ * fit of process_fit (:160-165: lnprobability.argmax(), ties to the smallest flat index); compute_peaklambda,
+ * compute_lir and compute_dustmass (:570-581, :627-674, :746-801) for the derived columns.
+ * Columns ("slots") of a summary: 0-4 the parameters, 5 peak wavelength [um], 6 L_IR [1e12 L_sun], 7 dust mass
+ * [1e8 M_sun].  A column's samples are steps burn, burn + thin, ... of every walker.  Percentiles are numpy's
+ * (method "linear") of EXACT order statistics; all sums are fixed-order trees, so a chain gives the same bits
+ * every time.  Covariance (numpy.cov of the five parameters, ddof 1) and best fit are over the same window,
+ * unclipped. */
+#define MBB_SUMMARY_COLS 8
+#define MBB_SUMMARY_MAX_PCT 8
+enum mbb_summary_derived { MBB_SUM_PEAK = 1, MBB_SUM_LIR = 2, MBB_SUM_DUSTMASS = 4 };
+/* status of a column: bits */
+enum mbb_summary_status {
+    MBB_SUM_EMPTY = 1,        /* no sample survives the clipping: n_used 0, mean and percentiles NaN          */
+    MBB_SUM_HAS_NAN = 2,      /* the column holds a NaN: mean and percentiles NaN, as numpy's                 */
+    MBB_SUM_ABSENT = 4,       /* a derived column that was not asked for                                      */
+    MBB_SUM_ROW_SHIFT = 8     /* bit 8 + s: a sample's SED kernel row had mbb_row_status s (derived columns)  */
+};
+typedef struct mbb_summary_spec {
+    int32_t npct;                          /* percentiles asked for, 1..MBB_SUMMARY_MAX_PCT                   */
+    int32_t burn, thin;                    /* window: steps burn <= t < nsteps, every thin-th                 */
+    int32_t derived;                       /* mbb_summary_derived bits                                        */
+    int32_t peak_model;                    /* 0: the fit's own model; 1: optically thick with alpha, which is
+                                              what compute_peaklambda evaluates whatever the fit (:574-581)   */
+    int32_t has_lo[MBB_SUMMARY_COLS], has_hi[MBB_SUMMARY_COLS];   /* clip a column: keep lo <= x <= hi       */
+    double pct[MBB_SUMMARY_MAX_PCT];       /* numpy's q in [0, 100]                                           */
+    double lo[MBB_SUMMARY_COLS], hi[MBB_SUMMARY_COLS];
+    double redshift, lumdist_mpc;          /* for L_IR and dust mass                                          */
+    double kappa, kappa_wave;              /* dust mass (results.py:746: 2.64 m^2/kg at 125 um)               */
+    double lir_wavemin, lir_wavemax;       /* rest-frame range of L_IR in um (results.py:627: 8, 1000)       */
+} mbb_summary_spec;
+/* Where a summary goes; every pointer is the caller's, host memory, required. */
+typedef struct mbb_summary_out {
+    int64_t *n_used;                       /* [nsrc][8]                                                       */
+    double *mean, *min, *max;              /* [nsrc][8]                                                       */
+    double *pct;                           /* [nsrc][8][npct]                                                 */
+    int32_t *status;                       /* [nsrc][8] mbb_summary_status bits                               */
+    double *cov;                           /* [nsrc][5][5]                                                    */
+    double *best;                          /* [nsrc][6]: the best sample's parameters and lnprob, bit for bit */
+    int32_t *best_index;                   /* [nsrc][2]: its walker and step                                  */
+} mbb_summary_out;
+/* A host chain in emcee's layout, chain [nsrc][nw][nsteps][5] and lnprob [nsrc][nw][nsteps]: upload, summarise on
+ * the device, download the summary.  The model flags of the context (mbb_set_model) are the derived columns'. */
+int mbb_chain_summary(mbb_ctx *ctx, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                      const mbb_summary_spec *spec, const mbb_summary_out *out);
+/* mbb_sampler_run that keeps the chain on the device, summarises it there and copies back the summary and the
+ * final ensemble: same run plan, same forms, same redo of a one-launch run that gave up as mbb_sampler_run, so
+ * the chain summarised is bit for bit the one mbb_sampler_run returns.  chain / lnprob may be NULL (then no chain
+ * crosses the bus) or given to get the chain as well.  nsteps == 0 runs nothing and summarises again, with
+ * another spec, the chain the last call with nsteps > 0 left on the device (MBB_ERR_STATE when there is none).
+ * A sharded run (a communicator or the one-hop exchange with more than one rank) is refused with
+ * MBB_ERR_STATE: a rank holds only its own walkers' chain. */
+int mbb_sampler_run_summary(mbb_ctx *ctx, void *sampler, int nsteps, double stretch_a,
+                            const mbb_summary_spec *spec, const mbb_summary_out *out, double *chain,
+                            double *lnprob, double *pos_out, double *lnprob_out, double *naccepted);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

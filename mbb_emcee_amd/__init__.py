@@ -12,7 +12,8 @@ from .likelihood import likelihood
 from .ensemble import EnsembleSampler
 from .device_sampler import DeviceEnsembleSampler
 from .mbb_fit import mbb_fitter
+from .results import chain_summary, ChainSummary
 
 __version__ = "0.1.0"
 __all__ = ["response", "response_set", "modified_blackbody", "alpha_merge_eqn", "isiterable", "likelihood",
-           "EnsembleSampler", "DeviceEnsembleSampler", "mbb_fitter"]
+           "EnsembleSampler", "DeviceEnsembleSampler", "mbb_fitter", "chain_summary", "ChainSummary"]

@@ -18,6 +18,29 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _vp = C.c_void_p
 
+SUMMARY_COLS, SUMMARY_MAX_PCT = 8, 8
+SUM_PEAK, SUM_LIR, SUM_DUSTMASS = 1, 2, 4
+SUM_EMPTY, SUM_HAS_NAN, SUM_ABSENT, SUM_ROW_SHIFT = 1, 2, 4, 8
+
+
+class SummarySpec(C.Structure):
+    """mbb_summary_spec (include/mbb_hip.h)"""
+    _fields_ = [("npct", C.c_int32), ("burn", C.c_int32), ("thin", C.c_int32), ("derived", C.c_int32),
+                ("peak_model", C.c_int32),
+                ("has_lo", C.c_int32 * SUMMARY_COLS), ("has_hi", C.c_int32 * SUMMARY_COLS),
+                ("pct", C.c_double * SUMMARY_MAX_PCT),
+                ("lo", C.c_double * SUMMARY_COLS), ("hi", C.c_double * SUMMARY_COLS),
+                ("redshift", C.c_double), ("lumdist_mpc", C.c_double),
+                ("kappa", C.c_double), ("kappa_wave", C.c_double),
+                ("lir_wavemin", C.c_double), ("lir_wavemax", C.c_double)]
+
+
+class SummaryOut(C.Structure):
+    """mbb_summary_out (include/mbb_hip.h)"""
+    _fields_ = [("n_used", C.POINTER(C.c_int64)), ("mean", _dp), ("min", _dp), ("max", _dp), ("pct", _dp),
+                ("status", _ip), ("cov", _dp), ("best", _dp), ("best_index", _ip)]
+
+
 # name -> (restype, argtypes); mirrors include/mbb_hip.h one to one
 SIGNATURES = {
     "mbb_last_error": (C.c_char_p, []),
@@ -42,6 +65,10 @@ SIGNATURES = {
     "mbb_sampler_reset": (C.c_int, [_vp, _vp]),
     "mbb_sampler_set_state": (C.c_int, [_vp, _vp, _dp, _dp]),
     "mbb_sampler_run": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]),
+    "mbb_chain_summary": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(SummarySpec),
+                                    C.POINTER(SummaryOut)]),
+    "mbb_sampler_run_summary": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(SummarySpec),
+                                          C.POINTER(SummaryOut), _dp, _dp, _dp, _dp, _dp]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_advance_timed": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "mbb_sed_prologue_batch": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_double,

@@ -29,6 +29,7 @@
 #include "../../include/mbb_hip.h"
 #include "mbb_device.hip.h"
 #include "mbb_kernels.hip.h"
+#include "mbb_summary.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
 #define MBB_FLOW_EXT(OT, NA)                                                    \
@@ -262,6 +263,12 @@ struct mbb_ctx {
     double *d_sed_pars = nullptr, *d_sed_out = nullptr;
     int32_t *d_sed_status = nullptr;
     WalkerK *d_sed_wk = nullptr;
+    // work buffers of the chain summary (summary_run): grown as needed, kept for the next call
+    struct SumWork {
+        void *part = nullptr, *state = nullptr, *hist = nullptr, *covpart = nullptr, *colstatus = nullptr,
+             *outbuf = nullptr, *der = nullptr;
+        size_t c_part = 0, c_state = 0, c_hist = 0, c_covpart = 0, c_colstatus = 0, c_outbuf = 0, c_der = 0;
+    } sum;
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -507,6 +514,8 @@ extern "C" void mbb_ctx_destroy(mbb_ctx *c)
     free_dev(c->d_pre);
     free_dev(c->d_sed_pars); free_dev(c->d_sed_out); free_dev(c->d_sed_status);
     free_dev(c->d_sed_wk);
+    free_dev(c->sum.part); free_dev(c->sum.state); free_dev(c->sum.hist); free_dev(c->sum.covpart);
+    free_dev(c->sum.colstatus); free_dev(c->sum.outbuf); free_dev(c->sum.der);
     for (int i = 0; i < 2; ++i)
         if (c->ev_timed[i]) (void)hipEventDestroy(c->ev_timed[i]);
     if (c->stream) {
@@ -1344,6 +1353,8 @@ struct mbb_sampler_state {
     double *h_chain = nullptr;           // ... and its pinned landing place on the host (a D2H into the caller's pageable,
                                          // often untouched, arrays ran at ~1 GB/s: 18.8 us per step for 2000 stored steps)
     size_t chain_cap = 0;
+    bool h_chain_tried = false;          // the landing buffer was asked for since d_chain_out was last made
+    int resident_nsteps = 0;             // steps of the chain d_chain_out holds in the caller's layout (0: none)
     unsigned long long seed = 0, steps_done = 0;
     int rows() const { return nw * nsrc; }
 };
@@ -1767,8 +1778,14 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, 
 }
 
 // mbb_sampler_run once its arguments are checked (one_launch_ok: plan_sampler_run)
+static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
+                       const mbb_summary_spec *sp, const mbb_summary_out *o);
+
+// (sspec / sout: mbb_sampler_run_summary -- the chain is kept and re-ordered on the device whether or not the caller
+// wants it on the host, and summarised there once the run is known to have gone through)
 static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stretch_a, double *chain, double *lnprob,
-                       double *pos_out, double *lnprob_out, double *naccepted, bool one_launch_ok)
+                       double *pos_out, double *lnprob_out, double *naccepted, bool one_launch_ok,
+                       const mbb_summary_spec *sspec = nullptr, const mbb_summary_out *sout = nullptr)
 {
     RunPlan rp;
     int rc = plan_sampler_run(c, s, nsteps, one_launch_ok, rp);
@@ -1776,8 +1793,10 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
     const ShardPlan &p = rp.p;
     const int R = s->rows(), nw = s->nw, half = nw / 2;
     const size_t nl = (size_t)rp.nl;
-    const bool store = (chain || lnprob) && nsteps > 0;
+    const bool to_host = (chain || lnprob) && nsteps > 0;
+    const bool store = (to_host || sspec) && nsteps > 0;
     if ((rc = sampler_check_pending(c, s))) return rc;
+    if (store) s->resident_nsteps = 0;
     if (store && (size_t)nsteps * R * 6 > s->chain_cap) {
         HIPCHK(hipStreamSynchronize(c->stream));
         free_dev(s->d_chain6); s->d_chain6 = nullptr; s->chain_cap = 0;
@@ -1788,12 +1807,16 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
         // (a landing buffer the host refuses to pin -- a limit on locked memory -- is done without: the chain
         // then goes straight into the caller's arrays, slower for big chains, never wrong)
         // (only chains big enough to go through it get one: pinning costs a few hundred microseconds)
-        if ((size_t)nsteps * R * 6 * sizeof(double) > kChainDirectBytes &&
-            hipHostMalloc((void **)&s->h_chain, (size_t)nsteps * R * 6 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        s->chain_cap = (size_t)nsteps * R * 6;
+        s->h_chain_tried = false;
+    }
+    if (to_host && !s->h_chain && !s->h_chain_tried && s->chain_cap * sizeof(double) > kChainDirectBytes) {
+        // (a run that only summarises its chain brings none back and pins nothing)
+        s->h_chain_tried = true;
+        if (hipHostMalloc((void **)&s->h_chain, s->chain_cap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             s->h_chain = nullptr;
         }
-        s->chain_cap = (size_t)nsteps * R * 6;
     }
     if ((rc = sampler_enqueue(c, s, rp, nsteps, stretch_a, store, true, nullptr))) return rc;
     std::vector<double> rows((size_t)R * 6);
@@ -1816,7 +1839,7 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
         // small chains go straight into the caller's arrays (the runtime stages them through its own pinned
         // buffers); big ones land in ours first -- a D2H into megabytes of pageable, untouched memory runs at
         // ~1 GB/s (measured: 3 MB direct 0.43 ms against 1.35 ms staged; 24 MB direct 25 ms against 6 ms staged)
-        via_pinned = s->h_chain != nullptr && (size_t)cells * 6 * sizeof(double) > kChainDirectBytes;
+        via_pinned = to_host && s->h_chain != nullptr && (size_t)cells * 6 * sizeof(double) > kChainDirectBytes;
         if (via_pinned) {
             HIPCHK(hipMemcpyAsync(s->h_chain, s->d_chain_out, (size_t)cells * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         } else {
@@ -1843,7 +1866,7 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
             s->spec_form = 0;
             ++c->flow_fallbacks;
             if (++c->flow_strikes >= kFlowStrikes) { c->flow_strikes = 0; c->flow_rest = kFlowRest; }
-            return sampler_run(c, s, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted, false);
+            return sampler_run(c, s, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted, false, sspec, sout);
         }
         if (err == 9) {
             // (a sharded run: nothing was kept to redo it from)
@@ -1881,6 +1904,11 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
                     if (lnprob) lnprob[(size_t)row * nsteps + t] = q[5];
                 }
             }
+    if (direct) s->resident_nsteps = nsteps;
+    if (sspec) {
+        const size_t cells = (size_t)R * nsteps;
+        return summary_run(c, s->d_chain_out, s->d_chain_out + cells * 5, s->nsrc, nw, nsteps, sspec, sout);
+    }
     return MBB_OK;
 }
 
@@ -1975,20 +2003,27 @@ static void dispatch_variant(int opthin, int noalpha, F &&f)
     else { if (noalpha) f(std::false_type(), std::true_type()); else f(std::false_type(), std::false_type()); }
 }
 
-static int run_prologue(mbb_ctx *c, const double *pars, int n, int opthin, int noalpha,
-                        double wavenorm, int want_peak, double *d_out6)
+// k_prologue on n parameter rows that are on the device already (the rows of a resident chain, or d_sed_pars)
+static int launch_prologue(mbb_ctx *c, const double *d_pars, int n, int opthin, int noalpha,
+                           double wavenorm, int want_peak, double *d_out6)
 {
-    HIPCHK(hipMemcpyAsync(c->d_sed_pars, pars, (size_t)n * 5 * sizeof(double),
-                          hipMemcpyHostToDevice, c->stream));
     const int threads = 64, grid = (n + threads - 1) / threads;
     dispatch_variant(opthin, noalpha, [&](auto OT, auto NA) {
         hipLaunchKernelGGL((k_prologue<decltype(OT)::value, decltype(NA)::value>), dim3(grid),
-                           dim3(threads), 0, c->stream, c->d_sed_pars, n, kUmToGHz / wavenorm,
+                           dim3(threads), 0, c->stream, d_pars, n, kUmToGHz / wavenorm,
                            log(kUmToGHz / wavenorm), want_peak, d_out6, c->d_sed_status,
                            c->d_sed_wk);
     });
     HIPCHK(hipGetLastError());
     return MBB_OK;
+}
+
+static int run_prologue(mbb_ctx *c, const double *pars, int n, int opthin, int noalpha,
+                        double wavenorm, int want_peak, double *d_out6)
+{
+    HIPCHK(hipMemcpyAsync(c->d_sed_pars, pars, (size_t)n * 5 * sizeof(double),
+                          hipMemcpyHostToDevice, c->stream));
+    return launch_prologue(c, c->d_sed_pars, n, opthin, noalpha, wavenorm, want_peak, d_out6);
 }
 
 extern "C" int mbb_sed_prologue_batch(mbb_ctx *c, const double *pars, int n, int opthin,
@@ -2037,18 +2072,10 @@ extern "C" int mbb_sed_eval_batch(mbb_ctx *c, const double *pars, int n, int opt
     return MBB_OK;
 }
 
-extern "C" int mbb_sed_integrate_batch(mbb_ctx *c, const double *pars, int n, int opthin, int noalpha,
-                                       double wavenorm, double numin, double numax, double *out,
-                                       int32_t *status)
+// Gauss-Legendre nodes and weights on [-1, 1], 64 points (Newton on P_n, Abramowitz & Stegun 25.4.29)
+static void gauss_legendre64(double *gx, double *gw)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (n <= 0 || !pars || !out || !(numin > 0.0) || !(numax > numin))
-        return fail(MBB_ERR_ARG, "bad arguments");
     const int ngl = 64;
-    if ((rc = ensure_sed(c, (size_t)n, (size_t)n + 2 * ngl))) return rc;
-    // Gauss-Legendre nodes and weights on [-1, 1] (Newton on P_n, Abramowitz & Stegun 25.4.29)
-    double gx[64], gw[64];
     for (int i = 0; i < ngl; ++i) {
         double x = cos(M_PI * (i + 0.75) / (ngl + 0.5)), pp = 1.0;
         for (int it = 0; it < 100; ++it) {
@@ -2062,6 +2089,20 @@ extern "C" int mbb_sed_integrate_batch(mbb_ctx *c, const double *pars, int n, in
         gx[i] = x;
         gw[i] = 2.0 / ((1.0 - x * x) * pp * pp);
     }
+}
+
+extern "C" int mbb_sed_integrate_batch(mbb_ctx *c, const double *pars, int n, int opthin, int noalpha,
+                                       double wavenorm, double numin, double numax, double *out,
+                                       int32_t *status)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (n <= 0 || !pars || !out || !(numin > 0.0) || !(numax > numin))
+        return fail(MBB_ERR_ARG, "bad arguments");
+    const int ngl = 64;
+    if ((rc = ensure_sed(c, (size_t)n, (size_t)n + 2 * ngl))) return rc;
+    double gx[64], gw[64];
+    gauss_legendre64(gx, gw);
     double *d_gx = c->d_sed_out + n, *d_gw = d_gx + ngl;
     if ((rc = run_prologue(c, pars, n, opthin, noalpha, wavenorm, 0, nullptr))) return rc;
     HIPCHK(hipMemcpyAsync(d_gx, gx, sizeof gx, hipMemcpyHostToDevice, c->stream));
@@ -2078,6 +2119,235 @@ extern "C" int mbb_sed_integrate_batch(mbb_ctx *c, const double *pars, int n, in
                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return MBB_OK;
+}
+
+// ---- posterior summaries of a chain (mbb_summary.hip.h) ------------------------
+static int sum_grow(mbb_ctx *c, void **p, size_t *cap, size_t bytes)
+{
+    if (bytes <= *cap) return MBB_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    free_dev(*p); *p = nullptr; *cap = 0;
+    HIPCHK(hipMalloc(p, bytes));
+    *cap = bytes;
+    return MBB_OK;
+}
+
+constexpr int kSumChunkRows = 1 << 18;      // chain rows a derived column is filled by at a time (bounds the WalkerK buffer)
+
+// The derived columns of spec sp for the resident chain, into a.der[]: the SED kernels are fed the chain's own rows
+// (emcee's layout IS an array of 5-parameter rows), a chunk at a time.
+static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::SumArgs &a, size_t cells)
+{
+    int rc, nder = 0;
+    for (int k = 0; k < 3; ++k) nder += (sp->derived >> k) & 1;
+    if (!nder) return MBB_OK;
+    if ((rc = sum_grow(c, &c->sum.der, &c->sum.c_der, (size_t)nder * cells * sizeof(double)))) return rc;
+    double *der[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0, i = 0; k < 3; ++k)
+        if ((sp->derived >> k) & 1) { der[k] = (double *)c->sum.der + (size_t)(i++) * cells; a.der[k] = der[k]; }
+    const int ngl = 64;
+    const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
+    if ((rc = ensure_sed(c, chunk, chunk * 6 + 2 * ngl))) return rc;
+    double *d_gx = c->d_sed_out + chunk * 6, *d_gw = d_gx + ngl;
+    const double opz = 1.0 + sp->redshift;
+    if (der[1]) {
+        double gx[64], gw[64];
+        gauss_legendre64(gx, gw);
+        HIPCHK(hipMemcpyAsync(d_gx, gx, sizeof gx, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_gw, gw, sizeof gw, hipMemcpyHostToDevice, c->stream));
+    }
+    for (size_t off = 0; off < cells; off += chunk) {
+        const int n = (int)std::min(chunk, cells - off);
+        const double *rows = a.chain + off * 5;
+        const int grid = (n + 255) / 256;
+        if (der[0]) {
+            // peak wavelength: the prologue with want_peak, the fit's model or the reference's (results.py:574-581)
+            const int ot = sp->peak_model ? 0 : c->opthin, na = sp->peak_model ? 0 : c->noalpha;
+            if ((rc = launch_prologue(c, rows, n, ot, na, c->wavenorm, 1, c->d_sed_out))) return rc;
+            hipLaunchKernelGGL(mbbs::k_sum_take, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
+                               (const int32_t *)c->d_sed_status, n, (long long)off, der[0], (int *)c->sum.colstatus,
+                               a.nw, a.nsteps, a.burn, a.thin);
+            HIPCHK(hipGetLastError());
+        }
+        if (der[1]) {
+            // L_IR as postprocess.lir: observer-frame [wavemin, wavemax] (1 + z), prefactor 4 pi Mpc^2 / L_sun (results.py:661)
+            const double minwave = std::min(sp->lir_wavemin, sp->lir_wavemax) * opz,
+                         maxwave = std::max(sp->lir_wavemin, sp->lir_wavemax) * opz;
+            const double prefac = 3.11749657e4 * (sp->lumdist_mpc * sp->lumdist_mpc);
+            if ((rc = launch_prologue(c, rows, n, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+            dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
+                hipLaunchKernelGGL((k_sed_integrate<decltype(OT)::value, decltype(NA)::value>), dim3(n), dim3(64), 0,
+                                   c->stream, c->d_sed_wk, kUmToGHz / maxwave, kUmToGHz / minwave, d_gx, d_gw, ngl, 8,
+                                   c->d_sed_out);
+            });
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(mbbs::k_sum_lir, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
+                               (const int32_t *)c->d_sed_status, n, (long long)off, prefac, der[1],
+                               (int *)c->sum.colstatus, a.nw, a.nsteps, a.burn, a.thin);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (der[2]) {
+        // dust mass: the constants of results.py:775-790 as postprocess.dustmass forms them
+        mbbs::DustArgs d;
+        const double dl = sp->lumdist_mpc * 3.0856775814913673e24;
+        const double wavenorm_rest = c->wavenorm / opz, nunorm_rest = 299792458e6 / wavenorm_rest;
+        d.opz = opz;
+        d.dl2 = dl * dl;
+        d.temp_fac = 6.6260693e-27 * nunorm_rest / 1.38065e-16;
+        d.bnu_fac = 2 * 6.6260693e-27 * (nunorm_rest * nunorm_rest * nunorm_rest) / (299792458e2 * 299792458e2);
+        d.knu_fac = wavenorm_rest / sp->kappa_wave;
+        d.k10 = 10.0 * sp->kappa;
+        d.msolar8 = 1.97792e41;
+        d.wavenorm = c->wavenorm;
+        d.opthin = c->opthin;
+        hipLaunchKernelGGL(mbbs::k_sum_dustmass, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream,
+                           a.chain, (long long)cells, d, der[2]);
+        HIPCHK(hipGetLastError());
+    }
+    return MBB_OK;
+}
+
+// Summarise a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
+static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
+                       const mbb_summary_spec *sp, const mbb_summary_out *o)
+{
+    using namespace mbbs;
+    static_assert(kCols == MBB_SUMMARY_COLS && kMaxPct == MBB_SUMMARY_MAX_PCT, "summary sizes");
+    static_assert(kStEmpty == MBB_SUM_EMPTY && kStNaN == MBB_SUM_HAS_NAN && kStAbsent == MBB_SUM_ABSENT &&
+                  kStRowShift == MBB_SUM_ROW_SHIFT, "summary status bits");
+    if (!sp || !o || !o->n_used || !o->mean || !o->min || !o->max || !o->pct || !o->status || !o->cov || !o->best ||
+        !o->best_index)
+        return fail(MBB_ERR_ARG, "null summary argument");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    if (sp->npct < 1 || sp->npct > kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per summary");
+    for (int k = 0; k < sp->npct; ++k)
+        if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
+    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    if (sp->derived & ~7) return fail(MBB_ERR_ARG, "unknown derived column");
+    if ((sp->derived & (MBB_SUM_LIR | MBB_SUM_DUSTMASS)) &&
+        !(sp->redshift > -1.0 && sp->redshift < INFINITY && sp->lumdist_mpc > 0.0 && sp->lumdist_mpc < INFINITY))
+        return fail(MBB_ERR_ARG, "L_IR and dust mass need a redshift and a luminosity distance");
+    if ((sp->derived & MBB_SUM_LIR) && !(sp->lir_wavemin > 0.0 && sp->lir_wavemax > 0.0))
+        return fail(MBB_ERR_ARG, "wavelengths must be positive");
+    if ((sp->derived & MBB_SUM_DUSTMASS) && !(sp->kappa > 0.0 && sp->kappa_wave > 0.0))
+        return fail(MBB_ERR_ARG, "kappa and kappa_wave must be positive");
+    const int nkept = (nsteps - sp->burn + sp->thin - 1) / sp->thin;
+    const long long n = (long long)nw * nkept;
+    if (n > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 samples per column");
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    SumArgs a;
+    memset(&a, 0, sizeof a);
+    a.chain = d_chain; a.lnprob = d_lnprob;
+    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin; a.nkept = nkept; a.n = n;
+    a.ncol = 5;
+    for (int k = 0; k < 5; ++k) a.col[k] = k;
+    for (int k = 0; k < 3; ++k) if ((sp->derived >> k) & 1) a.col[a.ncol++] = 5 + k;
+    a.npct = sp->npct;
+    for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
+    for (int k = 0; k < kCols; ++k) {
+        a.has_lo[k] = sp->has_lo[k] != 0; a.has_hi[k] = sp->has_hi[k] != 0;
+        a.lo[k] = sp->lo[k]; a.hi[k] = sp->hi[k];
+    }
+    // One workgroup per (source, column) when those fill the device by themselves; else a column is cut into
+    // splits of at most 16384 samples (64 per thread) whose partial sums and histograms are merged.
+    const size_t ncolumns = (size_t)nsrc * a.ncol;
+    a.splits = ncolumns >= 1024 ? 1 : (int)std::min<long long>(kMaxSplits, (n + 16383) / 16384);
+    a.per_split = (n + a.splits - 1) / a.splits;
+    int rc;
+    mbb_ctx::SumWork &w = c->sum;
+    const size_t np = (size_t)sp->npct;
+    const size_t nd = (size_t)nsrc * (kCols * (3 + np) + 25 + 6);           // doubles of the result block
+    const size_t out_bytes = (size_t)nsrc * kCols * sizeof(long long) + nd * sizeof(double) +
+                             (size_t)nsrc * (kCols + 2) * sizeof(int);
+    if ((rc = sum_grow(c, &w.part, &w.c_part, ncolumns * a.splits * kStatWords * sizeof(double)))) return rc;
+    if ((rc = sum_grow(c, &w.state, &w.c_state, ncolumns * sizeof(ColState)))) return rc;
+    if ((rc = sum_grow(c, &w.hist, &w.c_hist, ncolumns * a.splits * kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    if ((rc = sum_grow(c, &w.covpart, &w.c_covpart, (size_t)nsrc * a.splits * kCovWords * sizeof(double)))) return rc;
+    if ((rc = sum_grow(c, &w.colstatus, &w.c_colstatus, (size_t)nsrc * kCols * sizeof(int)))) return rc;
+    if ((rc = sum_grow(c, &w.outbuf, &w.c_outbuf, out_bytes))) return rc;
+    a.part = (double *)w.part; a.state = (ColState *)w.state; a.hist = (unsigned int *)w.hist;
+    a.covpart = (double *)w.covpart; a.colstatus = (int *)w.colstatus;
+    char *ob = (char *)w.outbuf;
+    a.o_nused = (long long *)ob;
+    a.o_mean = (double *)(ob + (size_t)nsrc * kCols * sizeof(long long));
+    a.o_min = a.o_mean + (size_t)nsrc * kCols;
+    a.o_max = a.o_min + (size_t)nsrc * kCols;
+    a.o_pct = a.o_max + (size_t)nsrc * kCols;
+    a.o_cov = a.o_pct + (size_t)nsrc * kCols * np;
+    a.o_best = a.o_cov + (size_t)nsrc * 25;
+    a.o_status = (int *)(a.o_best + (size_t)nsrc * 6);
+    a.o_bestidx = a.o_status + (size_t)nsrc * kCols;
+    HIPCHK(hipMemsetAsync(w.colstatus, 0, (size_t)nsrc * kCols * sizeof(int), c->stream));
+    if ((rc = summary_fill_derived(c, sp, a, cells))) return rc;
+    const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits), gsrc((unsigned)nsrc, (unsigned)a.splits);
+    hipLaunchKernelGGL(k_sum_stats, gcol, dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_sum_begin, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a);
+    for (int pass = 0; pass < 8; ++pass) {
+        hipLaunchKernelGGL(k_sum_hist, gcol, dim3(kThreads), 0, c->stream, a, pass);
+        hipLaunchKernelGGL(k_sum_pick, dim3((unsigned)ncolumns), dim3(kThreads), 0, c->stream, a);
+    }
+    hipLaunchKernelGGL(k_sum_cov, gsrc, dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_sum_finish, dim3((unsigned)(((size_t)nsrc * kCols + 63) / 64)), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    std::vector<char> host(out_bytes);
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const char *hb = host.data();
+    const size_t sc = (size_t)nsrc * kCols;
+    memcpy(o->n_used, hb, sc * sizeof(long long));
+    const double *hd = (const double *)(hb + sc * sizeof(long long));
+    memcpy(o->mean, hd, sc * sizeof(double));
+    memcpy(o->min, hd + sc, sc * sizeof(double));
+    memcpy(o->max, hd + 2 * sc, sc * sizeof(double));
+    memcpy(o->pct, hd + 3 * sc, sc * np * sizeof(double));
+    memcpy(o->cov, hd + 3 * sc + sc * np, (size_t)nsrc * 25 * sizeof(double));
+    memcpy(o->best, hd + 3 * sc + sc * np + (size_t)nsrc * 25, (size_t)nsrc * 6 * sizeof(double));
+    const int *hi = (const int *)(hd + nd);
+    memcpy(o->status, hi, sc * sizeof(int));
+    memcpy(o->best_index, hi + sc, (size_t)nsrc * 2 * sizeof(int));
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_summary(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                                 const mbb_summary_spec *spec, const mbb_summary_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!chain || !lnprob || nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "bad arguments");
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    double *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, cells * 6 * sizeof(double)));
+    hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + cells * 5, lnprob, cells * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(MBB_ERR_HIP, "upload of the chain", e); }
+    rc = summary_run(c, d, d + cells * 5, nsrc, nw, nsteps, spec, out);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int mbb_sampler_run_summary(mbb_ctx *c, void *sp, int nsteps, double stretch_a, const mbb_summary_spec *spec,
+                                       const mbb_summary_out *out, double *chain, double *lnprob, double *pos_out,
+                                       double *lnprob_out, double *naccepted)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    mbb_sampler_state *s = (mbb_sampler_state *)sp;
+    if (!s || nsteps < 0 || !(stretch_a > 1.0) || !spec || !out) return fail(MBB_ERR_ARG, "bad sampler arguments");
+    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
+    ShardPlan p;
+    if ((rc = shard_plan(c, s, p))) return rc;
+    if (p.collective)
+        return fail(MBB_ERR_STATE, "a sharded sampler run cannot be summarised on the device: a rank holds only its own "
+                                   "walkers' chain");
+    if (nsteps == 0) {
+        if (s->resident_nsteps <= 0)
+            return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
+        const size_t cells = (size_t)s->rows() * s->resident_nsteps;
+        return summary_run(c, s->d_chain_out, s->d_chain_out + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    }
+    return sampler_run(c, s, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted, true, spec, out);
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

@@ -69,6 +69,9 @@ class DeviceEnsembleSampler(object):
         self._chain = np.empty(lead + (0, self.dim))
         self._lnprob = np.empty(lead + (0,))
         self._last = None
+        if getattr(self, "summary", None) is not None:
+            self.summary.drop_chain()
+        self.summary = None
         if self._h is not None:
             _native._check(self._ctx.lib.mbb_sampler_reset(self._ctx.h, self._h))
 
@@ -108,9 +111,21 @@ class DeviceEnsembleSampler(object):
     def random_state(self):
         return self.seed
 
-    def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, **unused):
-        """N stretch-move steps from pos0 [nw, 5]; returns (pos, lnprob, rstate)."""
+    def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, **unused):
+        """N stretch-move steps from pos0 [nw, 5]; returns (pos, lnprob, rstate).
+
+        summary=True, or a dict of ``results.chain_summary``'s keywords (percentile, burn, thin, derived, redshift,
+        lumdist_mpc, kappa, kappa_wave, lir_range, peak_model, clip, percentiles): the chain of this run is
+        summarised on the device and ``sampler.summary`` is the ``results.ChainSummary`` of it; with
+        storechain=False no chain crosses the bus.  The chain stays on the device until the sampler's next run
+        (or reset), so that the summary can compute further percentiles on demand."""
         ctx, h = self._handle()
+        req = None
+        if summary is not None and summary is not False:
+            if ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None):
+                raise ValueError("a sharded sampler run cannot be summarised on the device: a rank holds only its "
+                                 "own walkers' chain")
+            req = self._summary_request({} if summary is True else dict(summary), int(N))
         # sharded with the one-hop exchange (parallel.ipc_exchange_setup): the ranks are
         # held together around set_state, because a peer's kernel writes into this rank's
         # copy of the ensemble
@@ -148,10 +163,22 @@ class DeviceEnsembleSampler(object):
         lnprob = np.empty(lead)
         nacc = np.zeros(lead)
         fallbacks = ctx.info("flow_fallbacks")
-        rc = ctx.lib.mbb_sampler_run(ctx.h, h, N, self.a,
-                                     _native._d(chain) if storechain else None,
-                                     _native._d(lnp) if storechain else None,
-                                     _native._d(pos), _native._d(lnprob), _native._d(nacc))
+        if self.summary is not None:
+            self.summary.drop_chain()            # (the chain it could go back to is about to be overwritten)
+            self.summary = None
+        if req is None:
+            rc = ctx.lib.mbb_sampler_run(ctx.h, h, N, self.a,
+                                         _native._d(chain) if storechain else None,
+                                         _native._d(lnp) if storechain else None,
+                                         _native._d(pos), _native._d(lnprob), _native._d(nacc))
+        else:
+            from . import results
+            raw = results._Raw(self.nsources, len(req.qs))
+            spec, out = req.spec(), raw.out()
+            rc = ctx.lib.mbb_sampler_run_summary(ctx.h, h, N, self.a, C.byref(spec), C.byref(out),
+                                                 _native._d(chain) if storechain else None,
+                                                 _native._d(lnp) if storechain else None,
+                                                 _native._d(pos), _native._d(lnprob), _native._d(nacc))
         if rc == -2:
             raise ValueError(ctx.lib.mbb_last_error().decode())
         _native._check(rc)
@@ -173,7 +200,35 @@ class DeviceEnsembleSampler(object):
                 self._chain = np.concatenate((self._chain, chain), axis=ax)
                 self._lnprob = np.concatenate((self._lnprob, lnp), axis=ax)
         self._last = (pos, lnprob)
+        if req is not None:
+            self.summary = results.ChainSummary(self.lnprobfn, req, raw, self.nsources > 1, self._summarise_again,
+                                                self._summary_percentile)
         return pos, lnprob, self.seed
+
+    def _summary_request(self, kw, nsteps):
+        from . import results
+        cens = [float(p) for p in np.atleast_1d(kw.pop("percentile", 68.3))]
+        qs = []
+        for q in [q for p in cens for q in results._pval(p)] + [float(q) for q in kw.pop("percentiles", ())]:
+            if q not in qs:
+                qs.append(q)
+        self._summary_percentile = cens[0]
+        req = results._Request(qs, **kw)
+        if nsteps < 1 or req.burn >= nsteps:
+            raise ValueError("burn leaves no step of the chain")
+        return req
+
+    def _summarise_again(self, req):
+        """Another summary of the chain the last summarised run left on the device (mbb_sampler_run_summary, 0 steps)."""
+        from . import results
+        ctx, h = self._handle()
+        raw = results._Raw(self.nsources, len(req.qs))
+        spec, out = req.spec(), raw.out()
+        rc = ctx.lib.mbb_sampler_run_summary(ctx.h, h, 0, self.a, C.byref(spec), C.byref(out), None, None, None, None, None)
+        if rc == -2:
+            raise ValueError(ctx.lib.mbb_last_error().decode())
+        _native._check(rc)
+        return raw
 
     def sample(self, p0, lnprob0=None, rstate0=None, iterations=1, storechain=True, chunk=64):
         """emcee's generator form (``for pos, lnprob, rstate in sampler.sample(p0, iterations=N)``): the ensemble after

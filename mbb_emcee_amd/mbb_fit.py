@@ -137,8 +137,12 @@ class mbb_fitter(object):
                                                                 lo[worst], hi[worst]))
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
-    def run(self, nburn, nsteps, p0, verbose=False):
-        """Burn in for nburn steps, reset, then sample nsteps steps per walker."""
+    def run(self, nburn, nsteps, p0, verbose=False, summary=None):
+        """Burn in for nburn steps, reset, then sample nsteps steps per walker.
+        summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
+        summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc)."""
+        if summary is not None and summary is not False and not hasattr(self.sampler, "_summarise_again"):
+            raise ValueError("summary= needs sampler=\"device\"")
         if not self.like.data_read:
             raise Exception("Data not read, needed to do fit")
         if verbose:
@@ -170,7 +174,10 @@ class mbb_fitter(object):
                              "{:d}".format(nsteps))
         if verbose:
             print("  Doing main chain with {:d} steps".format(nsteps))
-        self.sampler.run_mcmc(pos, nsteps, rstate0=rstate)
+        if summary is not None and summary is not False:
+            self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, summary=summary)
+        else:
+            self.sampler.run_mcmc(pos, nsteps, rstate0=rstate)
         self._sampled = True
 
         if verbose:
@@ -204,6 +211,8 @@ for _name, _attr, _doc in (("noalpha", "_noalpha", "Not using the blue side powe
                            ("sampled", "_sampled", "Has the distribution been sampled?"),
                            ("fixed", "_fixed", "Which parameters are held fixed")):
     setattr(mbb_fitter, _name, _view(_attr, _doc))
+mbb_fitter.summary = property(lambda self: getattr(self.sampler, "summary", None),
+                              doc="results.ChainSummary of the main chain when run() was given summary=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,
                                          doc="Is passband integration in use?")
 

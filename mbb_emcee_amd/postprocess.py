@@ -4,8 +4,9 @@ The reference computes these one chain step at a time in ``mbb_results``
 (reference mbb_emcee/results.py:534-801): peak wavelength (``max_wave`` per
 step), L_IR (``freq_integrate`` = scipy quad per step) and dust mass, skipping
 steps that repeat the previous one.  Here every step of every walker is one row
-of a batched kernel call, so no de-duplication is needed.  Only the arithmetic
-is provided; the results object, its HDF5 layout and the cosmology
+of a batched kernel call, so no de-duplication is needed.  This module provides
+the per-entry arithmetic; the reductions of the results object (credible
+intervals, limits, best fit) are in ``results``; its HDF5 layout and the cosmology
 (astropy) stay out of scope -- pass the luminosity distance in.
 
 Parity: PINNED.  Every function here is checked against what the reference's own

@@ -39,6 +39,9 @@ def build_parser():
     p.add_argument("--sampler", choices=["device", "native"], default="device")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--get_peaklambda", action="store_true")
+    p.add_argument("--summary", action="store_true",
+                   help="summarise the chain on the device (means, 68.3%% and 95.4%% intervals, covariance, best fit; "
+                        "with --get_peaklambda the peak wavelength too): printed, and added to the .npz")
     p.add_argument("-v", "--verbose", action="store_true")
     for nm, dflt in zip(NAMES, (10.0, 2.0, 2500.0, 4.0, 40.0)):
         p.add_argument("--init" + nm, type=float, default=dflt)
@@ -79,7 +82,10 @@ def main(argv=None):
 
     p0init = np.array([getattr(a, "init" + nm) for nm in NAMES])
     p0 = fit.generate_initial_values(p0init, np.array([2, 0.2, 100, 0.3, 5.0]))   # :285-291
-    fit.run(a.burn, a.nsteps, p0, verbose=a.verbose)
+    summary = None
+    if a.summary:
+        summary = dict(percentile=(68.3, 95.4), derived=("peaklambda",) if a.get_peaklambda else ())
+    fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary)
     chain, lnp = fit.sampler.chain, fit.sampler.lnprobability
     out = dict(chain=chain, lnprobability=lnp, acceptance_fraction=fit.sampler.acceptance_fraction,
                parnames=np.array(NAMES), noalpha=a.noalpha, opthin=a.opthin, wavenorm=a.wavenorm,
@@ -87,6 +93,9 @@ def main(argv=None):
                data_flux_unc=fit.like.data_flux_unc)
     if a.get_peaklambda:
         out["peaklambda"] = postprocess.peak_wavelength(fit.like, chain)
+    if a.summary:
+        out.update(fit.summary.arrays())
+        print(fit.summary)
     np.savez_compressed(a.outfile, **out)
     if a.verbose:
         flat = chain.reshape(-1, 5)
