@@ -134,7 +134,7 @@ __device__ __forceinline__ void vexp(double (&out)[K], A... arg)
         const double q = mbbm::expm1_reduced(mbbm::reduce_ln2(row_pick(arg...), k));
         const double e = ldexp(1.0 + q, k);                     // m_exp
         const double t = ldexp(1.0, k);
-        const double m = fma(t, q, t - 1.0);                    // m_expm1
+        const double m = k >= 1024 ? e : fma(t, q, t - 1.0);    // m_expm1
         row_scatter<K>(((M1 >> (threadIdx.x & 15)) & 1u) ? m : e, out);
     } else {
         const double a[K] = {arg...};
@@ -161,7 +161,9 @@ __device__ __forceinline__ void vlog(double (&out)[K], A... arg)
 // (modified_blackbody.py:144-150).
 __device__ __forceinline__ void h_and_dh(double y, double E, double &h, double &dh)
 {
-    const double rE = m_div(1.0, E);
+    // (the reciprocal without m_div's residual correction: a few 1e-16 of h move the root by as little; E = inf
+    // gives NaN here, and only where `big` discards it)
+    const double rE = mbbm::m_rcp(E);
     const double hh = y * rE, dd = (fma(-y, rE, 1.0) - y) * rE;
     const bool tiny = y < 1e-4, big = !(y < 700.0);
     h = big ? 0.0 : (tiny ? fma(y * y, 1.0 / 12.0, fma(-0.5, y, 1.0)) : hh);
@@ -236,10 +238,16 @@ __device__ inline float thick_merge_root_f32(float alpha, float beta, float lx0,
     return (u >= ulo && u <= uhi) ? u : 0.5f * (ulo + uhi);
 }
 
-// Stage 2, fp64 Newton in u with the analytic derivative
+// Stage 2, fp64 in u with the analytic derivative
 //   dg/du = x (1 - e^-x A) - (1 - e^-x) beta^2 h'(y) y,   A = 3 + alpha + beta h
-// inside the analytic bracket, accepted when a step is below 1e-6 (quadratic
-// convergence: < 1e-12 left; brentq in the reference stops at 2e-12).  Normally one
+// and second derivative
+//   g'' = x - x e^-x A (1 - x) - 2 x e^-x A' - (1 - e^-x) A'',  A' = beta^2 y h',  A'' = beta^3 y (h' + y h'')
+// inside the analytic bracket: Halley's iteration, accepted when a step is below 1e-6; what
+// is left is then of third order in the step.  (Rounds 1-7 took Newton steps.  A Newton
+// step leaves (g''/2g') step^2 in u, and g'' grows with beta^3: against the true roots
+// (tests/test_device_math_gpu.py) steps of 1e-6 -- what stage 1 leaves where its fp32
+// expm1(y) cancels, y a few hundredths -- left 5.3e-12 in x = e^u at beta = 8, and steps
+// of 2.5e-7 still 2e-12 at beta = 20; brentq in the reference stops at 2e-12.)  Normally one
 // evaluation.  An evaluation is two rounds of independent exps -- (x, y), then
 // (e^-x, expm1(y)) -- so each round is one row call.  PB: the prologue's own
 // normalisation exps ride in the idle lanes of the first evaluation:
@@ -290,25 +298,37 @@ __device__ inline double thick_merge_root(double alpha, double beta, double lx0,
         // (every fused multiply-add is written out: the library is built with -ffp-contract=off, so
         // that this arithmetic rounds the same wherever it is inlined -- the sampler forms are held
         // to one another bit for bit)
+        // h' is the last thing to arrive (a division behind expm1(y)): what multiplies it is formed beside it, so that
+        // g' and g'' follow it by one and two operations.  (yc: beyond 700 h and h' are 0 whatever y is, and an
+        // infinite y must not meet them in a product.)
         const double A = fma(beta, h, 3.0 + alpha);
         const double g = fma(-om, A, x);
-        const double dg = fma(x, fma(-em, A, 1.0), -(om * beta * beta * dh * y));
+        const double yc = fmin(y, 1000.0), b2y = beta * beta * yc, xe = x * em, omb = om * b2y;
+        const double dg = fma(-omb, dh, x * fma(-em, A, 1.0));
+        // h' + y h'' = h' (1 - y - 2 h) - h  (from h' = (1 - y - h)/E, E' = E + 1)
+        const double P = fma(dh, fma(-2.0, h, 1.0 - yc), -h);
+        const double d2g = fma(-(omb * beta), P, fma(-(xe * ((2.0 * beta * beta) * yc)), dh, fma(-(xe * A), 1.0 - x, x)));
         if (iters) *iters = it + 1;
         if (g == 0.0) { xroot = x; yroot = y; status = ROW_OK; if (PB && kappa && it == 0) *kappa = k0; break; }
         if (g < 0.0) ulo = u; else uhi = u;
-        const double step = m_div(-g, dg);          // dg > 0 around the root
+        // Halley's step -g / (dg - g g''/2dg) = -g dg / (dg^2 - g g''/2), dg > 0 around the root: g'' is formed
+        // beside dg and the one division is a reciprocal without m_div's residual correction (an accepted step is
+        // below 1e-6: a relative 1e-15 of it is 1e-21).  Far from the root the denominator may change sign; the
+        // bracket below catches such a step like any other that leaves it.
+        const double step = -(g * dg) * mbbm::m_rcp(fma(-0.5 * g, d2g, dg * dg));
         if (fabs(step) <= 1e-6) {
-            // x e^step and y e^(beta step) to third order: exact to 1e-24
-            u += step;
-            xroot = x * fma(step, fma(step, fma(step, 1.0 / 6.0, 0.5), 1.0), 1.0);
-            const double bs = beta * step;
+            const double hs = step;
+            // x e^hs to second order (hs^3/6 < 2e-19) and y e^(beta hs) to third
+            u += hs;
+            xroot = x * fma(hs, fma(hs, 0.5, 1.0), 1.0);
+            const double bs = beta * hs;
             yroot = y * fma(bs, fma(bs, fma(bs, 1.0 / 6.0, 0.5), 1.0), 1.0);
             status = ROW_OK;
             // kappa is stationary at the root: d ln kappa / du = s(u) = A - x/(1 - e^-x) =
             // -g/(1 - e^-x), zero there (it IS the merge condition), so over the step
             // ln kappa changes by s step + s' step^2/2 = s step/2 (s = -s' step to first
             // order): kappa(root) = kappa(u) (1 + s step / 2), error O(step^3) < 1e-18
-            if (PB && kappa && it == 0) *kappa = k0 * fma(-0.5 * step, m_div(g, om), 1.0);
+            if (PB && kappa && it == 0) *kappa = k0 * fma(-0.5 * step, g * mbbm::m_rcp(om), 1.0);
             break;
         }
         double un = u + step;

@@ -7,17 +7,27 @@
 // passband loop).  These versions use one shared range reduction, an Estrin
 // polynomial (dependency depth 5 instead of 13) and no branches.
 //
-// Accuracy (tools/test_math_host.cpp, 4e6 points each, vs long double libm):
-//   m_exp, m_expm1  <= 2 ulp over [-745, 709.7];  m_log <= 2 ulp;  m_div <= 1.5 ulp.
+// Accuracy, the contract (in ulp of the true value; subnormal results in subnormal spacing):
+//   m_exp, m_exp_t, m_expm1  <= 2 ulp over [-745, 709.78], expm1 relative down to |x| = 2^-60;
+//   exactly 0 (-1) below -746 and +inf above 709.79, never NaN;  m_log <= 2 ulp on normal x;
+//   m_div <= 1.5 ulp on its domain (see there).
+// Held ON THE DEVICE by tests/test_device_math_gpu.py through the probe tests/_device_probe.hip: about
+// 1300 curated points per function against 50-digit values (tests/golden/hp_math.npz: the ends of the
+// range, the seams of both reductions, 2^-k, both sides of sqrt(1/2) at every binade, the whole exponent
+// range of the quotient) and 4e6 seeded points each against long double.  Observed on an MI355X:
+// m_exp 1.02, m_exp_t 1.30, m_expm1 1.90, m_log 1.15, m_div 0.60 ulp (profiles/r08/parity_report.json).
 //
-// Compiles for the host too (MBB_MATH_HOST) so the accuracy test runs on CPU.
+// Compiles for the host too (MBB_MATH_HOST; tests/test_device_math_cpu.py runs the same points through
+// that build).  The host variant differs where the device uses an instruction of its own: the reciprocal
+// seed, the saturating conversion of reduce_ln2_256, the fraction and the row address of polyrow_eval.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #ifdef MBB_MATH_HOST
 #define MBB_HD inline
-static inline double m_rcp_seed(double b) { return (double)(1.0f / (float)b); }
+// (a float reciprocal of the mantissa, rescaled: as coarse as a hardware seed at every exponent a double has)
+static inline double m_rcp_seed(double b) { int e; const double m = frexp(b, &e); return ldexp((double)(1.0f / (float)m), -e); }
 #else
 #include <hip/hip_runtime.h>
 #define MBB_HD __device__ __forceinline__
@@ -62,13 +72,15 @@ MBB_HD double m_exp(double x)
     return ldexp(1.0 + q, k);
 }
 
-// expm1(x) = 2^k (e^r - 1) + (2^k - 1)
+// expm1(x) = 2^k (e^r - 1) + (2^k - 1).  From k = 1024 on 2^k is inf, and inf q + inf is NaN wherever r < 0 -- the
+// upper half of every such interval, 709.44 <= x < 709.78 (where the true value is still finite) among them: there
+// the result is e^x itself, the 1 being far below its last bit.
 MBB_HD double m_expm1(double x)
 {
     int k;
     const double q = expm1_reduced(reduce_ln2(x, k));
-    const double t = ldexp(1.0, k);                // inf for k >= 1024, as wanted
-    return fma(t, q, t - 1.0);
+    const double t = ldexp(1.0, k);
+    return k >= 1024 ? ldexp(1.0 + q, k) : fma(t, q, t - 1.0);
 }
 
 // ---- table-driven variants for the sample loop --------------------------------
@@ -77,8 +89,10 @@ MBB_HD double m_expm1(double x)
 // tools/gen_exp2_table.py's table: 2^(j/256) rounded to nearest) and a degree-4
 // polynomial for e^r - 1 (truncation r^5/120 <= 3.8e-17): 4 polynomial operations
 // instead of 15, one fma for the table value.  (Rounds 2-5 carried a hi/lo pair per
-// entry and one more operation per exp: 0.6 ulp instead of 1.1 here, which nothing
+// entry and one more operation per exp: 0.6 ulp instead of the 1.3 measured here, which nothing
 // downstream sees -- the stated tolerance is 1e-12 -- at 8 more bytes of LDS per sample.)
+// Bound: 2 ulp, that of the m_exp it replaces -- half an ulp from the rounded table entry, half from
+// the final fma, and the reduction's and the degree-4 remainder's share stays below one.
 constexpr int kExp2N = 256;
 #ifdef MBB_MATH_HOST
 static const double kExp2Tab[kExp2N] = {
@@ -162,10 +176,21 @@ MBB_HD double polyrow_eval(const double *tab, double X)
     return fma(p, t, c[0]);
 }
 
-// a / b for finite a and finite b != 0, or b = +inf (the quotient is then 0).
-// v_rcp_f64 is good to 4.6e-8 (measured); one Newton step squares that and the
-// residual correction of the quotient multiplies the two errors: <= 1 ulp
-// (1e6 random pairs against long double, same as with two steps).
+// a / b.  Domain: a finite; b a NORMAL double of either sign, 2^-1022 <= |b| <= 8e307; the quotient
+// finite (|a / b| below 1.7e308).  There: <= 1.5 ulp, subnormal quotients in subnormal spacing (the
+// hardware seed, one Newton step that squares its error, and the residual correction of the quotient;
+// observed 0.6 ulp).  Outside it the result is NOT IEEE's -- measured on the device, and held there by
+// tests/test_device_math_gpu.py::test_m_div_outside_its_domain_is_what_the_header_says:
+//   * b above 8e307, +inf included, is taken for 8e307: the result is a / 8e307 = 1.25e-308 a, which is 0
+//     only for a = 0 (what the callers divide by inf is a Planck factor at x > 709.78: 1e-308 of its numerator is as
+//     good as the 0 the reference returns there);
+//   * |b| below 2^-1024 (1/b overflows; a subnormal b): v_rcp_f64 gives inf, the Newton step
+//     inf (2 - b inf) = -inf: an infinity of the WRONG sign;
+//   * a quotient that overflows: a r = inf and the residual inf - inf: NaN.
+// Never a finite wrong value in the last two, so the kernels' non-finite checks catch them.  The
+// callers stay inside: every denominator is T, expm1 of a positive argument, the slope of a convex
+// function above its root, kappa, or m + 1 in m_log -- normal and far from either end for parameters a
+// prior admits; a row whose scalars come out non-finite is reported, not used.
 MBB_HD double m_div(double a, double b)
 {
     b = fmin(b, 8.0e307);
@@ -177,6 +202,14 @@ MBB_HD double m_div(double a, double b)
 #endif
     const double q = a * r;
     return fma(fma(-b, q, a), r, q);
+}
+
+// 1 / b to a few 1e-16 relative (the seed and its Newton step, no residual correction), b in m_div's domain: for
+// quotients that only steer an iteration.
+MBB_HD double m_rcp(double b)
+{
+    const double r = m_rcp_seed(b);
+    return r * fma(-b, r, 2.0);
 }
 
 // log(x), x > 0 finite normal.  x = 2^e m, m in [sqrt(1/2), sqrt(2));
