@@ -147,7 +147,11 @@ int mbb_roof_probe(mbb_ctx *ctx, const double pars[5], int reps, double *seconds
  * independent ensembles of nwalkers each in the same launches; every array then
  * has a leading nsrc dimension.  "Fixed" parameters work as in the reference: a column
  * of p0 with zero scatter is preserved exactly by the stretch move
- * (mbb_fit.py:442-443). */
+ * (mbb_fit.py:442-443), and the accept test's power of z is (columns of the ensemble
+ * that are not constant over its walkers) - 1, counted by mbb_sampler_set_state: the
+ * stretch move's Jacobian in the space the walkers span (the reference's dim - 1 = 4
+ * widens the posterior of a fit with fixed parameters).  The sources of a multi-source
+ * state must agree on that number (MBB_ERR_ARG otherwise). */
 int mbb_sampler_create(mbb_ctx *ctx, int nwalkers, unsigned long long seed, void **sampler);
 int mbb_sampler_destroy(mbb_ctx *ctx, void *sampler);
 int mbb_sampler_reset(mbb_ctx *ctx, void *sampler);          /* zero the acceptance counts */

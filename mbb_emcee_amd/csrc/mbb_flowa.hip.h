@@ -325,6 +325,7 @@ __global__ void __launch_bounds__(1024) k_flowa(const LikeArgs a_val)
         MBB_FA_COMMON();
         MBB_FM_WAITS();
         MBB_PIN(a.c_count); MBB_PIN(a.step); MBB_PIN(a.seed); MBB_PIN(a.stretch_a); MBB_PIN(a.nw); MBB_PIN(a.errflag); MBB_PIN(a.n);
+        MBB_PIN(a.zpow);
         MBB_PIN(a.lowlim[0]); MBB_PIN(a.lowlim[1]); MBB_PIN(a.lowlim[2]); MBB_PIN(a.lowlim[3]); MBB_PIN(a.lowlim[4]);
         MBB_PIN(a.nunorm); MBB_PIN(a.lnunorm); MBB_PIN(a.has_uplim); MBB_PIN(a.has_gprior);
         __builtin_amdgcn_s_setprio(3);
@@ -417,7 +418,7 @@ __global__ void __launch_bounds__(1024) k_flowa(const LikeArgs a_val)
                             else { wk[l].status = k.status; wk[l].pad = k.pad; }
 #pragma unroll
                             for (int i = 0; i < 5; ++i) rj[i] = p[i];
-                            rj[5] = 4.0 * lo[2];                  // (dim - 1) ln z, dim = 5
+                            rj[5] = a.zpow * lo[2];               // (d - 1) ln z, d = columns the ensemble spans
                             rj[6] = lo[3];                        // ln u
                             rj[7] = pen_u;
                             rj[8] = pen_g;

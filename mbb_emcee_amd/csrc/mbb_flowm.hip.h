@@ -547,7 +547,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
         MBB_ROLE_ARGS();
         MBB_FM_COMMON();
         MBB_FM_WAITS();
-        MBB_PIN(a.c_count); MBB_PIN(a.step); MBB_PIN(a.seed); MBB_PIN(a.stretch_a); MBB_PIN(a.nw); MBB_PIN(a.errflag);
+        MBB_PIN(a.c_count); MBB_PIN(a.step); MBB_PIN(a.seed); MBB_PIN(a.stretch_a); MBB_PIN(a.nw); MBB_PIN(a.errflag); MBB_PIN(a.zpow);
         MBB_PIN(a.lowlim[0]); MBB_PIN(a.lowlim[1]); MBB_PIN(a.lowlim[2]); MBB_PIN(a.lowlim[3]); MBB_PIN(a.lowlim[4]);
         MBB_PIN(a.nunorm); MBB_PIN(a.lnunorm); MBB_PIN(a.has_uplim); MBB_PIN(a.has_gprior);
         const int cb = role - 1;                                  // this wave takes the half-steps j = cb mod kFmNC
@@ -731,7 +731,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 double *pr = prop + bj * kFmProp;
 #pragma unroll
                 for (int i = 0; i < 5; ++i) { pr[i] = p[i]; pr[9 + i] = snv[i]; }
-                pr[5] = 4.0 * lo[2];                              // (dim - 1) ln z, dim = 5
+                pr[5] = a.zpow * lo[2];                           // (d - 1) ln z, d = columns the ensemble spans
                 pr[6] = lo[3];                                    // ln u
                 lds_post(ctl + kFmReady + bj, j + 1);             // (the quadrature may start; the penalties follow)
 #ifdef MBB_STAMPS

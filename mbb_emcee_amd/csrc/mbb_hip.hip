@@ -890,7 +890,7 @@ static int lnlike_shape(mbb_ctx *c, int n, LnlikeShape &g, LikeArgs &a)
     fill_model_args(c, a);
     a.n = n; a.wpb = g.wpb; a.cov_in_lds = cov_in_lds ? 1 : 0; a.nsrc = c->nsrc;
     a.rows_per_src = c->nsrc > 1 ? n / c->nsrc : 0;
-    a.stretch_a = 2.0;
+    a.stretch_a = 2.0; a.zpow = 4.0;
     c->last_wpb = g.wpb; c->last_threads = g.threads; c->last_grid = g.grid; c->last_smem = (long)g.smem;
     c->last_stage = g.stage ? 1 : 0; c->last_prepass = 0;
     return MBB_OK;
@@ -1356,6 +1356,7 @@ struct mbb_sampler_state {
     bool h_chain_tried = false;          // the landing buffer was asked for since d_chain_out was last made
     int resident_nsteps = 0;             // steps of the chain d_chain_out holds in the caller's layout (0: none)
     unsigned long long seed = 0, steps_done = 0;
+    double zpow = 4.0;                   // the exponent of z in the accept test: (columns the ensemble spans) - 1, set_state
     int rows() const { return nw * nsrc; }
 };
 
@@ -1436,6 +1437,21 @@ extern "C" int mbb_sampler_set_state(mbb_ctx *c, void *sp, const double *pos, co
         for (int i = 0; i < R; ++i)
             if (st[i] >= 2) return fail(MBB_ERR_ARG, "initial position is not a valid SED or lnprob is NaN");
     }
+    // The stretch move's Jacobian is z^(d - 1), d the dimension of the space the walkers span.  A column that is
+    // constant over an ensemble stays so exactly (stretch_q with c == s), which is how a parameter is held fixed: d
+    // counts the other columns, here, once per state.  One exponent per run: the sources must agree on which columns
+    // are constant.  (Walkers on a tilted plane -- rank deficiency that is not axis-aligned -- are not looked for.)
+    int nfree = 0;
+    for (int src = 0; src < s->nsrc; ++src) {
+        unsigned int mask = 0;
+        const double *p0 = pos + (size_t)src * s->nw * 5;
+        for (int w = 1; w < s->nw; ++w)
+            for (int k = 0; k < 5; ++k)
+                if (p0[(size_t)w * 5 + k] != p0[k]) mask |= 1u << k;
+        const int nf = __builtin_popcount(mask);
+        if (src > 0 && nf != nfree) return fail(MBB_ERR_ARG, "the sources' initial ensembles differ in the number of constant (fixed) columns");
+        nfree = nf;
+    }
     std::vector<double> rows((size_t)R * 6);
     for (int i = 0; i < R; ++i) {
         for (int k = 0; k < 5; ++k) rows[(size_t)i * 6 + k] = pos[(size_t)i * 5 + k];
@@ -1451,6 +1467,7 @@ extern "C" int mbb_sampler_set_state(mbb_ctx *c, void *sp, const double *pos, co
         s->lost = s->unchecked = false;
         s->spec_form = 0;
     }
+    s->zpow = nfree > 1 ? (double)(nfree - 1) : 0.0;
     return MBB_OK;
 }
 
@@ -1567,7 +1584,7 @@ struct SamplerLaunch {
     unsigned int *nacc;
     int *errflag;
     int s_begin, c_begin, c_count, m_count, nw, step, half, nw_src;
-    double stretch_a;
+    double stretch_a, zpow;
     unsigned long long seed;
     int persist = 0, parity = 0;         // forms 6, 7, 9: half-steps in this launch; 7, 9: its set of completion counters
     double *spec = nullptr;              // forms 6, 7, 9: the run's device state (form 6: the FlowX)
@@ -1592,7 +1609,7 @@ static int launch_sampler(mbb_ctx *c, const RunPlan &rp, const SamplerLaunch &sl
     if (rc) return rc;
     a.pos6 = sl.pos6; a.chain6 = sl.chain6; a.nacc = sl.nacc; a.errflag = sl.errflag;
     a.s_begin = sl.s_begin; a.c_begin = sl.c_begin; a.c_count = sl.c_count; a.m_count = sl.m_count; a.nw = sl.nw;
-    a.step = sl.step; a.half = sl.half; a.stretch_a = sl.stretch_a; a.seed = sl.seed; a.nw_src = sl.nw_src;
+    a.step = sl.step; a.half = sl.half; a.stretch_a = sl.stretch_a; a.zpow = sl.zpow; a.seed = sl.seed; a.nw_src = sl.nw_src;
     a.persist = sl.persist; a.spec = sl.spec; a.flow_serial = sl.serial;   // (forms 1, 2: serial 0, the null `pars`)
     const int spin = (int)((c->opt_flow_spin_log2 & 0x3f) << 24);
     if (form == 7 || form == 9) {
@@ -1768,7 +1785,7 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, 
     }
     SamplerLaunch sl;
     sl.pos6 = s->d_pos6; sl.errflag = s->d_err; sl.nw = s->rows(); sl.nw_src = s->nw;
-    sl.stretch_a = stretch_a; sl.c_count = s->nw / 2; sl.m_count = rp.p.per;
+    sl.stretch_a = stretch_a; sl.zpow = s->zpow; sl.c_count = s->nw / 2; sl.m_count = rp.p.per;
     const int rc = rp.form >= 6 ? run_one_launch(c, s, rp, sl, nsteps, store, carried ? tev : nullptr)
                                 : run_train(c, s, rp, sl, nsteps, store);
     if (rc) return rc;

@@ -59,6 +59,7 @@ struct LikeArgs {
     const double *invcov;     // [nb*nb] or nullptr
     int cov_in_lds;           // C^-1 copied to LDS (it fits) or read from global
     int nb, nunit, npart, nchunk;   // units and result slots per walker
+    int debug;                // status carries root-finder iterations << 8
     double nunorm;            // um_to_GHz / wavenorm, GHz
     double lnunorm;           // log(nunorm)
     double lowlim[5];
@@ -75,7 +76,7 @@ struct LikeArgs {
     };
     int n;
     int wpb;                  // walkers per block
-    int debug;                // status carries root-finder iterations << 8
+    double zpow;              // sampler: the exponent of z in the accept test, (columns the ensemble spans) - 1
     double *lnl;              // [n]
     int32_t *status;          // [n] or nullptr
     double *model_flux;       // [n*nb] or nullptr
@@ -231,48 +232,7 @@ __device__ __forceinline__ CLikeArgs *role_args(CLikeArgs *p)
 #define MBB_ROLE_ARGS() CLikeArgs &a = *role_args(ka)
 #define MBB_PIN(x) asm volatile("" ::"s"(x))
 
-// Philox4x32-10 (Salmon et al. 2011), counter = (row, 2 step + half), key = seed.
-__device__ __forceinline__ void philox4x32(unsigned int c[4], unsigned int k0, unsigned int k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // one 32x32->64 multiply (v_mad_u64_u32) per product instead of a high and a low
-        // half: integer multiplies are quarter rate and this sits on the latency path
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const unsigned int hi0 = (unsigned int)(p0 >> 32), lo0 = (unsigned int)p0;
-        const unsigned int hi1 = (unsigned int)(p1 >> 32), lo1 = (unsigned int)p1;
-        const unsigned int n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-// The stretch move's proposal c - z (c - s), one rounding per coordinate wherever it is formed.
-__device__ __forceinline__ double stretch_q(double cv, double sv, double zz)
-{
-    return __builtin_fma(-zz, cv - sv, cv);
-}
-
-// Philox draw of state row `row` at half-step (step, half): z of the stretch move, the
-// partner's index in the other half, the uniform of the accept test.  The key (`seed`) carries the step's number in
-// the sampler's LIFE, the counter the row and the half: what is drawn for a step does not depend on how a run was cut
-// into launches -- run_mcmc(p0, 64) twice and run_mcmc(p0, 128) make the same chain (rounds 1-5 also counted the
-// step's place in its launch, `step`: another grouping was another chain -- ADVICE r05).
-__device__ __forceinline__ void stretch_draw(int row, int step, int half, unsigned long long seed,
-                                             double stretch_a, int c_count, double &zz, int &pj, double &u3)
-{
-    (void)step;
-    unsigned int c4[4] = {(unsigned int)row, (unsigned int)half, 0u, 0u};
-    philox4x32(c4, (unsigned int)seed, (unsigned int)(seed >> 32));
-    const double u1 = fma((double)(c4[0] >> 5), 67108864.0, (double)(c4[1] >> 6)) * (1.0 / 9007199254740992.0);   // (exact)
-    const double u2 = (double)c4[2] * (1.0 / 4294967296.0);
-    u3 = ((double)c4[3] + 0.5) * (1.0 / 4294967296.0);
-    const double sq = fma(stretch_a - 1.0, u1, 1.0);
-    zz = sq * sq / stretch_a;
-    pj = (int)(u2 * (double)c_count);
-    if (pj >= c_count) pj = c_count - 1;
-}
+#include "mbb_stretch.hip.h"   // philox4x32, stretch_q, stretch_draw
 
 // Block = blockDim.x/64 waves working on `wpb` consecutive walkers.
 //   phase 1: prologue, one row of 16 lanes per walker     -> LDS
@@ -387,7 +347,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
         if ((int)blockIdx.x < a.n_ahead) {
             MBB_ROLE_ARGS();
             PIN(a.spec_cfg); PIN(a.m_count); PIN(a.persist); PIN(a.c_count); PIN(a.s_begin); PIN(a.step); PIN(a.seed);
-            PIN(a.stretch_a); PIN(a.nw); PIN(a.flow_serial); PIN(a.errflag); PIN(a.nunorm); PIN(a.lnunorm);
+            PIN(a.stretch_a); PIN(a.zpow); PIN(a.nw); PIN(a.flow_serial); PIN(a.errflag); PIN(a.nunorm); PIN(a.lnunorm);
             PIN(a.has_uplim); PIN(a.has_gprior);
             PIN(a.lowlim[0]); PIN(a.lowlim[1]); PIN(a.lowlim[2]); PIN(a.lowlim[3]); PIN(a.lowlim[4]);
             const int rpw = (a.spec_cfg >> 8) & 0xff, aw = (a.spec_cfg >> 16) & 0xff;
@@ -589,7 +549,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                         put(12, __longlong_as_double((long long)(((unsigned long long)(unsigned int)k.pad << 32) | (unsigned int)k.status)));
 #pragma unroll
                         for (int i = 0; i < 5; ++i) put(13 + i, p[i]);
-                        put(18, 4.0 * lo[2]); put(19, lo[3]); put(20, pen_u); put(21, pen_g);
+                        put(18, a.zpow * lo[2]); put(19, lo[3]); put(20, pen_u); put(21, pen_g);
                     }
                 }
                 STAMPD(10, pen_u + pen_g);
@@ -904,7 +864,7 @@ __global__ void __launch_bounds__(1024) k_lnlike(const LikeArgs a_val)
                 if (lead) {
 #pragma unroll
                     for (int i = 0; i < 5; ++i) prop[j * 8 + i] = p[i];
-                    prop[j * 8 + 5] = 4.0 * lo[2];            // (dim - 1) ln z, dim = 5
+                    prop[j * 8 + 5] = a.zpow * lo[2];         // (d - 1) ln z, d = columns the ensemble spans
                     prop[j * 8 + 6] = srow5;
                     prop[j * 8 + 7] = lo[3];                  // ln u
                 }

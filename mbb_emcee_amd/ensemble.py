@@ -151,6 +151,10 @@ class EnsembleSampler(object):
         lnprob = np.array(lnprob, dtype=np.float64)
         if np.any(np.isnan(lnprob)):
             raise ValueError("The initial lnprob was NaN.")
+        # the Jacobian of the stretch move is z^(d - 1), d the dimension of the space the walkers span: a column
+        # that is constant over the ensemble (a fixed parameter: no initial scatter) stays so exactly and does not
+        # count.  (Walkers on a tilted plane -- rank deficiency that is not axis-aligned -- are not looked for.)
+        self._zpow = max(int(np.count_nonzero(np.ptp(p, axis=0) != 0.0)) - 1, 0) * 1.0
         i0 = self._chain.shape[1]
         if storechain:
             self._chain = np.concatenate(
@@ -163,7 +167,7 @@ class EnsembleSampler(object):
         updated in place.  One likelihood launch per half-step."""
         halfk = self.k // 2
         halves = ((slice(halfk), slice(halfk, self.k), 0), (slice(halfk, self.k), slice(halfk), halfk))
-        rand, randint, a, dm1 = self._random.rand, self._random.randint, self.a, self.dim - 1.0
+        rand, randint, a, dm1 = self._random.rand, self._random.randint, self.a, self._zpow
         for it in its:
             self.iterations += 1
             for S0, S1, off in halves:

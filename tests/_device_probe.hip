@@ -1,5 +1,6 @@
-// _device_probe.hip -- test-only entry points onto the device functions of mbb_math.hip.h and
-// mbb_device.hip.h (tests/test_device_math_gpu.py, tests/test_device_math_cpu.py).  Never part of the
+// _device_probe.hip -- test-only entry points onto the device functions of mbb_math.hip.h,
+// mbb_device.hip.h and mbb_stretch.hip.h (tests/test_device_math_gpu.py, tests/test_device_math_cpu.py,
+// tests/test_sampler_statistics_gpu.py).  Never part of the
 // product library: tests/_device_probe.py compiles it, together with csrc/mbb_host_tables.cpp (the
 // builder of the polynomial tables the product uploads), into tests/device_probe/libmbb_device_probe.so with the
 // product's own device flags.
@@ -66,6 +67,7 @@ extern "C" int probe_poly(int which, const double *X, long n, double *out)
 #include <utility>
 
 #include "../mbb_emcee_amd/csrc/mbb_device.hip.h"
+#include "../mbb_emcee_amd/csrc/mbb_stretch.hip.h"
 
 using namespace mbbd;
 
@@ -450,6 +452,76 @@ extern "C" int probe_fnu(int opthin, int noalpha, const double *pars, const doub
     PCHK(hipMemcpy(out_tab, dt.p, fb, hipMemcpyDeviceToHost));
     PCHK(hipMemcpy(out_plain, dq.p, fb, hipMemcpyDeviceToHost));
     PCHK(hipMemcpy(status, dst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PROBE_OK;
+}
+// ---- the sampler's random draw (csrc/mbb_stretch.hip.h, what the sampler kernels include): one draw per lane
+namespace {
+
+__global__ void k_philox(const uint32_t *ctr, const uint32_t *key, long n, uint32_t *out)
+{
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    unsigned int c4[4] = {ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3]};
+    philox4x32(c4, key[2 * i], key[2 * i + 1]);
+    for (int k = 0; k < 4; ++k) out[4 * i + k] = c4[k];
+}
+
+__global__ void k_stretch_draw(const int32_t *row, const int32_t *half, const unsigned long long *seed, long n,
+                               double stretch_a, int c_count, double *zz, int32_t *pj, double *u3)
+{
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double z, u;
+    int j;
+    stretch_draw(row[i], 0, half[i], seed[i], stretch_a, c_count, z, j, u);
+    zz[i] = z; pj[i] = j; u3[i] = u;
+}
+
+}  // namespace
+
+// ctr[n][4], key[n][2] -> out[n][4]: Philox4x32-10 of each counter under each key
+extern "C" int probe_philox(const uint32_t *ctr, const uint32_t *key, long n, uint32_t *out)
+{
+    if (!ctr || !key || !out || n <= 0 || n > (1L << 26)) return PROBE_ERR_ARG;
+    DevBuf dc, dk, dout;
+    const size_t w = sizeof(uint32_t);
+    PCHK(dc.alloc((size_t)n * 4 * w)); PCHK(dk.alloc((size_t)n * 2 * w)); PCHK(dout.alloc((size_t)n * 4 * w));
+    PCHK(hipMemcpy(dc.p, ctr, (size_t)n * 4 * w, hipMemcpyHostToDevice));
+    PCHK(hipMemcpy(dk.p, key, (size_t)n * 2 * w, hipMemcpyHostToDevice));
+    const int threads = 256;
+    hipLaunchKernelGGL(k_philox, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, 0,
+                       dc.as<uint32_t>(), dk.as<uint32_t>(), n, dout.as<uint32_t>());
+    const int rc = done();
+    if (rc) return rc;
+    PCHK(hipMemcpy(out, dout.p, (size_t)n * 4 * w, hipMemcpyDeviceToHost));
+    return PROBE_OK;
+}
+
+// stretch_draw of state row row[i] (>= 0) in half half[i] (0 or 1) under key seed[i], scale stretch_a > 1, c_count >= 1
+// partners to draw from -> zz[n], pj[n], u3[n]
+extern "C" int probe_stretch_draw(const int32_t *row, const int32_t *half, const unsigned long long *seed, long n,
+                                  double stretch_a, int c_count, double *zz, int32_t *pj, double *u3)
+{
+    if (!row || !half || !seed || !zz || !pj || !u3 || n <= 0 || n > (1L << 26) || c_count < 1 ||
+        !(stretch_a > 1.0) || !finite_all(&stretch_a, 1))
+        return PROBE_ERR_ARG;
+    for (long i = 0; i < n; ++i)
+        if (row[i] < 0 || (half[i] != 0 && half[i] != 1)) return PROBE_ERR_DOMAIN;
+    DevBuf dr, dh, ds, dz, dj, du;
+    PCHK(dr.alloc((size_t)n * 4)); PCHK(dh.alloc((size_t)n * 4)); PCHK(ds.alloc((size_t)n * 8));
+    PCHK(dz.alloc((size_t)n * 8)); PCHK(dj.alloc((size_t)n * 4)); PCHK(du.alloc((size_t)n * 8));
+    PCHK(hipMemcpy(dr.p, row, (size_t)n * 4, hipMemcpyHostToDevice));
+    PCHK(hipMemcpy(dh.p, half, (size_t)n * 4, hipMemcpyHostToDevice));
+    PCHK(hipMemcpy(ds.p, seed, (size_t)n * 8, hipMemcpyHostToDevice));
+    const int threads = 256;
+    hipLaunchKernelGGL(k_stretch_draw, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, 0,
+                       dr.as<int32_t>(), dh.as<int32_t>(), ds.as<unsigned long long>(), n, stretch_a, c_count,
+                       dz.as<double>(), dj.as<int32_t>(), du.as<double>());
+    const int rc = done();
+    if (rc) return rc;
+    PCHK(hipMemcpy(zz, dz.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    PCHK(hipMemcpy(pj, dj.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    PCHK(hipMemcpy(u3, du.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return PROBE_OK;
 }
 #endif

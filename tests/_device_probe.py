@@ -30,7 +30,7 @@ CSRC = os.path.join(ROOT, "mbb_emcee_amd", "csrc")
 SRC_TABLES = os.path.join(CSRC, "mbb_host_tables.cpp")
 DEPS = [SRC, SRC_TABLES] + [os.path.join(CSRC, f) for f in
                             ("mbb_host_tables.h", "mbb_math.hip.h", "mbb_device.hip.h", "mbb_exp2_tab.inc",
-                             "mbb_flow_index.h")]
+                             "mbb_flow_index.h", "mbb_stretch.hip.h")]
 LIBDIR = os.path.join(HERE, "device_probe")
 SO = os.path.join(LIBDIR, "libmbb_device_probe.so")
 SO_HOST = os.path.join(LIBDIR, "libmbb_device_probe_host.so")
@@ -40,6 +40,7 @@ ERRORS = {-1: "bad arguments", -2: "an input outside the probed function's domai
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_up = C.POINTER(C.c_uint32)
 
 
 def _stale(so):
@@ -103,6 +104,8 @@ class Probe(object):
             lib.probe_rows_describe.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_int)]
             lib.probe_prologue.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_long, C.c_double, C.c_int, _dp, _ip, _ip]
             lib.probe_fnu.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_long, C.c_long, C.c_double, _dp, _dp, _ip]
+            lib.probe_philox.argtypes = [_up, _up, C.c_long, _up]
+            lib.probe_stretch_draw.argtypes = [_ip, _ip, C.POINTER(C.c_uint64), C.c_long, C.c_double, C.c_int, _dp, _ip, _dp]
 
     # ---- primitives
     def math(self, name, x, y=None, chunk=1 << 20):
@@ -176,6 +179,29 @@ class Probe(object):
         _check(self.lib.probe_fnu(int(opthin), int(noalpha), _d(p), _d(f), n, m, float(wavenorm), _d(ot), _d(op),
                                   _i(st)), "probe_fnu")
         return ot, op, st
+
+    # ---- the sampler's draw (csrc/mbb_stretch.hip.h)
+    def philox(self, ctr, key):
+        """ctr[n, 4], key[n, 2] uint32 -> Philox4x32-10 output [n, 4] uint32"""
+        ctr = np.ascontiguousarray(ctr, dtype=np.uint32).reshape(-1, 4)
+        key = np.ascontiguousarray(key, dtype=np.uint32).reshape(-1, 2)
+        assert len(ctr) == len(key)
+        out = np.empty_like(ctr)
+        _check(self.lib.probe_philox(ctr.ctypes.data_as(_up), key.ctypes.data_as(_up), len(ctr), out.ctypes.data_as(_up)),
+               "probe_philox")
+        return out
+
+    def stretch_draw(self, row, half, key, a, c_count):
+        """stretch_draw(row[i], half[i], key[i]) with scale a and c_count partners -> (zz, pj, u3)"""
+        row = np.ascontiguousarray(row, dtype=np.int32).ravel()
+        half = np.ascontiguousarray(half, dtype=np.int32).ravel()
+        key = np.ascontiguousarray(key, dtype=np.uint64).ravel()
+        n = row.size
+        assert half.size == n and key.size == n
+        zz = np.empty(n); u3 = np.empty(n); pj = np.empty(n, dtype=np.int32)
+        _check(self.lib.probe_stretch_draw(_i(row), _i(half), key.ctypes.data_as(C.POINTER(C.c_uint64)), n, float(a),
+                                           int(c_count), _d(zz), _i(pj), _d(u3)), "probe_stretch_draw")
+        return zz, pj, u3
 
 
 _loaded = {}
