@@ -69,6 +69,8 @@ constexpr int kFmEDone = 8;    // [kFmNB] half-step + 1 of the last record of bu
 constexpr int kFmPen = 16;     // [kFmNB] half-step + 1 of the record of buffer b whose two penalties are there (they follow the
                                // record: the quadrature does not wait for them, the accept test does)
 constexpr int kFmStaged = 12;  //        Q and E waves that have copied their share of the tables to LDS
+constexpr int kFmLooks = 8;    // looks an E wave takes at `QDone` in LDS while its loads of decision words are in flight: a look
+                               // and its sleep are 150-200 cycles, a round trip to global memory 0.6-0.8 us
 // (kFmProp, the hand-over record, and flowm_lds, the LDS plan: mbb_lds_plans.hip.h)
 
 // The lane number as the compiler cannot see through it: what a C wave derives from it (which item a lane
@@ -104,6 +106,26 @@ __device__ __forceinline__ bool fm_get(const double *pair, unsigned long long ta
     return (chk ^ vb) == tag;
 }
 
+// A value of one fixed lane, in every lane: v_readlane / a DPP row broadcast, no trip through LDS (a __shfl with a constant
+// lane compiles to ds_bpermute_b32, a round trip to LDS on the chain between a decision's arrival and its use).
+template <int L>
+__device__ __forceinline__ unsigned int fm_lane_lo(unsigned long long v)      // (the low word: a decision word's flag)
+{
+    return (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)v, L);
+}
+template <int L>
+__device__ __forceinline__ double fm_lane(double v)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), L), hi = __builtin_amdgcn_readlane(__double2hiint(v), L);
+    return __hiloint2double(hi, lo);
+}
+template <int N>
+__device__ __forceinline__ unsigned int fm_row_lo(unsigned long long v)       // lane N of each row of 16 -> its row (the low word)
+{
+    const int lo = (int)(unsigned int)v;
+    return (unsigned int)__builtin_amdgcn_update_dpp(lo, lo, 0x150 + N, 0xf, 0xf, false);   // row_newbcast:N
+}
+
 // What every role needs of the launch, declared inside the role after its own argument pointer (what a
 // role does not use is dead code there): band counts, the layout of the dynamic LDS, the run's state.
 #define MBB_FM_COMMON() \
@@ -119,7 +141,10 @@ __device__ __forceinline__ bool fm_get(const double *pair, unsigned long long ta
     int2 *s_band = reinterpret_cast<int2 *>(s_invcov + (a.cov_in_lds ? (size_t)nb * nb : 0)); \
     double *cscr = reinterpret_cast<double *>(s_band + nb + 1); \
     int *ctl0 = reinterpret_cast<int *>(cscr + kFmNC * 64); \
-    const size_t tab_off = ((size_t)(reinterpret_cast<unsigned char *>(ctl0 + 32 * NP) - smem_raw) + 15) & ~(size_t)15; \
+    const size_t unit_off = ((size_t)(reinterpret_cast<unsigned char *>(ctl0 + 32 * NP) - smem_raw) + 15) & ~(size_t)15; \
+    int4 *s_unit = reinterpret_cast<int4 *>(smem_raw + unit_off);    /* [nun] the units' descriptors ... */ \
+    int *s_tail = reinterpret_cast<int *>(s_unit + nun);              /* [nun][4] ... and a tail unit's four result slots */ \
+    const size_t tab_off = unit_off + (size_t)kFmUnitBytes * nun; \
     double *s_nu = reinterpret_cast<double *>(smem_raw + tab_off); \
     double *s_lnnu = s_nu + (STAGE ? a.nchunk * 64 : 0); \
     double *s_wt = s_lnnu + (STAGE ? a.nchunk * 64 : 0); \
@@ -265,6 +290,13 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
         for (int bb = t0; bb < nb; bb += nt) { s_flux[bb] = a.flux[bb]; s_ivar[bb] = a.ivar[bb]; s_band[bb] = a.band_rng[bb]; }
         if (a.cov_in_lds)
             for (int i = t0; i < nb * nb; i += nt) s_invcov[i] = a.invcov[i];
+        // (the units' descriptors, a tail unit's result slots beside it: what a Q wave needs of its second and later
+        // units comes from LDS, asked for a unit ahead, not from global memory between two units)
+        for (int u = t0; u < nun; u += nt) {
+            const int4 us = a.unit_tab[u];
+            s_unit[u] = us;
+            for (int r = 0; r < 4; ++r) s_tail[4 * u + r] = us.w == 2 ? a.tail_slot[4 * us.x + r] : -1;
+        }
         if (STAGE) {
             const int n2 = a.nchunk * 32;
             const double2 *g0 = reinterpret_cast<const double2 *>(a.nu), *g1 = reinterpret_cast<const double2 *>(a.lnnu),
@@ -306,10 +338,16 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             if (qi == 1) FM_EV(it, 14);
             const WalkerK *wkb = wk + b;
             double *part = partial + (size_t)b * npart;
-            if (wkb->status == ROW_OK) {                          // wave-uniform
-                const WalkerK k = *wkb;
+            const WalkerK k = *wkb;
+            if (k.status == ROW_OK) {                             // wave-uniform
+                int4 us = us_first;
+                int tail = tail_first;
                 for (int u = qi; u < nun; u += nq) {
-                    const int4 us = (u == qi) ? us_first : a.unit_tab[u];
+                    // (the next unit's descriptor: asked for now, looked at when this unit's samples are summed)
+                    const bool more = u + nq < nun;
+                    int4 us_next = us;
+                    int tail_next = -1;
+                    if (more) { us_next = s_unit[u + nq]; tail_next = s_tail[4 * (u + nq) + (lane >> 4)]; }
                     const int s = us.x, c0 = us.y, c1 = us.z;
                     double acc = 0.0;
                     int c = c0;
@@ -332,12 +370,14 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                         if (lane == 63) part[s] = acc;
                     } else if (us.w == 2) {
                         acc = row_sum(acc);
-                        if ((lane & 15) == 0) {
-                            const int sl = (u == qi) ? tail_first : a.tail_slot[4 * s + (lane >> 4)];
-                            if (sl >= 0) part[sl] = acc;
-                        }
+                        if ((lane & 15) == 0 && tail >= 0) part[tail] = acc;
                     } else {
                         part[s + lane] = acc;
+                    }
+                    if (more) {
+                        us = make_int4(__builtin_amdgcn_readfirstlane(us_next.x), __builtin_amdgcn_readfirstlane(us_next.y),
+                                       __builtin_amdgcn_readfirstlane(us_next.z), __builtin_amdgcn_readfirstlane(us_next.w));
+                        tail = tail_next;
                     }
                 }
             }
@@ -365,6 +405,13 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
         MBB_PIN(a.has_gprior); MBB_PIN(a.invcov); MBB_PIN(a.cov_in_lds); MBB_PIN(a.pos6); MBB_PIN(a.chain6);
         MBB_PIN(a.nacc); MBB_PIN(a.errflag);
         double *mflux = mflux_all + (size_t)(role - 1 - kFmNC) * nb;     // (the two E waves run side by side)
+        // Up to 64 bands: lane bb keeps band bb's range of partial sums, flux and inverse variance for the whole launch
+        // (they never change during one), so that behind `QDone` only the partial sums are fetched.
+        const bool band_regs = nb <= 64;                                 // wave-uniform
+        int2 rng_r = make_int2(0, 0);
+        double flux_r = 0.0, ivar_r = 0.0;
+        if (band_regs && lane < nb) { rng_r = s_band[lane]; flux_r = s_flux[lane]; ivar_r = s_ivar[lane]; }
+        asm volatile("" : "+v"(rng_r.x), "+v"(rng_r.y), "+v"(flux_r), "+v"(ivar_r));
         for (int it = role - 1 - kFmNC; it < niter; it += 2)
         MBB_FM_PAIRS_LOOP
         for (int vp = 0; vp < NP; ++vp) {
@@ -398,20 +445,29 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             int st = ROW_SKIP;
             double cbb = 0.0, pen_u = 0.0, pen_g = 0.0, lnz4 = 0.0, lnu = 0.0, acc = 0.0;
             double q[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, old5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            auto sums = [&]() {
-                lds_wait(ctl + kFmPen + b, it + 1);                    // (C posts the penalties behind the record)
+            // The record -- status, band scale, proposal, the row as it is, ln z, ln u, the two penalties -- is read as soon
+            // as C has posted the penalties (they follow the record), as a rule well before the quadrature is through.
+            bool have_rec = false;
+            auto record = [&]() {
                 st = wkb->status;
                 cbb = wkb->cq; pen_u = pr[7]; pen_g = pr[8];
 #pragma unroll
                 for (int i = 0; i < 5; ++i) { q[i] = pr[i]; old5[i] = pr[9 + i]; }
                 lnz4 = pr[5]; lnu = pr[6];
+                have_rec = true;
+            };
+            auto sums = [&]() {
+                if (!have_rec) {
+                    lds_wait(ctl + kFmPen + b, it + 1);                // (C posts the penalties behind the record)
+                    record();
+                }
                 if (st == ROW_OK) {
                     const double *pj2 = partial + (size_t)b * npart;
-                    auto band = [&](const int bb) {                    // band flux, fixed order (k_lnlike, phase 3)
+                    // band flux, fixed order (k_lnlike, phase 3)
+                    auto band = [&](const int bb, const int2 rng, const double flux, const double ivar) {
                         // (the product and the difference are separate roundings, as there: the library is
                         // built with -ffp-contract=off and every fused multiply-add is an explicit fma())
                         double sum = 0.0;
-                        const int2 rng = s_band[bb];
                         for (int sg = rng.x; sg < rng.y; sg += 4) {
                             const int l = rng.y - 1;
                             const double q0 = pj2[sg], q1 = pj2[min(sg + 1, l)], q2 = pj2[min(sg + 2, l)], q3 = pj2[min(sg + 3, l)];
@@ -421,11 +477,15 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                             if (sg + 3 < rng.y) sum += q3;
                         }
                         sum *= cbb;
-                        const double d = s_flux[bb] - sum;             // likelihood.py:821
+                        const double d = flux - sum;                   // likelihood.py:821
                         if (a.invcov) mflux[bb] = d;
-                        else acc = fma(d * d, s_ivar[bb], acc);        // :825
+                        else acc = fma(d * d, ivar, acc);              // :825
                     };
-                    for (int bb = lane; bb < nb; bb += 64) band(bb);
+                    if (band_regs) {
+                        if (lane < nb) band(lane, rng_r, flux_r, ivar_r);
+                    } else {
+                        for (int bb = lane; bb < nb; bb += 64) band(bb, s_band[bb], s_flux[bb], s_ivar[bb]);
+                    }
                     if (a.invcov) {                                    // :823
                         MBB_FM_ORDER();
                         for (int i = lane; i < nb; i += 64) {
@@ -450,23 +510,39 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             bool ok = !(watch || lane == 21), have_sums = false;
             long long spins = 0;
             for (;;) {
-                // (asked for ...)
-                double lv = 0.0;
-                unsigned long long lchk = 0, wv = 0;
+                // (asked for ...  No initial values: merging a loaded value with one made the compiler wait for lane 21's
+                // load right where it is issued, a round trip before the decision word was even asked for.  Each is
+                // looked at only by the lanes that asked.)
+                double lv;
+                unsigned long long lchk, wv;
                 const bool ask_l = lane == 21 && !ok, ask_w = watch && !ok;
                 if (ask_l) {
                     lv = ld_dev(lnp_p);
                     lchk = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(lnp_p) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 if (ask_w) wv = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // (... the sums meanwhile, if Q is through ...)
-                if (!have_sums && __hip_atomic_load(ctl + kFmQDone + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= q_need) {
-                    MBB_FM_ORDER();
-                    FM_EV(it, 4);
-                    sums();
-                    have_sums = true;
+                // (... the record meanwhile, once its penalties are posted, and the sums, once Q is through: looked for while
+                // the words are on their way -- kFmLooks looks a sleep apart, about one round trip to global memory -- and
+                // not once per round trip; bounded, the words are looked at afterwards either way ...)
+#pragma nounroll
+                for (int look = 0; !have_sums; ++look) {
+                    if (!have_rec && __hip_atomic_load(ctl + kFmPen + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= it + 1) {
+                        MBB_FM_ORDER();
+                        record();
+                    }
+                    if (__hip_atomic_load(ctl + kFmQDone + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= q_need) {
+                        MBB_FM_ORDER();
+                        FM_EV(it, 4);
+                        sums();
+                        have_sums = true;
+                        break;
+                    }
+                    if (look >= kFmLooks) break;
+                    __builtin_amdgcn_s_sleep(1);
                 }
                 // (... and looked at)
+                if (ask_l) asm volatile("" : "+v"(lv), "+v"(lchk));       // (not before the code above: see "asked for")
+                if (ask_w) asm volatile("" : "+v"(wv));
                 if (ask_l) { lnp = lv; ok = (lchk ^ (unsigned long long)__double_as_longlong(lv)) == tag_s; }
                 if (ask_w) { pv = wv; ok = lane == 22 ? dec_ok(pv, need_p) : pv >= need_g; }
 #ifdef MBB_STAMPS
@@ -481,9 +557,9 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 }
                 __builtin_amdgcn_s_sleep(1);
             }
-            const int flag = (need_p > 0 && (__shfl(pv, 22) & 1ull)) ? 1 : 0;
+            const int flag = (need_p > 0 && (fm_lane_lo<22>(pv) & 1u)) ? 1 : 0;
             const bool mine = flag == cand;                       // this workgroup's candidate is the chain's proposal
-            const double lnp_cur = __shfl(lnp, 21);
+            const double lnp_cur = fm_lane<21>(lnp);
             FM_TD(0, lnp_cur);
             FM_EV(it, 5);
             FM_EVV(it, 7, prow);
@@ -575,7 +651,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
         for (int vp = 0; vp < NP; ++vp) {
             MBB_FM_PAIR(vp);
             const int lane = fm_loop_lane(lane_w);
-            const int vrow = lane >> 4, l16 = lane & 15, base = lane & 48;
+            const int vrow = lane >> 4, l16 = lane & 15;
             const int hj = j & 1;
             const int sb = hj ? a.c_count : 0, ob = hj ? 0 : a.c_count;    // the half that moves in j / the other
             const int tn = a.step + (j >> 1);
@@ -670,7 +746,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                                  ((unsigned long long)(ob + qp) << 30) | ((unsigned long long)(c1 ? 1 : 0) << 40) | ((unsigned long long)(m_s > 0 ? 1 : 0) << 41));
                 MBB_FM_ORDER();
                 // (a decision word that was not waited for reads as candidate 0)
-                const int cr = (int)(__shfl(dv, 0) & 1ull), cp = (int)(__shfl(dv, 1) & 1ull);
+                const int cr = (int)(fm_lane_lo<0>(dv) & 1u), cp = (int)(fm_lane_lo<1>(dv) & 1u);
                 // this row of lanes' assumption about the two moves of half-step j - 2
                 const bool ar_v = has && (vrow & 1), ap_v = has && c1 && (vrow & 2);
                 snv_off = ar_v ? 5 + 5 * cr : 0;
@@ -718,7 +794,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             FM_TD(2, pen_u + pen_g + k.cbb);
             FM_EV(j, 1);
             if (__builtin_amdgcn_ballot_w64(watch2 && !dec_ok(v2, need2)) != 0) v2 = spin(w2, need2, watch2);
-            const bool ar = m_s > 0 && (__shfl(v2, base + 0) & 1ull), ap = m_s > 0 && c1 && (__shfl(v2, base + 1) & 1ull);
+            const bool ar = m_s > 0 && (fm_row_lo<0>(v2) & 1u), ap = m_s > 0 && c1 && (fm_row_lo<1>(v2) & 1u);
             const int vsel = (ar ? 1 : 0) | (ap ? 2 : 0);
             FM_TD(3, v2);
             FM_EV(j, 2);

@@ -1622,7 +1622,7 @@ static int launch_sampler(mbb_ctx *c, const RunPlan &rp, const SamplerLaunch &sl
         const int wgs = fa ? (n + W - 1) / W : 2 * n;
         const int thr = fa ? 1024 : (std::min(g.threads / 64, 11) + 5) * 64;
         const size_t dyn_limit = dynamic_lds_limit(c), table_bytes = (size_t)c->nchunk * 64 * 3 * sizeof(double);
-        auto lds_of = [&](bool cov) { return fa ? flowa_lds(c->nb, c->npart, cov, W) : flowm_lds(c->nb, c->npart, cov); };
+        auto lds_of = [&](bool cov) { return fa ? flowa_lds(c->nb, c->npart, cov, W) : flowm_lds(c->nb, c->npart, cov, c->nunit); };
         a.wpb = W;
         a.cov_in_lds = (c->has_cov && lds_of(true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
         const size_t sm = lds_of(a.cov_in_lds != 0);

@@ -11,12 +11,15 @@
 constexpr int kFmProp = 16;    // doubles per hand-over record besides WalkerK: proposal 0..4, (dim-1) ln z,
                                // ln u, the two penalties, the walker's row as it is (9..13)
 // dynamic LDS of a k_flowm launch besides the staged passband tables (bytes)
-// (np = pairs of walkers a workgroup serves: the hand-over records and their control words are per pair)
-__host__ __device__ constexpr size_t flowm_lds(size_t nb, size_t npart, bool cov_in_lds, size_t np = 1)
+// (np = pairs of walkers a workgroup serves: the hand-over records and their control words are per pair;
+// nunit: the quadrature's units, whose descriptors -- {slot, first chunk, end chunk, kind} and the four result
+// slots of a tail unit's rows, 32 bytes a unit -- the Q waves read from LDS, not from global memory, inside a pass)
+constexpr int kFmUnitBytes = 32;
+__host__ __device__ constexpr size_t flowm_lds(size_t nb, size_t npart, bool cov_in_lds, size_t nunit, size_t np = 1)
 {
     return np * kFmNB * sizeof(mbbd::WalkerK) +
            8 * (np * kFmNB * npart + 2 * nb + np * kFmNB * kFmProp + 2 * nb + (cov_in_lds ? nb * nb : 0)) +
-           8 * (nb + 2) + 8 * (kFmNC * 64) + 128 * np + 32;
+           8 * (nb + 2) + 8 * (kFmNC * 64) + 128 * np + 32 + kFmUnitBytes * nunit;
 }
 
 // ---- k_flowa, sampler form 9 (mbb_flowa.hip.h)
