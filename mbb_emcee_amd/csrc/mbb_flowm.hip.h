@@ -71,6 +71,13 @@ constexpr int kFmPen = 16;     // [kFmNB] half-step + 1 of the record of buffer 
 constexpr int kFmStaged = 12;  //        Q and E waves that have copied their share of the tables to LDS
 constexpr int kFmLooks = 8;    // looks an E wave takes at `QDone` in LDS while its loads of decision words are in flight: a look
                                // and its sleep are 150-200 cycles, a round trip to global memory 0.6-0.8 us
+// Priorities of the C and E waves (s_setprio; the Q waves stay at 0).  The three C waves and E0 share one SIMD, E1 shares
+// another with three Q waves, and a SIMD issues for its highest priority first, its oldest wave among equals: a wave that
+// polls at the constructor's priority takes every issue slot its poll loop can use from the wave whose chain the
+// half-step is waiting for.  So a C or E wave is at kFmPrioWork while it works on the chain -- constructor, selection and
+// hand-over, band sums, accept test, publish -- and at kFmPrioWait while it polls for other workgroups' words: still ahead
+// of the quadrature, behind every wave that has work (profiles/r11/form7.txt: -3.7 % per step).
+constexpr int kFmPrioWork = 3, kFmPrioWait = 1;
 // (kFmProp, the hand-over record, and flowm_lds, the LDS plan: mbb_lds_plans.hip.h)
 
 // The lane number as the compiler cannot see through it: what a C wave derives from it (which item a lane
@@ -312,7 +319,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
         lds_wait(ctl0 + kFmStaged, ns);
     }
     // (the chains of C and E are what a half-step waits for: ahead of the Q wave they share a SIMD with)
-    if (role != 0) __builtin_amdgcn_s_setprio(3);
+    if (role != 0) __builtin_amdgcn_s_setprio(kFmPrioWork);
     // =========================== Q: the passband quadrature ====================================
     if (role == 0) {
         MBB_ROLE_ARGS();
@@ -457,6 +464,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 have_rec = true;
             };
             auto sums = [&]() {
+                __builtin_amdgcn_s_setprio(kFmPrioWork);
                 if (!have_rec) {
                     lds_wait(ctl + kFmPen + b, it + 1);                // (C posts the penalties behind the record)
                     record();
@@ -509,6 +517,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             double lnp = 0.0;
             bool ok = !(watch || lane == 21), have_sums = false;
             long long spins = 0;
+            __builtin_amdgcn_s_setprio(kFmPrioWait);              // (polling; sums() and what follows the loop: work)
             for (;;) {
                 // (asked for ...  No initial values: merging a loaded value with one made the compiler wait for lane 21's
                 // load right where it is issued, a round trip before the decision word was even asked for.  Each is
@@ -557,6 +566,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 }
                 __builtin_amdgcn_s_sleep(1);
             }
+            __builtin_amdgcn_s_setprio(kFmPrioWork);
             const int flag = (need_p > 0 && (fm_lane_lo<22>(pv) & 1u)) ? 1 : 0;
             const bool mine = flag == cand;                       // this workgroup's candidate is the chain's proposal
             const double lnp_cur = fm_lane<21>(lnp);
@@ -722,6 +732,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                     kind = (has && c1) ? 2 : 0;
                 }
                 FM_EV(j, 13);
+                __builtin_amdgcn_s_setprio(kFmPrioWait);          // (polling, until everything is there)
                 bool ok = kind == 0;
                 double v = 0.0;
                 unsigned long long dv = 0;
@@ -738,6 +749,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                     }
                     __builtin_amdgcn_s_sleep(1);
                 }
+                __builtin_amdgcn_s_setprio(kFmPrioWork);
                 if (slot >= 0) scr[slot] = v;
                 FM_TD(0, v);
                 FM_EV(j, 0);
@@ -793,7 +805,11 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
 #endif
             FM_TD(2, pen_u + pen_g + k.cbb);
             FM_EV(j, 1);
-            if (__builtin_amdgcn_ballot_w64(watch2 && !dec_ok(v2, need2)) != 0) v2 = spin(w2, need2, watch2);
+            if (__builtin_amdgcn_ballot_w64(watch2 && !dec_ok(v2, need2)) != 0) {
+                __builtin_amdgcn_s_setprio(kFmPrioWait);
+                v2 = spin(w2, need2, watch2);
+                __builtin_amdgcn_s_setprio(kFmPrioWork);
+            }
             const bool ar = m_s > 0 && (fm_row_lo<0>(v2) & 1u), ap = m_s > 0 && c1 && (fm_row_lo<1>(v2) & 1u);
             const int vsel = (ar ? 1 : 0) | (ap ? 2 : 0);
             FM_TD(3, v2);
