@@ -71,13 +71,19 @@ constexpr int kFmPen = 16;     // [kFmNB] half-step + 1 of the record of buffer 
 constexpr int kFmStaged = 12;  //        Q and E waves that have copied their share of the tables to LDS
 constexpr int kFmLooks = 8;    // looks an E wave takes at `QDone` in LDS while its loads of decision words are in flight: a look
                                // and its sleep are 150-200 cycles, a round trip to global memory 0.6-0.8 us
-// Priorities of the C and E waves (s_setprio; the Q waves stay at 0).  The three C waves and E0 share one SIMD, E1 shares
-// another with three Q waves, and a SIMD issues for its highest priority first, its oldest wave among equals: a wave that
-// polls at the constructor's priority takes every issue slot its poll loop can use from the wave whose chain the
-// half-step is waiting for.  So a C or E wave is at kFmPrioWork while it works on the chain -- constructor, selection and
-// hand-over, band sums, accept test, publish -- and at kFmPrioWait while it polls for other workgroups' words: still ahead
-// of the quadrature, behind every wave that has work (profiles/r11/form7.txt: -3.7 % per step).
-constexpr int kFmPrioWork = 3, kFmPrioWait = 1;
+// Priorities of the C and E waves (s_setprio; the Q waves stay at 0): by how soon the chain needs what a wave is doing,
+// not by its role.  A SIMD issues for its highest priority first and for its oldest wave among equals, so whatever runs at
+// the level of the chain takes its issue slots from the wave the half-step is waiting for.
+//   kFmPrioChain  E from the band sums to the stores of the decision and the row's six elements: the whole compute part of
+//                 the one-half-step chain, a few hundred cycles that nothing on the SIMD should delay
+//   kFmPrioCtor   C from the arrival of the words of j - 3 to the hand-over of the record (constructor, W2 look,
+//                 selection, hand-over, the proposal's stores): the three-half-step chain, thousands of cycles
+//   kFmPrioWait   every poll for another workgroup's words (round 11), and work with a half-step of slack or more: E's
+//                 chain entry, counters and write-back behind the row's stores, C's walls and priors behind the hand-over
+//                 (their first reader is the accept test a half-step later) and the draws of its next proposal.  Still
+//                 ahead of the quadrature a wave shares its SIMD with.
+// (profiles/r12/form7.txt: each level, and the placement of the roles below, A/B'd one by one.)
+constexpr int kFmPrioChain = 3, kFmPrioCtor = 2, kFmPrioWait = 1;
 // (kFmProp, the hand-over record, and flowm_lds, the LDS plan: mbb_lds_plans.hip.h)
 
 // The lane number as the compiler cannot see through it: what a C wave derives from it (which item a lane
@@ -217,15 +223,18 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
     __shared__ __align__(16) double s_pc[OPTHIN ? 2 : kPolyCDoubles];
     const int tid = threadIdx.x, lane = tid & 63, wave = MBB_WAVE_ID(tid);
     const int nwave = blockDim.x >> 6, nq = nwave - kFmNC - 2;
-    // Which wave does what.  The constructor is one long dependent chain and runs fastest on a SIMD it
-    // does not share with the quadrature's bursts: waves 3, 7, 11 and 15 (one SIMD: a workgroup's waves
-    // go round the four in turn) are the three C waves and E0, wave 14 is E1, the eleven others are Q
-    // waves, numbered in order.  (Fewer than 16 waves: the last five.)  Three C waves, a half-step in
-    // three each, and two E waves, one per half of the ensemble: a proposal takes ~1.5 half-steps of a
-    // wave's time, an E pass ~0.4, and one that had to queue behind the wave's previous one was what a
-    // half-step waited for most often (tools/probe_chain_flowm.py).
+    // Which wave does what.  Waves 3, 7, 11 and 15 share one SIMD (a workgroup's waves go round the four
+    // in turn): C0, C1, E0 and E1, the service SIMD, with no quadrature wave on it.  C2 is wave 14, the
+    // fourth wave of the SIMD whose three Q waves carry the fewest chunks (8 of the bench's 36 against 14
+    // and 14): a working C wave outranks the quadrature there, a polling or idle one leaves it alone, and
+    // only two constructors, not three, contend for one SIMD's issue slots (round 4 had every placement
+    // of a C wave among Q waves slower -- with all of them at one priority; profiles/r12/form7.txt).  The
+    // eleven others are Q waves, numbered in order.  (Fewer than 16 waves: the last five.)  Three C
+    // waves, a half-step in three each, and two E waves, one per half of the ensemble: a proposal takes
+    // ~1.5 half-steps of a wave's time, an E pass ~0.4, and one that had to queue behind the wave's
+    // previous one was what a half-step waited for most often (tools/probe_chain_flowm.py).
     const bool spread = nwave == 16;
-    const int role = spread ? ((wave & 3) == 3 ? 1 + (wave >> 2) : (wave == 14 ? 2 + kFmNC : 0))
+    const int role = spread ? (wave == 3 ? 1 : wave == 7 ? 2 : wave == 14 ? 3 : wave == 11 ? 1 + kFmNC : wave == 15 ? 2 + kFmNC : 0)
                             : (wave < nq ? 0 : 1 + wave - nq);                    // 0 Q, 1..3 C, 4 E0, 5 E1
     const int qi = spread ? wave - (wave >> 2) : wave;                           // Q wave number (14 is not one)
     // ---- set-up, once per launch ---------------------------------------------------------------
@@ -318,8 +327,9 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
         if (lane == 0) __hip_atomic_fetch_add(ctl0 + kFmStaged, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         lds_wait(ctl0 + kFmStaged, ns);
     }
-    // (the chains of C and E are what a half-step waits for: ahead of the Q wave they share a SIMD with)
-    if (role != 0) __builtin_amdgcn_s_setprio(kFmPrioWork);
+    // (the chains of C and E are what a half-step waits for: ahead of the Q waves they share a SIMD with)
+    if (role > kFmNC) __builtin_amdgcn_s_setprio(kFmPrioChain);
+    else if (role != 0) __builtin_amdgcn_s_setprio(kFmPrioCtor);
     // =========================== Q: the passband quadrature ====================================
     if (role == 0) {
         MBB_ROLE_ARGS();
@@ -464,7 +474,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 have_rec = true;
             };
             auto sums = [&]() {
-                __builtin_amdgcn_s_setprio(kFmPrioWork);
+                __builtin_amdgcn_s_setprio(kFmPrioChain);
                 if (!have_rec) {
                     lds_wait(ctl + kFmPen + b, it + 1);                // (C posts the penalties behind the record)
                     record();
@@ -566,7 +576,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 }
                 __builtin_amdgcn_s_sleep(1);
             }
-            __builtin_amdgcn_s_setprio(kFmPrioWork);
+            __builtin_amdgcn_s_setprio(kFmPrioChain);
             const int flag = (need_p > 0 && (fm_lane_lo<22>(pv) & 1u)) ? 1 : 0;
             const bool mine = flag == cand;                       // this workgroup's candidate is the chain's proposal
             const double lnp_cur = fm_lane<21>(lnp);
@@ -610,16 +620,18 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                     double ve = lnp_new;
 #pragma unroll
                     for (int i = 0; i < 5; ++i) ve = ((lane & 7) == i) ? (accept ? q[i] : old5[i]) : ve;
-                    if (lane < 6) {
+                    if (lane < 6)
                         fm_put(fv.row + ((size_t)(m_new % kFmSlots) * a.nw + row) * kFmWords + 2 * lane, ve,
                                serial32 | (unsigned long long)(it + 1));
-                        // the row's last move of the launch: back into the sampler's rows (no kernel after this one)
-                        if (it + 2 >= niter) a.pos6[(size_t)row * 6 + lane] = ve;
-                    }
+                    // (the chain has what it waits for: everything from here on has a half-step of slack or more)
+                    __builtin_amdgcn_s_setprio(kFmPrioWait);
+                    // the row's last move of the launch: back into the sampler's rows (no kernel after this one)
+                    if (lane < 6) { if (it + 2 >= niter) a.pos6[(size_t)row * 6 + lane] = ve; }
                     else if (lane >= 8 && lane < 14 && a.chain6)
                         a.chain6[((size_t)it * a.n + w) * 6 + (lane - 8)] = ve;
                     if (lane == 0 && accept) atomicAdd(a.nacc + (size_t)L_half * a.n + w, 1u);
                 }
+                __builtin_amdgcn_s_setprio(kFmPrioWait);          // (the sibling whose candidate it was not: the same)
                 if (lane == 0) __hip_atomic_fetch_add(done_set + (it & (kFmRing - 1)) * 16, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             FM_T(3);
@@ -749,7 +761,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                     }
                     __builtin_amdgcn_s_sleep(1);
                 }
-                __builtin_amdgcn_s_setprio(kFmPrioWork);
+                __builtin_amdgcn_s_setprio(kFmPrioCtor);
                 if (slot >= 0) scr[slot] = v;
                 FM_TD(0, v);
                 FM_EV(j, 0);
@@ -808,7 +820,7 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             if (__builtin_amdgcn_ballot_w64(watch2 && !dec_ok(v2, need2)) != 0) {
                 __builtin_amdgcn_s_setprio(kFmPrioWait);
                 v2 = spin(w2, need2, watch2);
-                __builtin_amdgcn_s_setprio(kFmPrioWork);
+                __builtin_amdgcn_s_setprio(kFmPrioCtor);
             }
             const bool ar = m_s > 0 && (fm_row_lo<0>(v2) & 1u), ap = m_s > 0 && c1 && (fm_row_lo<1>(v2) & 1u);
             const int vsel = (ar ? 1 : 0) | (ap ? 2 : 0);
@@ -837,7 +849,10 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
 #pragma unroll
                 for (int i = 0; i < 5; ++i) fm_put(rec + 2 * i, p[i], tag);
             }
-            // the five parameters' walls and priors, behind the hand-over: their first reader is the accept test
+            // the five parameters' walls and priors, behind the hand-over: their first reader is the accept test, a half-step
+            // later (E waits for `Pen` only where the sums start) -- off the constructor's level, like the draws of this wave's
+            // next proposal, until the words that one waits for are there
+            __builtin_amdgcn_s_setprio(kFmPrioWait);
 #include "mbb_walker_penalties.inc"
             if (vrow == vsel && l16 == 0) {
                 double *pr = prop + bj * kFmProp;

@@ -27,9 +27,12 @@ lib.mbb_stamps(ctx.h, st.ctypes.data_as(C.c_void_p), nb * 4)
 t = st.reshape(-1)[: nb * 16 * 8].reshape(nb, 16, 8).astype(np.float64) / (2 * NS)    # cycles per half-step
 nq = nwave - 5
 spread = nwave == 16
+# (the spread placement of a 16-wave workgroup: MBB_STAMPS_OLD_PLACEMENT=1 for libraries of before round 12, whose C waves
+# were 3, 7, 11 and whose E waves 15, 14)
+OLD = os.environ.get("MBB_STAMPS_OLD_PLACEMENT") == "1"
 QW = [wv for wv in range(nwave) if (wv & 3) != 3 and wv != 14] if spread else list(range(nq))
-CW = (3, 7, 11) if spread else (nq, nq + 1, nq + 2)
-EWS = (15, 14) if spread else (nq + 3, nq + 4)
+CW = ((3, 7, 11) if OLD else (3, 7, 14)) if spread else (nq, nq + 1, nq + 2)
+EWS = ((15, 14) if OLD else (11, 15)) if spread else (nq + 3, nq + 4)
 EW = EWS[0]
 raw = st.reshape(-1)[: nb * 16 * 8].reshape(nb, 16, 8).astype(np.float64)
 med = lambda v: [int(x) for x in np.median(v, axis=0)]
