@@ -241,6 +241,12 @@ class ChainSummary(object):
             raise ValueError("{} was not asked for when the summary was made (derived=)".format(name))
 
     def _cen(self, slot, percentile, lowlim, uplim):
+        """[mean, upper - mean, mean - lower] of column `slot`.  A multi-source summary is one result: the statuses of
+        all its sources are combined first, so it raises -- nothing surviving the clipping, or the exception of a
+        failing SED row as ``postprocess`` raises it for the same chain -- when ANY source's column met that inside
+        the burn / thin window, also for the sources whose own column is fine (``status`` says which those are, and
+        ``mean`` / ``percentiles`` hold their numbers).  Rows outside the window never count; a NaN parameter gives NaN
+        and does not raise."""
         qs = list(_pval(percentile))
         raw, idx = self._lookup(slot, qs, lowlim, uplim)
         if np.any(raw.status[:, slot] & _native.SUM_EMPTY):
@@ -252,7 +258,7 @@ class ChainSummary(object):
 
     @staticmethod
     def _row_status(raw, slot):
-        """The SED kernels' row status codes a derived column met, as raise_for_status takes them."""
+        """The SED kernels' row status codes a derived column met in any source, as raise_for_status takes them."""
         bits = int(np.bitwise_or.reduce(raw.status[:, slot])) >> _native.SUM_ROW_SHIFT
         return np.array([s for s in range(8) if bits & (1 << s)] or [0], dtype=np.int32)
 

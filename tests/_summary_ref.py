@@ -48,3 +48,176 @@ def ulps_off(got, want, lo, hi):
     """|got - want| in units of the spacing of the larger bracketing value (the rounding of the interpolation)."""
     scale = np.spacing(np.maximum(np.maximum(np.abs(lo), np.abs(hi)), np.finfo(np.float64).tiny))
     return np.abs(np.asarray(got) - np.asarray(want)) / scale
+
+
+# ---- derived columns per entry (tests/test_summary_derived_gpu.py; the builders are held by tests/test_summary_cpu.py) ----
+# The suite's usual box, valid for all four models: T, beta, lambda0, alpha, fnorm.
+BOX_LO = np.array([10.0, 1.0, 100.0, 1.5, 5.0])
+BOX_HI = np.array([60.0, 2.5, 900.0, 4.5, 90.0])
+
+
+def chunk_rows(root):
+    """kSumChunkRows as csrc/mbb_hip.hip states it: the chain rows summary_fill_derived fills per iteration."""
+    import os
+    import re
+    text = open(os.path.join(root, "mbb_emcee_amd", "csrc", "mbb_hip.hip")).read()
+    m = re.search(r"constexpr\s+int\s+kSumChunkRows\s*=\s*([^;]+);", text)
+    assert m, "kSumChunkRows is not where the derived-column tests read it"
+    expr = m.group(1).strip()
+    s = re.fullmatch(r"(\d+)\s*<<\s*(\d+)", expr)
+    value = int(s.group(1)) << int(s.group(2)) if s else int(expr)
+    return value
+
+
+def seam_shapes(chunk):
+    """The shapes the seam tests use, from the chunk length: (single-cell chain, its steps at the seam), (short last
+    chunk chain, its steps), the two window shapes (nsrc, nw, nsteps, burn, thin) and the resident chain's."""
+    nsteps = chunk // 64 + 4                                     # 64 sources of one walker: cell `chunk` is source 63
+    seam = chunk - 63 * nsteps
+    return {"cells": ((64, 1, nsteps), (0, 1, seam - 1, seam, seam + 1, nsteps - 1)),
+            "tail": ((1, 1, chunk + 1), (0, chunk - 1, chunk)),
+            "windows": ((3, 50, -(-(chunk + 256) // 150), 7, 3), (1, 64, chunk // 64 + 1, 0, 1)),
+            "resident": (1, 64, chunk // 64 + 4)}
+
+
+def cell_of(flat, nw, nsteps):
+    """(source, walker, step) of flat chain row `flat`."""
+    return (flat // (nw * nsteps), (flat // nsteps) % nw, flat % nsteps)
+
+
+def box_rows(rng, n, centre=None, width=1.0):
+    """n distinct parameter rows from the box (a fraction `width` of it about `centre`, kept inside)."""
+    lo, hi = BOX_LO, BOX_HI
+    if centre is not None:
+        half = 0.5 * width * (BOX_HI - BOX_LO)
+        lo, hi = np.maximum(BOX_LO, centre - half), np.minimum(BOX_HI, centre + half)
+    rows = lo + (hi - lo) * rng.rand(n, 5)
+    assert len(np.unique(rows, axis=0)) == n and all(len(np.unique(rows[:, k])) == n for k in range(5))
+    return rows
+
+
+def distinct_chain(nsrc, nw, nsteps, seed):
+    """A chain whose every row, and every value of every column, is distinct: an off-by-one shows in every cell."""
+    rng = np.random.RandomState(seed)
+    chain = box_rows(rng, nsrc * nw * nsteps).reshape(nsrc, nw, nsteps, 5)
+    return chain, -0.5 * rng.chisquare(5, (nsrc, nw, nsteps))
+
+
+SOURCE_CENTRES = np.array([[12.0, 1.2, 250.0, 2.0, 60.0], [25.0, 1.8, 500.0, 3.0, 30.0], [45.0, 2.3, 750.0, 4.0, 10.0]])
+SENT_T, SENT_F = (62.0, 0.25), (2000.0, 0.125)          # in-window sentinel k: T 62 + k / 4, fnorm 2000 (1 + k / 8)
+OUT_T, OUT_F = (72.0, 0.25), (2.0e5, 0.125)             # out-of-window neighbour k: more extreme still
+
+
+def sentinel_chain(nsrc, nw, nsteps, burn, thin, chunk, seed):
+    """A chain of `nsrc` sources about their own centres with 40 % rejected-move repeats (as test_summary_gpu's
+    _random_chain), then sentinel cells.  Returns chain, lnprob, inside {cell: k}, outside {cell: k}.
+
+    inside: the flat cells 0, chunk - 1, chunk and the last one where the window keeps them, and the first and last
+    kept step of the first and last walker of every source -- the source's centre row with T and fnorm beyond the
+    rest of the column, by a different amount at each place, so that each source's smallest peak wavelength and largest L_IR and dust mass are
+    sentinels.  outside: for thin > 1 the steps burn - 1, burn + 1 and the last step where it is not kept, of the same
+    walkers, and those of the four flat cells that the window drops -- more extreme still."""
+    rng = np.random.RandomState(seed)
+    R = nsrc * nw
+    centres = np.repeat(SOURCE_CENTRES[np.arange(nsrc) % len(SOURCE_CENTRES)], nw, axis=0)      # [R, 5]
+    half = 0.125 * (BOX_HI - BOX_LO)
+    lo, hi = np.maximum(BOX_LO, centres - half), np.minimum(BOX_HI, centres + half)
+    chain = np.empty((R, nsteps, 5))
+    lnp = np.empty((R, nsteps))
+    chain[:, 0], lnp[:, 0] = lo + (hi - lo) * rng.rand(R, 5), -0.5 * rng.chisquare(5, R)
+    for t in range(1, nsteps):
+        move = rng.rand(R) < 0.4
+        chain[:, t] = np.where(move[:, None], lo + (hi - lo) * rng.rand(R, 5), chain[:, t - 1])
+        lnp[:, t] = np.where(move, -0.5 * rng.chisquare(5, R), lnp[:, t - 1])
+    chain, lnp = chain.reshape(nsrc, nw, nsteps, 5), lnp.reshape(nsrc, nw, nsteps)
+    kept = lambda t: t >= burn and (t - burn) % thin == 0
+    last_kept = burn + ((nsteps - 1 - burn) // thin) * thin
+    inside, outside = {}, {}
+    for flat in (0, chunk - 1, chunk, nsrc * nw * nsteps - 1):
+        if flat >= nsrc * nw * nsteps:
+            continue
+        cell = cell_of(flat, nw, nsteps)
+        (inside if kept(cell[2]) else outside).setdefault(cell, None)
+    for s in range(nsrc):
+        for w in sorted({0, nw - 1}):
+            for t in (burn, last_kept):
+                inside.setdefault((s, w, t), None)
+            if thin > 1:
+                for t in (burn - 1, burn + 1, nsteps - 1):
+                    if 0 <= t < nsteps and not kept(t):
+                        outside.setdefault((s, w, t), None)
+    for k, cell in enumerate(sorted(inside)):
+        inside[cell] = k
+        chain[cell] = SOURCE_CENTRES[cell[0] % len(SOURCE_CENTRES)]
+        chain[cell][0], chain[cell][4] = SENT_T[0] + SENT_T[1] * k, SENT_F[0] * (1.0 + SENT_F[1] * k)
+    for k, cell in enumerate(sorted(outside)):
+        outside[cell] = k
+        chain[cell] = SOURCE_CENTRES[cell[0] % len(SOURCE_CENTRES)]
+        chain[cell][0], chain[cell][4] = OUT_T[0] + OUT_T[1] * k, OUT_F[0] * (1.0 + OUT_F[1] * k)
+    return chain, lnp, inside, outside
+
+
+def windowed(a, burn, thin):
+    """The kept steps of a [nsrc, nw, nsteps, ...] array as plain rows per source: [nsrc, nw * nkept, ...]."""
+    w = a[:, :, burn::thin]
+    return np.ascontiguousarray(w.reshape((w.shape[0], w.shape[1] * w.shape[2]) + w.shape[3:]))
+
+
+def column_reference(col, qs, lo=None, hi=None):
+    """numpy's count, min, max, mean and percentiles of one source's contiguous 1-d column, clipped as
+    _parcen_internal clips; with the sorted column (for the brackets)."""
+    x = np.ascontiguousarray(col, dtype=np.float64)
+    assert x.ndim == 1
+    if lo is not None:
+        x = x[x >= lo]
+    if hi is not None:
+        x = x[x <= hi]
+    x = np.ascontiguousarray(x)
+    return {"n": x.size, "min": x.min(), "max": x.max(), "mean": x.mean(), "pct": np.percentile(x, qs),
+            "sorted": np.sort(x), "scale": np.abs(x).mean()}
+
+
+def clip_midpoint(pooled_sorted, near, min_gap=1e-6, reach=2000):
+    """A clip bound that rounding cannot move an entry across: the midpoint of the two adjacent values of
+    `pooled_sorted` nearest to `near` whose relative gap exceeds min_gap.  Returns (bound, relative gap)."""
+    p = np.asarray(pooled_sorted)
+    i0 = int(np.clip(np.searchsorted(p, near), 1, p.size - 1))
+    for d in range(reach):
+        for i in (i0 + d, i0 - d):
+            if 1 <= i < p.size:
+                gap = (p[i] - p[i - 1]) / abs(p[i])
+                if gap > min_gap:
+                    return 0.5 * (p[i] + p[i - 1]), gap
+    raise AssertionError("no adjacent pair with a relative gap above %g within %d entries of %g" % (min_gap, reach, near))
+
+
+def dustmass_mp(row, opthin, wavenorm, redshift, lumdist_mpc, kappa=2.64, kappa_wave=125.0):
+    """The closed form of postprocess.dustmass for one chain row in 50-digit arithmetic (the row's doubles and the
+    constants' decimal literals are the inputs), rounded to double at the end."""
+    import mpmath as mp
+    with mp.workdps(50):
+        f = lambda x: mp.mpf(float(x))
+        T0, beta, lam0, fnorm = f(row[0]), f(row[1]), f(row[2]), f(row[4])
+        opz = 1 + f(redshift)
+        dl2 = (f(lumdist_mpc) * mp.mpf("3.0856775814913673e24")) ** 2
+        wavenorm_rest = f(wavenorm) / opz
+        nunorm_rest = mp.mpf("299792458e6") / wavenorm_rest
+        h, k, c = mp.mpf("6.6260693e-27"), mp.mpf("1.38065e-16"), mp.mpf("299792458e2")
+        temp_fac = h * nunorm_rest / k
+        bnu_fac = 2 * h * nunorm_rest ** 3 / c ** 2
+        knu_fac = wavenorm_rest / f(kappa_wave)
+        B = bnu_fac / mp.expm1(temp_fac / (T0 * opz))
+        K = 10 * f(kappa) * knu_fac ** (-beta)
+        m = dl2 * (fnorm * mp.mpf("1e-26")) / (opz * K * B * mp.mpf("1.97792e41"))
+        if not opthin:
+            tau = (lam0 / f(wavenorm)) ** beta
+            m = m * (-tau / mp.expm1(-tau))
+        return float(m)
+
+
+RAW_FIELDS = ("n_used", "mean", "min", "max", "pct", "status", "cov", "best", "best_index")
+
+
+def raw_equal(a, b, fields=RAW_FIELDS):
+    """Two ChainSummary results hold the same bits (NaNs at the same places)."""
+    return all(np.array_equal(getattr(a._raw, f), getattr(b._raw, f), equal_nan=True) for f in fields)

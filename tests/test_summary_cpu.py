@@ -176,3 +176,134 @@ def test_summary_entries_are_declared_and_bound():
         assert names == [f[0] for f in cls._fields_], (struct, names)
     assert _native.SUMMARY_COLS == int(re.search(r"#define MBB_SUMMARY_COLS (\d+)", hdr).group(1))
     assert _native.SUMMARY_MAX_PCT == int(re.search(r"#define MBB_SUMMARY_MAX_PCT (\d+)", hdr).group(1))
+
+
+# ---------------------------------------------------------------- builders of tests/test_summary_derived_gpu.py
+REDSHIFT, LUMDIST = 2.3, 18700.0
+
+
+def test_derived_seam_shapes_put_the_seam_inside_a_source():
+    """The shapes derived from the parsed kSumChunkRows: the chunk seam is strictly inside a source (and inside a
+    walker), a second chunk exists, and the short last chunk is one row.  A change of the constant fails here."""
+    chunk = SR.chunk_rows(ROOT)
+    assert chunk == 1 << 18
+    sh = SR.seam_shapes(chunk)
+    assert sh["cells"] == ((64, 1, 4100), (0, 1, 3843, 3844, 3845, 4099))
+    assert sh["tail"] == ((1, 1, (1 << 18) + 1), (0, (1 << 18) - 1, 1 << 18))
+    assert sh["windows"] == ((3, 50, 1750, 7, 3), (1, 64, 4097, 0, 1)) and sh["resident"] == (1, 64, 4100)
+    (nsrc, nw, nsteps), steps = sh["cells"]
+    assert SR.cell_of(chunk, nw, nsteps) == (63, 0, 3844) and SR.cell_of(chunk - 1, nw, nsteps) == (63, 0, 3843)
+    assert set(steps) >= {3843, 3844, 3845} and 0 < 3844 < nsteps - 1
+    for nsrc, nw, nsteps in [sh["cells"][0], sh["tail"][0], sh["resident"]] + [w[:3] for w in sh["windows"]]:
+        cells = nsrc * nw * nsteps
+        assert chunk < cells < 2 * chunk                                   # two chunks, the last one short
+        s, w, t = SR.cell_of(chunk, nw, nsteps)
+        assert 0 < t < nsteps and (s * nw + w) * nsteps + t == chunk         # the seam is inside a walker's steps
+    assert sh["tail"][0][2] - chunk == 1
+
+
+def test_distinct_chain_is_distinct_and_in_the_box():
+    chain, lnp = SR.distinct_chain(5, 3, 41, seed=2)
+    flat = chain.reshape(-1, 5)
+    assert lnp.shape == chain.shape[:-1] and np.all(flat >= SR.BOX_LO) and np.all(flat <= SR.BOX_HI)
+    for k in range(5):
+        assert len(np.unique(flat[:, k])) == flat.shape[0]
+
+
+@pytest.mark.parametrize("shape", SR.seam_shapes(1 << 18)["windows"] + ((3, 20, 30, 5, 2),))
+def test_sentinel_chain_has_its_sentinels_where_claimed(shape):
+    """Sentinels sit where claimed, the in-window and out-of-window sets are disjoint and as the window says, the
+    windowed reference of a parameter column is chain[:, :, burn::thin, i] flattened, and the dust mass (host numpy)
+    has its per-source maximum at the in-window sentinel of largest k while every out-of-window cell is larger."""
+    from mbb_emcee_amd import postprocess as pp
+    nsrc, nw, nsteps, burn, thin = shape
+    chunk = 1 << 18
+    chain, lnp, inside, outside = SR.sentinel_chain(nsrc, nw, nsteps, burn, thin, chunk, seed=5)
+    assert chain.shape == (nsrc, nw, nsteps, 5) and lnp.shape == (nsrc, nw, nsteps)
+    assert inside and not (set(inside) & set(outside))
+    assert bool(outside) == (thin > 1)
+    assert sorted(inside.values()) == list(range(len(inside))) and sorted(outside.values()) == list(range(len(outside)))
+    kept = np.zeros(nsteps, dtype=bool)
+    kept[burn::thin] = True
+    for (s, w, t), k in inside.items():
+        assert kept[t] and chain[s, w, t, 0] == SR.SENT_T[0] + SR.SENT_T[1] * k
+        assert chain[s, w, t, 4] == SR.SENT_F[0] * (1.0 + SR.SENT_F[1] * k)
+    for (s, w, t), k in outside.items():
+        assert not kept[t] and chain[s, w, t, 0] == SR.OUT_T[0] + SR.OUT_T[1] * k
+        assert chain[s, w, t, 4] == SR.OUT_F[0] * (1.0 + SR.OUT_F[1] * k)
+    cells = nsrc * nw * nsteps
+    for flat in (0, chunk - 1, chunk, cells - 1):
+        if flat < cells:
+            assert SR.cell_of(flat, nw, nsteps) in inside or SR.cell_of(flat, nw, nsteps) in outside
+    for s in range(nsrc):
+        for w in (0, nw - 1):
+            first, last = np.flatnonzero(kept)[[0, -1]]
+            assert (s, w, first) in inside and (s, w, last) in inside
+            if thin > 1:
+                assert (s, w, burn - 1) in outside and (s, w, burn + 1) in outside
+                assert kept[nsteps - 1] or (s, w, nsteps - 1) in outside
+    # everything else is an ordinary row: inside the box, with repeats
+    mask = np.ones((nsrc, nw, nsteps), dtype=bool)
+    for cell in list(inside) + list(outside):
+        mask[cell] = False
+    rest = chain[mask]
+    assert np.all(rest >= SR.BOX_LO) and np.all(rest <= SR.BOX_HI) and rest[:, 0].max() < SR.SENT_T[0]
+    rep = np.all(chain[:, :, 1:] == chain[:, :, :-1], axis=-1)
+    assert 0.5 < rep.mean() < 0.7                                           # 60 % of the moves are rejected
+    # the window
+    win = SR.windowed(chain, burn, thin)
+    n = nw * len(range(burn, nsteps, thin))
+    assert win.shape == (nsrc, n, 5)
+    for i in range(5):
+        for s in range(nsrc):
+            assert np.array_equal(win[s, :, i], chain[s, :, burn::thin, i].flatten())
+    assert np.array_equal(SR.windowed(lnp, burn, thin)[0], lnp[0, :, burn::thin].flatten())
+    # dust mass, thick and thin: who holds the maximum
+    for like in (_Like(), type("Thin", (_Like,), {"opthin": True, "noalpha": True})()):
+        m = pp.dustmass(like, chain, REDSHIFT, LUMDIST)
+        mw = SR.windowed(m, burn, thin)
+        for s in range(nsrc):
+            top = max((k, c) for c, k in inside.items() if c[0] == s)[1]
+            assert mw[s].max() == m[top] and (mw[s] == m[top]).sum() == 1
+            ks = sorted((k, m[c]) for c, k in inside.items() if c[0] == s)
+            assert all(a[1] < b[1] for a, b in zip(ks[:-1], ks[1:]))         # each sentinel is its own value
+            for c in outside:
+                if c[0] == s:
+                    assert m[c] > mw[s].max()
+    # the reference statistics of one column, clipped, are numpy's of what survives
+    col = win[0, :, 0]
+    ref = SR.column_reference(col, [15.85, 84.15], lo=float(np.median(col)))
+    keep = col[col >= np.median(col)]
+    assert ref["n"] == keep.size and ref["mean"] == keep.mean() and ref["min"] == keep.min() and ref["max"] == keep.max()
+    assert np.array_equal(ref["pct"], np.percentile(keep, [15.85, 84.15]))
+
+
+def test_clip_midpoints_exist_with_their_gap():
+    """Test 3's clip bounds: near the 20th and 90th percentile of every source's dust-mass column of the builder's
+    chain there is an adjacent pair of the pooled sorted values more than 1e-6 apart (relative), although 60 % of the
+    entries repeat their predecessor; the midpoint has entries on both sides within the source."""
+    from mbb_emcee_amd import postprocess as pp
+    nsrc, nw, nsteps, burn, thin = SR.seam_shapes(SR.chunk_rows(ROOT))["windows"][0]
+    chain, _, _, _ = SR.sentinel_chain(nsrc, nw, nsteps, burn, thin, 1 << 18, seed=5)
+    m = SR.windowed(pp.dustmass(_Like(), chain, REDSHIFT, LUMDIST), burn, thin)
+    pooled = np.sort(m.reshape(-1))
+    for s in range(nsrc):
+        for q in (20.0, 90.0):
+            near = np.percentile(m[s], q)
+            bound, gap = SR.clip_midpoint(pooled, near)
+            assert gap > 1e-6 and np.all(np.abs(pooled - bound) > 0.4e-6 * bound)
+            below = (m[s] < bound).mean()
+            assert abs(below - q / 100.0) < 0.01 and 0 < (m[s] <= bound).sum() < m.shape[1]
+    with pytest.raises(AssertionError):
+        SR.clip_midpoint(np.ones(50), 1.0)
+
+
+def test_dustmass_closed_form_in_50_digits_is_the_host_closed_form():
+    """dustmass_mp (the arbiter when device and host dust mass differ by more than 1e-13) against postprocess.dustmass
+    on rows of the box: the double evaluation is within 1e-13 of it."""
+    from mbb_emcee_amd import postprocess as pp
+    rows = SR.box_rows(np.random.RandomState(9), 12)
+    for like, kw in ((_Like(), {}), (type("Thin", (_Like,), {"opthin": True})(), {"kappa": 1.5, "kappa_wave": 250.0})):
+        host = pp.dustmass(like, rows, REDSHIFT, LUMDIST, **kw)
+        want = np.array([SR.dustmass_mp(r, like.opthin, like.wavenorm, REDSHIFT, LUMDIST, **kw) for r in rows])
+        assert np.all(np.abs(host - want) <= 1e-13 * np.abs(want))
