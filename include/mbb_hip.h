@@ -159,6 +159,12 @@ int mbb_sampler_set_state(mbb_ctx *ctx, void *sampler, const double *pos, const 
 int mbb_sampler_run(mbb_ctx *ctx, void *sampler, int nsteps, double stretch_a, double *chain,
                     double *lnprob, double *pos_out, double *lnprob_out, double *naccepted);
 int mbb_sampler_advance_async(mbb_ctx *ctx, void *sampler, int nsteps, double stretch_a);
+/* The completion counters of the sampler's one-launch runs (the lag guard of sampler forms 7 and 9), one value per
+ * counter, [2 sets][*ring][*shards] (cap >= 2 * ring * shards values; 128 is enough): read (store 0) or written
+ * (store 1) with the stream idle; *next_set is the set the next launch uses.  MBB_ERR_STATE when the sampler's last run
+ * was not of such a form.  A test hook; no reference counterpart. */
+int mbb_sampler_flow_counters(mbb_ctx *ctx, void *sampler, unsigned long long *counters, int cap, int store, int *ring,
+                              int *shards, int *next_set);
 /* Measurement helper (bench.py's timed region on one GPU): nsteps steps as mbb_sampler_advance_async
  * enqueues them, bracketed inside ONE call by the host clock and by two events on the context's stream,
  * recorded right before the run's first launch and right behind its last: clock; enqueue; stream wait; clock.

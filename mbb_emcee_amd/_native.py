@@ -70,6 +70,8 @@ SIGNATURES = {
     "mbb_sampler_run_summary": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(SummarySpec),
                                           C.POINTER(SummaryOut), _dp, _dp, _dp, _dp, _dp]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
+    "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mbb_sampler_advance_timed": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "mbb_sed_prologue_batch": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
                                          C.c_int, _dp, _ip]),

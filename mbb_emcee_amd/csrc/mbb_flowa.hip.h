@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(1024) k_flowa(const LikeArgs a_val)
     const int Wl = min(W, a.n - wbase); \
     const FlowMView fv = flowm_view(a.spec, a.nw); \
     const unsigned long long serial32 = a.flow_serial << 32; \
-    unsigned long long *const done_set = fv.done + (size_t)(a.spec_cfg & 1) * kFmRing * 16; \
+    unsigned long long *const done_set = fv.done + fm_done_word(a.spec_cfg & 1, 0, 0);      /* (shard 0 alone: the full count) */ \
     const long long spin_limit = flow_spin_limit(a.spec_cfg); \
     const int niter = a.persist; \
     int *const c_ready = ctl + 16, *const c_qdone = ctl + 32, *const c_edone = ctl + 4; \
@@ -94,8 +94,9 @@ __global__ void __launch_bounds__(1024) k_flowa(const LikeArgs a_val)
                 fm_put(fv.row + (size_t)r * kFmWords + 2 * e, v, serial32);
             }
         }
-        if (blockIdx.x == 0 && tid < kFmRing * 16)
-            __hip_atomic_store(fv.done + (size_t)((a.spec_cfg & 1) ^ 1) * kFmRing * 16 + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (blockIdx.x == 0 && tid < kFmRing * kFmShards)        // (every shard: the next launch may be form 7's)
+            __hip_atomic_store(fv.done + fm_done_word((a.spec_cfg & 1) ^ 1, tid / kFmShards, tid % kFmShards), 0ull, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
         const double2 *gb = reinterpret_cast<const double2 *>(a.poly_b);
         const double2 *gc = reinterpret_cast<const double2 *>(a.poly_c);
         double2 *lb = reinterpret_cast<double2 *>(s_pb);
@@ -356,7 +357,7 @@ __global__ void __launch_bounds__(1024) k_flowa(const LikeArgs a_val)
             const unsigned long long tag = serial32 | (unsigned long long)(c1 ? j : flow_seq(h ^ 1, m0));
             const bool want_e = active && l16 < 5, want_g = ci == 0 && lane == 5 && j >= kFmLag;
             const unsigned long long need_g = (unsigned long long)gridDim.x * (unsigned long long)nC * (unsigned long long)(((j - kFmLag) / kFmRing) + 1);
-            const unsigned long long *gword = done_set + ((j - kFmLag) & (kFmRing - 1)) * 16;
+            const unsigned long long *gword = done_set + fm_done_word(0, (j - kFmLag) & (kFmRing - 1), 0);
             if (ci == 0) FA_EV(j, 8);
             double pv = 0.0;
             {
@@ -446,7 +447,7 @@ __global__ void __launch_bounds__(1024) k_flowa(const LikeArgs a_val)
             MBB_FM_ORDER();
             if (ci == 0) FA_EV(j, 12);
             // this wave has read what it needs of half-step j - 1's rows, proposals and decisions: the lag guard
-            if (lane == 0) __hip_atomic_fetch_add(done_set + (j & (kFmRing - 1)) * 16, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) __hip_atomic_fetch_add(done_set + fm_done_word(0, j & (kFmRing - 1), 0), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 #undef MBB_FA_COMMON

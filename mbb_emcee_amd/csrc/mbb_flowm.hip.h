@@ -40,8 +40,12 @@
 //   row  [kFmSlots][nw][16]     the row after move m (T, beta, lambda0, alpha, fnorm, lnprob), same pairs;
 //                                 slot 0 also holds what the launch found (m = 0)
 //   mseq [nw][kFmSlots]         the decision: (serial of the launch << 32) | 2 x (half-step of move m + 1) + (it was accepted)
-//   done [2][kFmRing][16]       workgroups through with half-step j, running total per j mod kFmRing; a launch
-//                                 uses one of the two sets and clears the other for the sampler's next launch
+//   done [2][kFmRing][kFmShards][16]  workgroups through with half-step j, running total per j mod kFmRing, in kFmShards
+//                                 counters on 128-byte lines of their own: a workgroup arrives on the counter of its number
+//                                 mod kFmShards, a reader asks every counter for the workgroups that arrive on it (one lane
+//                                 each, one load instruction).  250 adds per half-step on ONE word are more than a word
+//                                 takes (tools/lat_handoff load: 84 per us), and whatever shares its channel waits behind
+//                                 them.  A launch uses one of the two sets and clears the other for the sampler's next launch
 // A check word is (serial of the launch << 32 | half-step of the move + 1) XOR the bits of the value:
 // a reader takes an element when the pair fits, whenever and in whatever order the two stores arrive,
 // so nobody waits for stores to land or raises a flag after them, and nothing left in memory by an
@@ -164,7 +168,7 @@ __device__ __forceinline__ unsigned int fm_row_lo(unsigned long long v)       //
     const long long spin_limit = flow_spin_limit(a.spec_cfg); \
     const FlowMView fv = flowm_view(a.spec, a.nw); \
     const unsigned long long serial32 = a.flow_serial << 32; \
-    unsigned long long *const done_set = fv.done + (size_t)(a.spec_cfg & 1) * kFmRing * 16; \
+    unsigned long long *const done_set = fv.done + fm_done_word(a.spec_cfg & 1, 0, 0); \
     const int niter = a.persist;
 // One workgroup serves NP pairs of walkers.  Only NP = 1 is instantiated since round 4 (up to two walkers per CU);
 // round 3's NP = 2 for ensembles of up to four per CU -- the roles taking the pairs one after another in every
@@ -253,8 +257,9 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             const int r = (t12 < 6 ? 0 : a.c_count) + wbase + tid / 12, e = t12 < 6 ? t12 : t12 - 6;
             fm_put(fv.row + (size_t)r * kFmWords + 2 * e, a.pos6[(size_t)r * 6 + e], serial32);
         }
-        if (blockIdx.x == 0 && tid < kFmRing * 16)
-            __hip_atomic_store(fv.done + (size_t)((a.spec_cfg & 1) ^ 1) * kFmRing * 16 + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (blockIdx.x == 0 && tid < kFmRing * kFmShards)
+            __hip_atomic_store(fv.done + fm_done_word((a.spec_cfg & 1) ^ 1, tid / kFmShards, tid % kFmShards), 0ull, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
         (void)done_set; (void)niter; (void)spin_limit;
     }
     __syncthreads();
@@ -447,13 +452,14 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             const unsigned long long need_p = (unsigned long long)flow_seq(L_half ^ 1, m_par);
             // one loop, one round trip when everything is there: lane 21 the walker's lnprob as it is
             // (element 5 of its row after move m_s), lane 22 the partner's decision of half-step it - 1,
-            // lane 23 the lag guard
+            // lanes 23 .. 23 + kFmShards - 1 the lag guard, a shard of its counters each (an empty shard is not asked)
             const double *lnp_p = fv.row + ((size_t)(m_s % kFmSlots) * a.nw + row) * kFmWords + 10;
             const unsigned long long tag_s = serial32 | (unsigned long long)flow_seq(L_half, m_s);
-            const unsigned long long need_g = 2ull * (unsigned long long)a.n * (unsigned long long)(((it - kFmLag) / kFmRing) + 1);
+            const int gsh = (lane - 23) & (kFmShards - 1);
+            const unsigned long long need_g = (unsigned long long)fm_shard_wgs(2 * a.n, gsh) * (unsigned long long)(((it - kFmLag) / kFmRing) + 1);
             const unsigned long long *word = lane == 22 ? fv.mseq + (size_t)prow * kFmMseq + (m_par % kFmSlots)
-                                                        : done_set + ((it - kFmLag) & (kFmRing - 1)) * 16;
-            const bool watch = (lane == 22 && need_p > 0) || (lane == 23 && it >= kFmLag);
+                                                        : done_set + fm_done_word(0, (it - kFmLag) & (kFmRing - 1), gsh);
+            const bool watch = (lane == 22 && need_p > 0) || (lane >= 23 && lane < 23 + kFmShards && it >= kFmLag && need_g > 0);
             // The band sums do not wait for the partner: as soon as Q is through they are formed, between
             // asking for the words and looking at the answers; whichever comes last -- the partner's
             // decision or the sums -- is followed by the accept test alone.
@@ -521,7 +527,8 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             const int q_need = nq * ((it / kFmNB) + 1);
             FM_EV(it, 9);
 #ifdef MBB_STAMPS
-            unsigned long long t_ok = 0;
+            unsigned long long t_ok = 0;                          // when a lane's word was seen, and in the top 12 bits how many
+                                                                  // ticks before that the look that saw it was issued
 #endif
             unsigned long long pv = 0;
             double lnp = 0.0;
@@ -535,6 +542,9 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 double lv;
                 unsigned long long lchk, wv;
                 const bool ask_l = lane == 21 && !ok, ask_w = watch && !ok;
+#ifdef MBB_STAMPS
+                const unsigned long long t_ask = __builtin_amdgcn_s_memrealtime();
+#endif
                 if (ask_l) {
                     lv = ld_dev(lnp_p);
                     lchk = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(lnp_p) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -565,7 +575,11 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                 if (ask_l) { lnp = lv; ok = (lchk ^ (unsigned long long)__double_as_longlong(lv)) == tag_s; }
                 if (ask_w) { pv = wv; ok = lane == 22 ? dec_ok(pv, need_p) : pv >= need_g; }
 #ifdef MBB_STAMPS
-                if ((ask_l || ask_w) && ok) t_ok = __builtin_amdgcn_s_memrealtime();
+                if ((ask_l || ask_w) && ok) {
+                    t_ok = __builtin_amdgcn_s_memrealtime();
+                    const unsigned long long dt = t_ok - t_ask;
+                    t_ok = (t_ok & ((1ull << 52) - 1)) | ((dt > 4095ull ? 4095ull : dt) << 52);
+                }
 #endif
                 if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
                 ++spins;
@@ -584,7 +598,11 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
             FM_EV(it, 5);
             FM_EVV(it, 7, prow);
 #ifdef MBB_STAMPS
-            { const unsigned long long t21 = __shfl(t_ok, 21), t22 = __shfl(t_ok, 22), t23 = __shfl(t_ok, 23);
+            { unsigned long long t21 = __shfl(t_ok, 21), t22 = __shfl(t_ok, 22), t23 = __shfl(t_ok, 23);
+              for (int sh = 1; sh < kFmShards; ++sh) {            // (the lag guard: the shard seen last)
+                  const unsigned long long ts = __shfl(t_ok, 23 + sh);
+                  if ((ts & ((1ull << 52) - 1)) > (t23 & ((1ull << 52) - 1))) t23 = ts;
+              }
               FM_EVV(it, 10, t21); FM_EVV(it, 11, t22); FM_EVV(it, 12, t23); }
 #endif
             if (!have_sums) {
@@ -632,7 +650,9 @@ __global__ void __launch_bounds__(1024) k_flowm(const LikeArgs a)
                     if (lane == 0 && accept) atomicAdd(a.nacc + (size_t)L_half * a.n + w, 1u);
                 }
                 __builtin_amdgcn_s_setprio(kFmPrioWait);          // (the sibling whose candidate it was not: the same)
-                if (lane == 0) __hip_atomic_fetch_add(done_set + (it & (kFmRing - 1)) * 16, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0)
+                    __hip_atomic_fetch_add(done_set + fm_done_word(0, it & (kFmRing - 1), fm_shard((int)blockIdx.x)), 1ull, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
             }
             FM_T(3);
         }

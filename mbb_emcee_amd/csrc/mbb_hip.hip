@@ -1405,6 +1405,35 @@ extern "C" int mbb_sampler_destroy(mbb_ctx *c, void *sp)
 
 static int sampler_check_pending(mbb_ctx *c, mbb_sampler_state *s);
 
+// The completion counters of a sampler's one-launch runs (forms 7 and 9; FlowMView's `done`), [2][ring][shards] as the
+// kernels lay them out (mbb_flow_index.h), one value per counter: read (store 0) or written (store 1) with the stream
+// idle.  *next_set is the set the sampler's next launch uses.  For the tests that hold the lag guard's bookkeeping.
+extern "C" int mbb_sampler_flow_counters(mbb_ctx *c, void *sp, unsigned long long *counters, int cap, int store, int *ring,
+                                         int *shards, int *next_set)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    mbb_sampler_state *s = (mbb_sampler_state *)sp;
+    const int n = 2 * kFmRing * kFmShards;
+    if (!s || !counters || !ring || !shards || !next_set || cap < n) return fail(MBB_ERR_ARG, "bad arguments");
+    if (!s->d_spec || (s->spec_form != 7 && s->spec_form != 9))
+        return fail(MBB_ERR_STATE, "the sampler holds no state of a one-launch run (forms 7, 9)");
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const FlowMView fv = flowm_view(s->d_spec, s->rows());
+    std::vector<unsigned long long> w(kFmDoneWords);
+    HIPCHK(hipMemcpy(w.data(), fv.done, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int set = 0; set < 2; ++set)
+        for (int slot = 0; slot < kFmRing; ++slot)
+            for (int sh = 0; sh < kFmShards; ++sh) {
+                unsigned long long &word = w[fm_done_word(set, slot, sh)], &val = counters[(set * kFmRing + slot) * kFmShards + sh];
+                if (store) word = val;
+                else val = word;
+            }
+    if (store) HIPCHK(hipMemcpy(fv.done, w.data(), w.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    *ring = kFmRing; *shards = kFmShards; *next_set = s->flowm_parity;
+    return MBB_OK;
+}
+
 extern "C" int mbb_sampler_reset(mbb_ctx *c, void *sp)
 {
     int rc = use(c);
@@ -1766,7 +1795,7 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, 
             // forms 7 and 9 find their completion counters cleared by the launch before it (either's); after
             // another form (or a run that gave up) has used the memory, once from here
             const FlowMView fvh = flowm_view(s->d_spec, (int)R);
-            HIPCHK(hipMemsetAsync(fvh.done, 0, 2 * kFmRing * 16 * sizeof(unsigned long long), c->stream));
+            HIPCHK(hipMemsetAsync(fvh.done, 0, kFmDoneWords * sizeof(unsigned long long), c->stream));
             s->flowm_parity = 0;
         }
         s->spec_form = rp.form;

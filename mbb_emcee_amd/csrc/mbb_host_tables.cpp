@@ -327,3 +327,19 @@ extern "C" int mbbh_flowm_consts(int *slots, int *lag, int *ring, int *nc, int *
     *slots = kFmSlots; *lag = kFmLag; *ring = kFmRing; *nc = kFmNC; *nb = kFmNB;
     return 0;
 }
+
+// ... and its sharded lag guard (tests/test_flow_guard_cpu.py): shards, the shard workgroup `wg` arrives on, the
+// workgroups of a grid that arrive on `shard`, the word of (set, ring slot, shard) counted from the start of a run's
+// state of `nw` rows, where that state's decision words end, its size and the size of the allocation it lives in
+extern "C" int mbbh_flowm_guard(int grid, int wg, int set, int slot, int shard, int nw, int *shards, int *wg_shard,
+                                int *shard_wgs, long long *word, long long *mseq_end, long long *words, long long *alloc_words)
+{
+    *shards = kFmShards;
+    *wg_shard = fm_shard(wg);
+    *shard_wgs = fm_shard_wgs(grid, shard);
+    *words = (long long)flowm_words((size_t)nw);
+    *word = *words - kFmDoneWords + fm_done_word(set, slot, shard);
+    *mseq_end = (long long)flowm_mseq_end((size_t)nw);
+    *alloc_words = (long long)spec_words((size_t)nw);
+    return 0;
+}

@@ -158,15 +158,11 @@ static_assert(sizeof(LikeArgs) == 480, "the argument block: every launch of ever
 //   startf, endf [16]  per rank: the number of the run whose state is set up / whose launch has ended
 // In a sharded run every rank holds all of it (its own records only) in memory its peers have
 // mapped, and whoever publishes a decision, a row or a word stores it into every rank's copy.
-constexpr int kFlowRecN = 22, kFlowRec = 48;
+// (kFlowRecN, kFlowRec and spec_words, the size of the allocation: mbb_flow_index.h)
 struct FlowView {
     double *rec, *st;
     unsigned long long *seq, *done, *mseq, *pub, *startf, *endf;
 };
-__host__ __device__ constexpr size_t spec_words(size_t nw)
-{
-    return nw * ((size_t)kFlowSlots * 2 * kFlowRec + kFlowSlots * 8 + 1 + kFlowSlots) + 8 * 16 + 16 * 8 + 32;
-}
 __host__ __device__ __forceinline__ FlowView flow_view(double *spec, int nw)
 {
     FlowView v;
@@ -1274,15 +1270,7 @@ struct FlowMView {
     double *prop, *row;
     unsigned long long *mseq, *done;
 };
-constexpr int kFmWords = 16;   // words per proposal / per row
-// (kFmSlots, kFmLag, kFmRing: mbb_flow_index.h)
-__host__ __device__ constexpr size_t flowm_words(size_t nw)
-{
-    // (the completion counters begin on a 256-byte boundary: 250 atomic adds per half-step on a word that shared its
-    // 128-byte line with the last rows' decision words, which their partners poll, cost every second launch of a
-    // sampler 2 % -- profiles/r04/done_counters_alignment.txt)
-    return ((nw * ((size_t)kFmSlots * 2 * kFmWords + kFmSlots * kFmWords + kFmMseq) + 31) & ~(size_t)31) + 2 * kFmRing * 16;
-}
+// (kFmWords, kFmSlots, kFmLag, kFmRing, and flowm_words, the size of the state: mbb_flow_index.h)
 static_assert(flowm_words(1000) <= spec_words(1000) && flowm_words(2) <= spec_words(2), "form 7 lives in the allocation of forms 5/6");
 __host__ __device__ __forceinline__ FlowMView flowm_view(double *spec, int nw)
 {
@@ -1290,7 +1278,7 @@ __host__ __device__ __forceinline__ FlowMView flowm_view(double *spec, int nw)
     v.prop = spec;
     v.row = spec + (size_t)nw * kFmSlots * 2 * kFmWords;
     v.mseq = reinterpret_cast<unsigned long long *>(v.row + (size_t)nw * kFmSlots * kFmWords);
-    v.done = reinterpret_cast<unsigned long long *>(spec) + (flowm_words((size_t)nw) - 2 * kFmRing * 16);
+    v.done = reinterpret_cast<unsigned long long *>(spec) + (flowm_words((size_t)nw) - kFmDoneWords);
     return v;
 }
 // SMODE 6: tells every rank that this rank's copy is set up for run `run` (which = 0) or that

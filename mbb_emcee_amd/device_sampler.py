@@ -296,6 +296,22 @@ class DeviceEnsembleSampler(object):
         ctx, h = self._handle()
         _native._check(ctx.lib.mbb_sampler_advance_async(ctx.h, h, int(N), self.a))
 
+    def flow_counters(self, store=None):
+        """The completion counters of the sampler's one-launch runs (the lag guard of forms 7 and 9) as an array
+        [2 sets, ring, shards] of uint64, and the set the next launch uses; `store`: such an array, written first.
+        A test hook."""
+        ctx, h = self._handle()
+        buf = (C.c_ulonglong * 256)()
+        ring, shards, nxt = C.c_int(), C.c_int(), C.c_int()
+        if store is not None:
+            flat = np.asarray(store, dtype=np.uint64).reshape(-1)
+            for i, v in enumerate(flat):
+                buf[i] = int(v)
+            _native._check(ctx.lib.mbb_sampler_flow_counters(ctx.h, h, buf, 256, 1, C.byref(ring), C.byref(shards), C.byref(nxt)))
+        _native._check(ctx.lib.mbb_sampler_flow_counters(ctx.h, h, buf, 256, 0, C.byref(ring), C.byref(shards), C.byref(nxt)))
+        n = 2 * ring.value * shards.value
+        return np.array(buf[:n], dtype=np.uint64).reshape(2, ring.value, shards.value), nxt.value
+
     def advance_timed(self, N):
         """N steps as advance_async enqueues them, timed inside one native call: (wall seconds from an
         idle stream to an idle stream, stream milliseconds between two events).  Benchmarks."""

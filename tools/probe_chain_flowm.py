@@ -1,6 +1,9 @@
 """Diagnostic build only (-DMBB_STAMPS): the critical path of sampler form 7, from event times of the launch's
 last 64 half-steps (s_memrealtime, 10 ns ticks; all CUs share that clock).  From a late decision the path is walked
-back, at every join along the input that arrived last, and the time is booked to the kind of segment."""
+back, at every join along the input that arrived last, and the time is booked to the kind of segment.
+Events 10-12 (when lanes 21, 22 and the lag guard's lanes saw their words) carry in their top 12 bits how many ticks
+earlier the look that succeeded was issued: "out -> seen" splits into "out -> the successful look issued" (how long
+the store takes to become visible to a look) and "issued -> seen" (the load's trip on the consumer's CU)."""
 import os, sys, ctypes as C, collections
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +27,11 @@ print("%.3f us per step, form %d" % (ctx.elapsed_ms(e0, e1) * 1e3 / NS, ctx.info
 nb = int(ctx.info("last_grid")); half = nb // 2
 big = np.zeros((32768 + 256 + nb * 32 + 8, 32), dtype=np.uint64)
 lib.mbb_stamps(ctx.h, big.ctypes.data_as(C.c_void_p), big.shape[0])
-ev = big.reshape(-1)[(1 << 20) + 8192:(1 << 20) + 8192 + nb * 64 * 16].reshape(nb, 64, 16).astype(np.int64)
+raw = big.reshape(-1)[(1 << 20) + 8192:(1 << 20) + 8192 + nb * 64 * 16].reshape(nb, 64, 16)
+trip = (raw >> np.uint64(52)).astype(np.int64)                      # (events 10-12: issued -> seen, ticks; 0 elsewhere)
+ev = raw.copy()
+ev[:, :, 10:13] &= np.uint64((1 << 52) - 1)
+ev = ev.astype(np.int64)
 niter = 2 * NS
 T = lambda g, j, e: ev[g, j & 63, e] * 10.0               # ns
 
@@ -125,6 +132,9 @@ for j in range(niter - 50, niter - 2):
         td = decider(int(prow) % half, j - 1)[1]
         if t22 > 0 and t9 < td:
             lat["partner's decision out -> seen by a waiting E"].append(t22 - td)
+            dt = trip[g, j & 63, 11] * 10.0
+            lat["    out -> the successful look issued"].append(t22 - dt - td)
+            lat["    issued -> seen"].append(dt)
         if t23 > 0:
             tl = max(max(T(x, j - 4, 5), T(x, j - 4, 4)) for x in range(nb))
             lat["last workgroup through with j - 4 (its words and sums) -> lag guard seen"].append(t23 - tl)
