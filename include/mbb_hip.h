@@ -232,6 +232,52 @@ int mbb_sampler_run_summary(mbb_ctx *ctx, void *sampler, int nsteps, double stre
                             const mbb_summary_spec *spec, const mbb_summary_out *out, double *chain,
                             double *lnprob, double *pos_out, double *lnprob_out, double *naccepted);
 
+/* ---- convergence diagnostics of a chain, computed where the chain is ------ */
+/* Replaces: sampler.acor as the fit driver prints it (mbb_fit.py:548-561), for every source of a catalogue fit and
+ * without the chain on the host.  Per (source, parameter), over the steps burn <= t < nsteps (n of them):
+ *   tau, window  the integrated autocorrelation time with Sokal's automatic window: rho_k = c_k / c_0 with
+ *                c_k = sum_{i < n - k} y_i y_{i+k} of the centred series y, tau(m) = 2 sum_{k <= m} rho_k - 1,
+ *                window M = the first m with m >= c tau(m), else n - 1; tau = tau(M).
+ *                MBB_DIAG_MEAN: the series is the ensemble mean over walkers at each step.
+ *                MBB_DIAG_WALKERS: each walker's own rho_k, averaged over walkers, windowed once (emcee >= 3).
+ *   ess          nw n / tau
+ *   rhat         split R-hat (Gelman & Rubin, not rank-normalised): every walker's first and last h = n / 2 kept
+ *                steps are 2 nw sequences; W the mean of their variances (ddof 1), B = h var(their means) (ddof 1),
+ *                R = sqrt(((h - 1) / h W + B / h) / W); NaN when h < 2.
+ *   acf          rho_0 .. rho_{nacf-1}
+ * All sums are fixed-order: a chain gives the same bits every time, resident or uploaded.  A series may have
+ * MBB_DIAG_MAX_STEPS kept steps; a longer one is MBB_ERR_ARG. */
+#define MBB_DIAG_MAX_STEPS 16384
+enum mbb_diag_method { MBB_DIAG_MEAN = 0, MBB_DIAG_WALKERS = 1 };
+/* status of a (source, parameter): bits */
+enum mbb_diag_status {
+    MBB_DIAG_SHORT = 1,       /* fewer than 8 kept steps: tau, ess NaN, window -1                                  */
+    MBB_DIAG_CONSTANT = 2,    /* the series (MEAN) or a walker's series (WALKERS) is constant, or c_0 <= 0: a fixed
+                                 parameter; tau, ess NaN, window -1                                                  */
+    MBB_DIAG_HAS_NAN = 4,     /* the column holds a NaN or an infinity inside the window: tau, ess NaN, window -1   */
+    MBB_DIAG_UNRELIABLE = 8   /* the chain is shorter than tol tau                                                  */
+};
+typedef struct mbb_diag_spec {
+    int32_t burn;                          /* window: steps burn <= t < nsteps                                */
+    int32_t method;                        /* mbb_diag_method                                                 */
+    int32_t nacf;                          /* values of rho wanted, 0 .. nsteps - burn                        */
+    double c;                              /* Sokal's window factor (emcee: 5)                                */
+    double tol;                            /* MBB_DIAG_UNRELIABLE below tol tau kept steps (emcee: 50)        */
+} mbb_diag_spec;
+/* Where diagnostics go; every pointer is the caller's, host memory; acf may be NULL. */
+typedef struct mbb_diag_out {
+    double *tau, *ess, *rhat;              /* [nsrc][5]                                                       */
+    int32_t *window, *status;              /* [nsrc][5]: M, mbb_diag_status bits                              */
+    double *acf;                           /* [nsrc][5][nacf] or NULL                                         */
+} mbb_diag_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5]: upload, diagnose on the device, download the result. */
+int mbb_chain_diagnostics(mbb_ctx *ctx, const double *chain, int nsrc, int nw, int nsteps,
+                          const mbb_diag_spec *spec, const mbb_diag_out *out);
+/* The same of the chain the sampler's last stored or summarised run (mbb_sampler_run with a chain or lnprob
+ * array, mbb_sampler_run_summary) left on the device.  MBB_ERR_STATE when there is none, and for a sharded run (a
+ * communicator or the one-hop exchange with more than one rank): a rank holds only its own walkers' chain. */
+int mbb_sampler_diagnostics(mbb_ctx *ctx, void *sampler, const mbb_diag_spec *spec, const mbb_diag_out *out);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

@@ -13,7 +13,9 @@ from .ensemble import EnsembleSampler
 from .device_sampler import DeviceEnsembleSampler
 from .mbb_fit import mbb_fitter
 from .results import chain_summary, ChainSummary
+from .diagnostics import chain_diagnostics, ChainDiagnostics
 
 __version__ = "0.1.0"
 __all__ = ["response", "response_set", "modified_blackbody", "alpha_merge_eqn", "isiterable", "likelihood",
-           "EnsembleSampler", "DeviceEnsembleSampler", "mbb_fitter", "chain_summary", "ChainSummary"]
+           "EnsembleSampler", "DeviceEnsembleSampler", "mbb_fitter", "chain_summary", "ChainSummary",
+           "chain_diagnostics", "ChainDiagnostics"]

@@ -41,6 +41,21 @@ class SummaryOut(C.Structure):
                 ("status", _ip), ("cov", _dp), ("best", _dp), ("best_index", _ip)]
 
 
+DIAG_MEAN, DIAG_WALKERS = 0, 1
+DIAG_SHORT, DIAG_CONSTANT, DIAG_HAS_NAN, DIAG_UNRELIABLE = 1, 2, 4, 8
+DIAG_MAX_STEPS = 16384
+
+
+class DiagSpec(C.Structure):
+    """mbb_diag_spec (include/mbb_hip.h)"""
+    _fields_ = [("burn", C.c_int32), ("method", C.c_int32), ("nacf", C.c_int32), ("c", C.c_double), ("tol", C.c_double)]
+
+
+class DiagOut(C.Structure):
+    """mbb_diag_out (include/mbb_hip.h)"""
+    _fields_ = [("tau", _dp), ("ess", _dp), ("rhat", _dp), ("window", _ip), ("status", _ip), ("acf", _dp)]
+
+
 # name -> (restype, argtypes); mirrors include/mbb_hip.h one to one
 SIGNATURES = {
     "mbb_last_error": (C.c_char_p, []),
@@ -69,6 +84,8 @@ SIGNATURES = {
                                     C.POINTER(SummaryOut)]),
     "mbb_sampler_run_summary": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(SummarySpec),
                                           C.POINTER(SummaryOut), _dp, _dp, _dp, _dp, _dp]),
+    "mbb_chain_diagnostics": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(DiagSpec), C.POINTER(DiagOut)]),
+    "mbb_sampler_diagnostics": (C.c_int, [_vp, _vp, C.POINTER(DiagSpec), C.POINTER(DiagOut)]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

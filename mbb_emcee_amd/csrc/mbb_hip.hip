@@ -30,6 +30,7 @@
 #include "mbb_device.hip.h"
 #include "mbb_kernels.hip.h"
 #include "mbb_summary.hip.h"
+#include "mbb_diag.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
 #define MBB_FLOW_EXT(OT, NA)                                                    \
@@ -269,6 +270,12 @@ struct mbb_ctx {
              *outbuf = nullptr, *der = nullptr;
         size_t c_part = 0, c_state = 0, c_hist = 0, c_covpart = 0, c_colstatus = 0, c_outbuf = 0, c_der = 0;
     } sum;
+    // ... and of the chain diagnostics (diag_run)
+    struct DiagWork {
+        void *mean = nullptr, *seq = nullptr, *outbuf = nullptr;
+        size_t c_mean = 0, c_seq = 0, c_outbuf = 0;
+        size_t lds_granted = 0;               // dynamic-LDS ceiling already requested for k_diag_acf
+    } diag;
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -516,6 +523,7 @@ extern "C" void mbb_ctx_destroy(mbb_ctx *c)
     free_dev(c->d_sed_wk);
     free_dev(c->sum.part); free_dev(c->sum.state); free_dev(c->sum.hist); free_dev(c->sum.covpart);
     free_dev(c->sum.colstatus); free_dev(c->sum.outbuf); free_dev(c->sum.der);
+    free_dev(c->diag.mean); free_dev(c->diag.seq); free_dev(c->diag.outbuf);
     for (int i = 0; i < 2; ++i)
         if (c->ev_timed[i]) (void)hipEventDestroy(c->ev_timed[i]);
     if (c->stream) {
@@ -2394,6 +2402,122 @@ extern "C" int mbb_sampler_run_summary(mbb_ctx *c, void *sp, int nsteps, double 
         return summary_run(c, s->d_chain_out, s->d_chain_out + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
     }
     return sampler_run(c, s, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted, true, spec, out);
+}
+
+// ---- convergence diagnostics of a chain (mbb_diag.hip.h) ------------------------
+// The argument checks of a diagnostics call: before anything is allocated or uploaded.
+static int diag_check(int nsrc, int nw, int nsteps, const mbb_diag_spec *sp, const mbb_diag_out *o)
+{
+    if (!sp || !o || !o->tau || !o->ess || !o->rhat || !o->window || !o->status)
+        return fail(MBB_ERR_ARG, "null diagnostics argument");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    if (sp->burn < 0 || sp->burn >= nsteps) return fail(MBB_ERR_ARG, "burn leaves no step of the chain");
+    if (sp->method != MBB_DIAG_MEAN && sp->method != MBB_DIAG_WALKERS)
+        return fail(MBB_ERR_ARG, "unknown diagnostics method (0 mean, 1 walkers)");
+    if (!(sp->c > 0.0 && sp->c < INFINITY)) return fail(MBB_ERR_ARG, "the window factor c must be positive");
+    if (!(sp->tol >= 0.0 && sp->tol < INFINITY)) return fail(MBB_ERR_ARG, "tol must not be negative");
+    const int n = nsteps - sp->burn;
+    if (n > mbbg::kMaxSteps) return fail(MBB_ERR_ARG, "more than 16384 kept steps per series: raise burn");
+    if (sp->nacf < 0 || sp->nacf > n) return fail(MBB_ERR_ARG, "nacf must be between 0 and the number of kept steps");
+    if ((size_t)nsrc * 5 > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    return MBB_OK;
+}
+
+// Diagnose a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
+static int diag_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nsteps, const mbb_diag_spec *sp,
+                    const mbb_diag_out *o)
+{
+    using namespace mbbg;
+    static_assert(kStShort == MBB_DIAG_SHORT && kStConst == MBB_DIAG_CONSTANT && kStNaN == MBB_DIAG_HAS_NAN &&
+                  kStUnreliable == MBB_DIAG_UNRELIABLE && kMaxSteps == MBB_DIAG_MAX_STEPS, "diagnostics constants");
+    int rc;
+    if ((rc = diag_check(nsrc, nw, nsteps, sp, o))) return rc;
+    const int n = nsteps - sp->burn;
+    const size_t ncol = (size_t)nsrc * 5, nacf = o->acf ? (size_t)sp->nacf : 0;
+    DiagArgs a;
+    memset(&a, 0, sizeof a);
+    a.chain = d_chain;
+    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.n = n;
+    a.method = sp->method; a.nacf = (int)nacf; a.c = sp->c; a.tol = sp->tol;
+    mbb_ctx::DiagWork &w = c->diag;
+    const size_t nd = ncol * (3 + nacf), out_bytes = nd * sizeof(double) + ncol * 2 * sizeof(int);
+    if (sp->method == MBB_DIAG_MEAN && (rc = sum_grow(c, &w.mean, &w.c_mean, ncol * n * sizeof(double)))) return rc;
+    if ((rc = sum_grow(c, &w.seq, &w.c_seq, ncol * nw * 4 * sizeof(double)))) return rc;
+    if ((rc = sum_grow(c, &w.outbuf, &w.c_outbuf, out_bytes))) return rc;
+    a.mean = (double *)w.mean; a.seq = (double *)w.seq;
+    a.o_tau = (double *)w.outbuf;
+    a.o_ess = a.o_tau + ncol;
+    a.o_rhat = a.o_ess + ncol;
+    a.o_acf = nacf ? a.o_rhat + ncol : nullptr;
+    a.o_window = (int *)((double *)w.outbuf + nd);
+    a.o_status = a.o_window + ncol;
+    const size_t lds = acf_lds_bytes(n);
+    if (lds > 60 * 1024 && lds > w.lds_granted) {
+        // (beyond 64 KB of LDS per workgroup, the kernel's 2.3 KB of static LDS included, its dynamic-LDS ceiling has
+        // to be raised: from 60 KB of dynamic on, once per size)
+        const size_t want = std::min<size_t>((lds + 16383) & ~(size_t)16383, acf_lds_bytes(kMaxSteps));
+        HIPCHK(hipFuncSetAttribute((const void *)k_diag_acf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
+        w.lds_granted = want;
+    }
+    if (sp->method == MBB_DIAG_MEAN) {
+        const size_t per = ((size_t)n * 5 + kThreads - 1) / kThreads;
+        if (per * nsrc > 0x7fffffffull) return fail(MBB_ERR_ARG, "too many sources");
+        hipLaunchKernelGGL(k_diag_mean, dim3((unsigned)(per * nsrc)), dim3(kThreads), 0, c->stream, a);
+    }
+    hipLaunchKernelGGL(k_diag_acf, dim3((unsigned)ncol), dim3(kThreads), lds, c->stream, a);
+    // a wave per walker; when the columns do not fill the device by themselves, the walkers are spread over y
+    const int waves = kThreads / 64;
+    const int gy = ncol >= 1024 ? 1 : std::min(64, (nw + waves - 1) / waves);
+    hipLaunchKernelGGL(k_diag_seq, dim3((unsigned)ncol, (unsigned)gy), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_diag_rhat, dim3((unsigned)ncol), dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    std::vector<char> host(out_bytes);
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const double *hd = (const double *)host.data();
+    memcpy(o->tau, hd, ncol * sizeof(double));
+    memcpy(o->ess, hd + ncol, ncol * sizeof(double));
+    memcpy(o->rhat, hd + 2 * ncol, ncol * sizeof(double));
+    if (nacf) memcpy(o->acf, hd + 3 * ncol, ncol * nacf * sizeof(double));
+    const int *hi = (const int *)(hd + nd);
+    memcpy(o->window, hi, ncol * sizeof(int));
+    memcpy(o->status, hi + ncol, ncol * sizeof(int));
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_diagnostics(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
+                                     const mbb_diag_spec *spec, const mbb_diag_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = diag_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    double *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, cells * 5 * sizeof(double)));
+    hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(MBB_ERR_HIP, "upload of the chain", e); }
+    rc = diag_run(c, d, nsrc, nw, nsteps, spec, out);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int mbb_sampler_diagnostics(mbb_ctx *c, void *sp, const mbb_diag_spec *spec, const mbb_diag_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    mbb_sampler_state *s = (mbb_sampler_state *)sp;
+    if (!s || !spec || !out) return fail(MBB_ERR_ARG, "bad sampler arguments");
+    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
+    ShardPlan p;
+    if ((rc = shard_plan(c, s, p))) return rc;
+    if (p.collective)
+        return fail(MBB_ERR_STATE, "a sharded sampler run cannot be diagnosed on the device: a rank holds only its own "
+                                   "walkers' chain");
+    if (s->resident_nsteps <= 0 || !s->d_chain_out)
+        return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
+    return diag_run(c, s->d_chain_out, s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

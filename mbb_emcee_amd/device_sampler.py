@@ -72,6 +72,8 @@ class DeviceEnsembleSampler(object):
         if getattr(self, "summary", None) is not None:
             self.summary.drop_chain()
         self.summary = None
+        self.convergence_ = None
+        self._resident = 0                    # steps of the last run's chain that are resident on the device
         if self._h is not None:
             _native._check(self._ctx.lib.mbb_sampler_reset(self._ctx.h, self._h))
 
@@ -111,15 +113,50 @@ class DeviceEnsembleSampler(object):
     def random_state(self):
         return self.seed
 
-    def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, **unused):
+    def convergence(self, burn=0, c=5.0, tol=50.0, method="mean", nacf=0):
+        """``diagnostics.ChainDiagnostics`` (autocorrelation time, ESS, split R-hat per parameter and source) of the
+        chain the last run left on the device -- a run with storechain=True or with summary= -- over its steps from
+        ``burn`` on; the keywords are ``diagnostics.chain_diagnostics``'s.  No chain crosses the bus."""
+        from . import diagnostics
+        req = diagnostics._Request(burn, c, tol, method, nacf)
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: convergence() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset")
+        n = req.check_steps(self._resident)
+        ctx, h = self._handle()
+        raw = diagnostics._Raw(self.nsources, req.nacf)
+        spec, out = req.spec(), raw.out()
+        diagnostics._native_call(ctx.lib.mbb_sampler_diagnostics(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return diagnostics.ChainDiagnostics(req, raw, self.nsources > 1, self.k, n)
+
+    def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
+                 **unused):
         """N stretch-move steps from pos0 [nw, 5]; returns (pos, lnprob, rstate).
 
         summary=True, or a dict of ``results.chain_summary``'s keywords (percentile, burn, thin, derived, redshift,
         lumdist_mpc, kappa, kappa_wave, lir_range, peak_model, clip, percentiles): the chain of this run is
         summarised on the device and ``sampler.summary`` is the ``results.ChainSummary`` of it; with
         storechain=False no chain crosses the bus.  The chain stays on the device until the sampler's next run
-        (or reset), so that the summary can compute further percentiles on demand."""
+        (or reset), so that the summary can compute further percentiles on demand.
+
+        convergence=True, or a dict of ``convergence()``'s keywords: the chain of this run is diagnosed on the device
+        and ``sampler.convergence_`` is the ``diagnostics.ChainDiagnostics`` of it (None again after reset() and at the
+        start of the next run).  With storechain=False it needs summary= too: that is what keeps the chain of a run on
+        the device."""
+        creq = None
+        self.convergence_ = None
+        if convergence is not None and convergence is not False:
+            from . import diagnostics
+            ckw = {} if convergence is True else dict(convergence)
+            creq = diagnostics._Request(**ckw)
+            if not storechain and (summary is None or summary is False):
+                raise ValueError("convergence= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device")
+            creq.check_steps(int(N))
         ctx, h = self._handle()
+        if creq is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be diagnosed on the device: a rank holds only its own "
+                             "walkers' chain")
         req = None
         if summary is not None and summary is not False:
             if ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None):
@@ -163,6 +200,7 @@ class DeviceEnsembleSampler(object):
         lnprob = np.empty(lead)
         nacc = np.zeros(lead)
         fallbacks = ctx.info("flow_fallbacks")
+        self._resident = 0
         if self.summary is not None:
             self.summary.drop_chain()            # (the chain it could go back to is about to be overwritten)
             self.summary = None
@@ -200,9 +238,13 @@ class DeviceEnsembleSampler(object):
                 self._chain = np.concatenate((self._chain, chain), axis=ax)
                 self._lnprob = np.concatenate((self._lnprob, lnp), axis=ax)
         self._last = (pos, lnprob)
+        if (storechain or req is not None) and N > 0 and not (barrier or ctx.info("nranks") > 1):
+            self._resident = N
         if req is not None:
             self.summary = results.ChainSummary(self.lnprobfn, req, raw, self.nsources > 1, self._summarise_again,
                                                 self._summary_percentile)
+        if creq is not None:
+            self.convergence_ = self.convergence(creq.burn, creq.c, creq.tol, creq.method, creq.nacf)
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):

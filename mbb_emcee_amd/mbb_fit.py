@@ -137,10 +137,14 @@ class mbb_fitter(object):
                                                                 lo[worst], hi[worst]))
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
-    def run(self, nburn, nsteps, p0, verbose=False, summary=None):
+    def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
-        summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc)."""
+        summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc).
+        convergence (device sampler only): True or a dict of ``diagnostics.chain_diagnostics``'s keywords -- the main
+        chain's autocorrelation times, effective sample sizes and split R-hat, ``mbb_fitter.convergence``."""
+        if convergence is not None and convergence is not False and not hasattr(self.sampler, "convergence"):
+            raise ValueError("convergence= needs sampler=\"device\"")
         if summary is not None and summary is not False and not hasattr(self.sampler, "_summarise_again"):
             raise ValueError("summary= needs sampler=\"device\"")
         if not self.like.data_read:
@@ -174,10 +178,12 @@ class mbb_fitter(object):
                              "{:d}".format(nsteps))
         if verbose:
             print("  Doing main chain with {:d} steps".format(nsteps))
+        extra = {}
         if summary is not None and summary is not False:
-            self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, summary=summary)
-        else:
-            self.sampler.run_mcmc(pos, nsteps, rstate0=rstate)
+            extra["summary"] = summary
+        if convergence is not None and convergence is not False:
+            extra["convergence"] = convergence
+        self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, **extra)
         self._sampled = True
 
         if verbose:
@@ -213,6 +219,9 @@ for _name, _attr, _doc in (("noalpha", "_noalpha", "Not using the blue side powe
     setattr(mbb_fitter, _name, _view(_attr, _doc))
 mbb_fitter.summary = property(lambda self: getattr(self.sampler, "summary", None),
                               doc="results.ChainSummary of the main chain when run() was given summary=, else None")
+mbb_fitter.convergence = property(lambda self: getattr(self.sampler, "convergence_", None),
+                                  doc="diagnostics.ChainDiagnostics of the main chain when run() was given convergence=, "
+                                      "else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,
                                          doc="Is passband integration in use?")
 

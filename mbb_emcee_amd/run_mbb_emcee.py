@@ -42,6 +42,9 @@ def build_parser():
     p.add_argument("--summary", action="store_true",
                    help="summarise the chain on the device (means, 68.3%% and 95.4%% intervals, covariance, best fit; "
                         "with --get_peaklambda the peak wavelength too): printed, and added to the .npz")
+    p.add_argument("--convergence", action="store_true",
+                   help="diagnose the chain on the device (autocorrelation time, effective sample size, split R-hat "
+                        "per parameter; needs --sampler device): printed, and added to the .npz as convergence_*")
     p.add_argument("-v", "--verbose", action="store_true")
     for nm, dflt in zip(NAMES, (10.0, 2.0, 2500.0, 4.0, 40.0)):
         p.add_argument("--init" + nm, type=float, default=dflt)
@@ -85,7 +88,8 @@ def main(argv=None):
     summary = None
     if a.summary:
         summary = dict(percentile=(68.3, 95.4), derived=("peaklambda",) if a.get_peaklambda else ())
-    fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary)
+    extra = dict(convergence=True) if a.convergence else {}
+    fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary, **extra)
     chain, lnp = fit.sampler.chain, fit.sampler.lnprobability
     out = dict(chain=chain, lnprobability=lnp, acceptance_fraction=fit.sampler.acceptance_fraction,
                parnames=np.array(NAMES), noalpha=a.noalpha, opthin=a.opthin, wavenorm=a.wavenorm,
@@ -96,6 +100,9 @@ def main(argv=None):
     if a.summary:
         out.update(fit.summary.arrays())
         print(fit.summary)
+    if a.convergence:
+        out.update(fit.convergence.arrays())
+        print(fit.convergence)
     np.savez_compressed(a.outfile, **out)
     if a.verbose:
         flat = chain.reshape(-1, 5)
