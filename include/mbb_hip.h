@@ -183,7 +183,11 @@ int mbb_sampler_advance_timed(mbb_ctx *ctx, void *sampler, int nsteps, double st
  * [1e8 M_sun].  A column's samples are steps burn, burn + thin, ... of every walker.  Percentiles are numpy's
  * (method "linear") of EXACT order statistics; all sums are fixed-order trees, so a chain gives the same bits
  * every time.  Covariance (numpy.cov of the five parameters, ddof 1) and best fit are over the same window,
- * unclipped. */
+ * unclipped.
+ * L_IR and dust mass need a redshift and a luminosity distance: one of each for the whole call (redshift,
+ * lumdist_mpc -- what the reference has, one object per results file), or, for a catalogue of sources fitted in one
+ * launch, one per source (src_redshift, src_lumdist_mpc).  There is no cosmology here: distances are passed in.  No
+ * reference counterpart for the per-source form. */
 #define MBB_SUMMARY_COLS 8
 #define MBB_SUMMARY_MAX_PCT 8
 enum mbb_summary_derived { MBB_SUM_PEAK = 1, MBB_SUM_LIR = 2, MBB_SUM_DUSTMASS = 4 };
@@ -206,6 +210,15 @@ typedef struct mbb_summary_spec {
     double redshift, lumdist_mpc;          /* for L_IR and dust mass                                          */
     double kappa, kappa_wave;              /* dust mass (results.py:746: 2.64 m^2/kg at 125 um)               */
     double lir_wavemin, lir_wavemax;       /* rest-frame range of L_IR in um (results.py:627: 8, 1000)       */
+    /* A redshift and a luminosity distance per source, for a catalogue: host arrays [nsrc], both or neither (NULL:
+     * the two scalars above serve every source; exactly one NULL is MBB_ERR_ARG).  When given, the scalars are
+     * ignored and the L_IR and dust-mass columns of source s are computed with entry s.  An entry is finite with
+     * redshift > -1 and distance > 0, or NaN: unknown for this source, whose L_IR and dust-mass columns are then
+     * NaN in every cell (MBB_SUM_HAS_NAN, NaN mean and percentiles) while its other columns and all other sources
+     * are as ever.  Anything else is MBB_ERR_ARG, the message naming the first such source, before anything is
+     * allocated, uploaded or launched.  Looked at only when MBB_SUM_LIR or MBB_SUM_DUSTMASS is asked for; read
+     * during the call only.  Clip bounds, kappa, kappa_wave and the L_IR range stay one per call. */
+    double *src_redshift, *src_lumdist_mpc;
 } mbb_summary_spec;
 /* Where a summary goes; every pointer is the caller's, host memory, required. */
 typedef struct mbb_summary_out {

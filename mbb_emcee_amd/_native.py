@@ -32,7 +32,8 @@ class SummarySpec(C.Structure):
                 ("lo", C.c_double * SUMMARY_COLS), ("hi", C.c_double * SUMMARY_COLS),
                 ("redshift", C.c_double), ("lumdist_mpc", C.c_double),
                 ("kappa", C.c_double), ("kappa_wave", C.c_double),
-                ("lir_wavemin", C.c_double), ("lir_wavemax", C.c_double)]
+                ("lir_wavemin", C.c_double), ("lir_wavemax", C.c_double),
+                ("src_redshift", _dp), ("src_lumdist_mpc", _dp)]
 
 
 class SummaryOut(C.Structure):

@@ -267,8 +267,10 @@ struct mbb_ctx {
     // work buffers of the chain summary (summary_run): grown as needed, kept for the next call
     struct SumWork {
         void *part = nullptr, *state = nullptr, *hist = nullptr, *covpart = nullptr, *colstatus = nullptr,
-             *outbuf = nullptr, *der = nullptr;
-        size_t c_part = 0, c_state = 0, c_hist = 0, c_covpart = 0, c_colstatus = 0, c_outbuf = 0, c_der = 0;
+             *outbuf = nullptr, *der = nullptr, *src = nullptr;
+        size_t c_part = 0, c_state = 0, c_hist = 0, c_covpart = 0, c_colstatus = 0, c_outbuf = 0, c_der = 0, c_src = 0;
+        std::vector<mbbs::SrcConst> h_src;    // the per-source constants as uploaded (kept until the next call's)
+        bool src_in_flight = false;           // ... and whether that upload may still be reading them
     } sum;
     // ... and of the chain diagnostics (diag_run)
     struct DiagWork {
@@ -522,7 +524,7 @@ extern "C" void mbb_ctx_destroy(mbb_ctx *c)
     free_dev(c->d_sed_pars); free_dev(c->d_sed_out); free_dev(c->d_sed_status);
     free_dev(c->d_sed_wk);
     free_dev(c->sum.part); free_dev(c->sum.state); free_dev(c->sum.hist); free_dev(c->sum.covpart);
-    free_dev(c->sum.colstatus); free_dev(c->sum.outbuf); free_dev(c->sum.der);
+    free_dev(c->sum.colstatus); free_dev(c->sum.outbuf); free_dev(c->sum.der); free_dev(c->sum.src);
     free_dev(c->diag.mean); free_dev(c->diag.seq); free_dev(c->diag.outbuf);
     for (int i = 0; i < 2; ++i)
         if (c->ev_timed[i]) (void)hipEventDestroy(c->ev_timed[i]);
@@ -2188,11 +2190,36 @@ static int sum_grow(mbb_ctx *c, void **p, size_t *cap, size_t bytes)
 
 constexpr int kSumChunkRows = 1 << 18;      // chain rows a derived column is filled by at a time (bounds the WalkerK buffer)
 
+// What of L_IR and dust mass depends on redshift z and luminosity distance lumdist [Mpc], as postprocess.lir and
+// postprocess.dustmass form it: L_IR over observer-frame [wavemin, wavemax] (1 + z) with prefactor 4 pi Mpc^2 / L_sun
+// (results.py:661), the dust-mass constants of results.py:775-790.  One place, so that a source of a per-source call
+// and the same source summarised alone get the same bits.
+static mbbs::SrcConst summary_src_const(const mbb_ctx *c, const mbb_summary_spec *sp, double z, double lumdist)
+{
+    mbbs::SrcConst e;
+    const double opz = 1.0 + z;
+    const double minwave = std::min(sp->lir_wavemin, sp->lir_wavemax) * opz,
+                 maxwave = std::max(sp->lir_wavemin, sp->lir_wavemax) * opz;
+    e.numin = kUmToGHz / maxwave;
+    e.numax = kUmToGHz / minwave;
+    e.prefac = 3.11749657e4 * (lumdist * lumdist);
+    const double dl = lumdist * 3.0856775814913673e24;
+    const double wavenorm_rest = c->wavenorm / opz, nunorm_rest = 299792458e6 / wavenorm_rest;
+    e.opz = opz;
+    e.dl2 = dl * dl;
+    e.temp_fac = 6.6260693e-27 * nunorm_rest / 1.38065e-16;
+    e.bnu_fac = 2 * 6.6260693e-27 * (nunorm_rest * nunorm_rest * nunorm_rest) / (299792458e2 * 299792458e2);
+    e.knu_fac = wavenorm_rest / sp->kappa_wave;
+    return e;
+}
+
 // The derived columns of spec sp for the resident chain, into a.der[]: the SED kernels are fed the chain's own rows
 // (emcee's layout IS an array of 5-parameter rows), a chunk at a time.
 static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::SumArgs &a, size_t cells)
 {
     int rc, nder = 0;
+    const bool per_src = sp->src_redshift && (sp->derived & (MBB_SUM_LIR | MBB_SUM_DUSTMASS));
+    const long long per = (long long)a.nw * a.nsteps;      // rows per source
     for (int k = 0; k < 3; ++k) nder += (sp->derived >> k) & 1;
     if (!nder) return MBB_OK;
     if ((rc = sum_grow(c, &c->sum.der, &c->sum.c_der, (size_t)nder * cells * sizeof(double)))) return rc;
@@ -2203,7 +2230,32 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::Su
     const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
     if ((rc = ensure_sed(c, chunk, chunk * 6 + 2 * ngl))) return rc;
     double *d_gx = c->d_sed_out + chunk * 6, *d_gw = d_gx + ngl;
-    const double opz = 1.0 + sp->redshift;
+    // what depends on redshift and distance: one entry for the call, or a table with one per source
+    mbbs::SrcConst one = {};
+    mbbs::SrcConst *d_src = nullptr;
+    if (!per_src) {
+        if (der[1] || der[2]) one = summary_src_const(c, sp, sp->redshift, sp->lumdist_mpc);
+    } else {
+        std::vector<mbbs::SrcConst> &h = c->sum.h_src;
+        if ((rc = sum_grow(c, &c->sum.src, &c->sum.c_src, (size_t)a.nsrc * sizeof(mbbs::SrcConst)))) return rc;
+        // (h is the pageable source of the upload below: a call that returned early on an error may have left its
+        // copy in flight)
+        if (c->sum.src_in_flight) HIPCHK(hipStreamSynchronize(c->stream));
+        c->sum.src_in_flight = false;
+        h.resize((size_t)a.nsrc);
+        for (int s = 0; s < a.nsrc; ++s) {
+            const double z = sp->src_redshift[s], lumdist = sp->src_lumdist_mpc[s];
+            if (z != z || lumdist != lumdist) {             // unknown: every member NaN
+                mbbs::SrcConst &e = h[(size_t)s];
+                e.numin = e.numax = e.prefac = e.opz = e.dl2 = e.temp_fac = e.bnu_fac = e.knu_fac = NAN;
+            } else {
+                h[(size_t)s] = summary_src_const(c, sp, z, lumdist);
+            }
+        }
+        d_src = (mbbs::SrcConst *)c->sum.src;
+        c->sum.src_in_flight = true;
+        HIPCHK(hipMemcpyAsync(d_src, h.data(), (size_t)a.nsrc * sizeof(mbbs::SrcConst), hipMemcpyHostToDevice, c->stream));
+    }
     if (der[1]) {
         double gx[64], gw[64];
         gauss_legendre64(gx, gw);
@@ -2224,40 +2276,75 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::Su
             HIPCHK(hipGetLastError());
         }
         if (der[1]) {
-            // L_IR as postprocess.lir: observer-frame [wavemin, wavemax] (1 + z), prefactor 4 pi Mpc^2 / L_sun (results.py:661)
-            const double minwave = std::min(sp->lir_wavemin, sp->lir_wavemax) * opz,
-                         maxwave = std::max(sp->lir_wavemin, sp->lir_wavemax) * opz;
-            const double prefac = 3.11749657e4 * (sp->lumdist_mpc * sp->lumdist_mpc);
+            // L_IR as postprocess.lir (summary_src_const)
             if ((rc = launch_prologue(c, rows, n, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
             dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
-                hipLaunchKernelGGL((k_sed_integrate<decltype(OT)::value, decltype(NA)::value>), dim3(n), dim3(64), 0,
-                                   c->stream, c->d_sed_wk, kUmToGHz / maxwave, kUmToGHz / minwave, d_gx, d_gw, ngl, 8,
-                                   c->d_sed_out);
+                if (per_src)
+                    hipLaunchKernelGGL((k_sed_integrate_src<decltype(OT)::value, decltype(NA)::value>), dim3(n),
+                                       dim3(64), 0, c->stream, c->d_sed_wk, (const double *)d_src,
+                                       (int)(sizeof(mbbs::SrcConst) / sizeof(double)), (long long)off, per, d_gx, d_gw,
+                                       ngl, 8, c->d_sed_out);
+                else
+                    hipLaunchKernelGGL((k_sed_integrate<decltype(OT)::value, decltype(NA)::value>), dim3(n), dim3(64),
+                                       0, c->stream, c->d_sed_wk, one.numin, one.numax, d_gx, d_gw,
+                                       ngl, 8, c->d_sed_out);
             });
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(mbbs::k_sum_lir, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
-                               (const int32_t *)c->d_sed_status, n, (long long)off, prefac, der[1],
-                               (int *)c->sum.colstatus, a.nw, a.nsteps, a.burn, a.thin);
+            if (per_src)
+                hipLaunchKernelGGL(mbbs::k_sum_lir_src, dim3(grid), dim3(256), 0, c->stream,
+                                   (const double *)c->d_sed_out, (const int32_t *)c->d_sed_status, n, (long long)off,
+                                   (const mbbs::SrcConst *)d_src, der[1], (int *)c->sum.colstatus, a.nw, a.nsteps,
+                                   a.burn, a.thin);
+            else
+                hipLaunchKernelGGL(mbbs::k_sum_lir, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
+                                   (const int32_t *)c->d_sed_status, n, (long long)off, one.prefac, der[1],
+                                   (int *)c->sum.colstatus, a.nw, a.nsteps, a.burn, a.thin);
             HIPCHK(hipGetLastError());
         }
     }
     if (der[2]) {
-        // dust mass: the constants of results.py:775-790 as postprocess.dustmass forms them
+        // dust mass: the constants of results.py:775-790 (summary_src_const; k_sum_dustmass_src takes them per source)
         mbbs::DustArgs d;
-        const double dl = sp->lumdist_mpc * 3.0856775814913673e24;
-        const double wavenorm_rest = c->wavenorm / opz, nunorm_rest = 299792458e6 / wavenorm_rest;
-        d.opz = opz;
-        d.dl2 = dl * dl;
-        d.temp_fac = 6.6260693e-27 * nunorm_rest / 1.38065e-16;
-        d.bnu_fac = 2 * 6.6260693e-27 * (nunorm_rest * nunorm_rest * nunorm_rest) / (299792458e2 * 299792458e2);
-        d.knu_fac = wavenorm_rest / sp->kappa_wave;
+        d.opz = one.opz;
+        d.dl2 = one.dl2;
+        d.temp_fac = one.temp_fac;
+        d.bnu_fac = one.bnu_fac;
+        d.knu_fac = one.knu_fac;
         d.k10 = 10.0 * sp->kappa;
         d.msolar8 = 1.97792e41;
         d.wavenorm = c->wavenorm;
         d.opthin = c->opthin;
-        hipLaunchKernelGGL(mbbs::k_sum_dustmass, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream,
-                           a.chain, (long long)cells, d, der[2]);
+        if (per_src)
+            hipLaunchKernelGGL(mbbs::k_sum_dustmass_src, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream,
+                               a.chain, (long long)cells, per, (const mbbs::SrcConst *)d_src, d, der[2]);
+        else
+            hipLaunchKernelGGL(mbbs::k_sum_dustmass, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream,
+                               a.chain, (long long)cells, d, der[2]);
         HIPCHK(hipGetLastError());
+    }
+    return MBB_OK;
+}
+
+// The redshift and luminosity distance L_IR and dust mass are asked with: one of each for the call, or one per source
+// (then NaN is allowed: that source's are unknown).  Nothing is looked at when neither column is asked for.
+static int summary_check_cosmology(const mbb_summary_spec *sp, int nsrc)
+{
+    if (!(sp->derived & (MBB_SUM_LIR | MBB_SUM_DUSTMASS))) return MBB_OK;
+    if (!sp->src_redshift != !sp->src_lumdist_mpc)
+        return fail(MBB_ERR_ARG, "src_redshift and src_lumdist_mpc go together: both or neither");
+    if (!sp->src_redshift) {
+        if (!(sp->redshift > -1.0 && sp->redshift < INFINITY && sp->lumdist_mpc > 0.0 && sp->lumdist_mpc < INFINITY))
+            return fail(MBB_ERR_ARG, "L_IR and dust mass need a redshift and a luminosity distance");
+        return MBB_OK;
+    }
+    for (int s = 0; s < nsrc; ++s) {
+        const double z = sp->src_redshift[s], d = sp->src_lumdist_mpc[s];
+        const bool z_ok = z != z || (z > -1.0 && z < INFINITY), d_ok = d != d || (d > 0.0 && d < INFINITY);
+        if (z_ok && d_ok) continue;
+        char buf[160];
+        snprintf(buf, sizeof buf, "source %d: %s %g is neither NaN (unknown) nor %s", s,
+                 z_ok ? "luminosity distance" : "redshift", z_ok ? d : z, z_ok ? "finite and > 0" : "finite and > -1");
+        return fail(MBB_ERR_ARG, buf);
     }
     return MBB_OK;
 }
@@ -2279,9 +2366,8 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
         if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
     if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
     if (sp->derived & ~7) return fail(MBB_ERR_ARG, "unknown derived column");
-    if ((sp->derived & (MBB_SUM_LIR | MBB_SUM_DUSTMASS)) &&
-        !(sp->redshift > -1.0 && sp->redshift < INFINITY && sp->lumdist_mpc > 0.0 && sp->lumdist_mpc < INFINITY))
-        return fail(MBB_ERR_ARG, "L_IR and dust mass need a redshift and a luminosity distance");
+    int rc;
+    if ((rc = summary_check_cosmology(sp, nsrc))) return rc;
     if ((sp->derived & MBB_SUM_LIR) && !(sp->lir_wavemin > 0.0 && sp->lir_wavemax > 0.0))
         return fail(MBB_ERR_ARG, "wavelengths must be positive");
     if ((sp->derived & MBB_SUM_DUSTMASS) && !(sp->kappa > 0.0 && sp->kappa_wave > 0.0))
@@ -2308,7 +2394,6 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
     const size_t ncolumns = (size_t)nsrc * a.ncol;
     a.splits = ncolumns >= 1024 ? 1 : (int)std::min<long long>(kMaxSplits, (n + 16383) / 16384);
     a.per_split = (n + a.splits - 1) / a.splits;
-    int rc;
     mbb_ctx::SumWork &w = c->sum;
     const size_t np = (size_t)sp->npct;
     const size_t nd = (size_t)nsrc * (kCols * (3 + np) + 25 + 6);           // doubles of the result block
@@ -2347,6 +2432,7 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
     std::vector<char> host(out_bytes);
     HIPCHK(hipMemcpyAsync(host.data(), w.outbuf, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    w.src_in_flight = false;
     const char *hb = host.data();
     const size_t sc = (size_t)nsrc * kCols;
     memcpy(o->n_used, hb, sc * sizeof(long long));
@@ -2369,6 +2455,8 @@ extern "C" int mbb_chain_summary(mbb_ctx *c, const double *chain, const double *
     int rc = use(c);
     if (rc) return rc;
     if (!chain || !lnprob || nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "bad arguments");
+    // (per-source values are checked before the chain goes up; everything else where it always was, in summary_run)
+    if (spec && (spec->src_redshift || spec->src_lumdist_mpc) && (rc = summary_check_cosmology(spec, nsrc))) return rc;
     const size_t cells = (size_t)nsrc * nw * nsteps;
     double *d = nullptr;
     HIPCHK(hipMalloc((void **)&d, cells * 6 * sizeof(double)));
@@ -2395,6 +2483,8 @@ extern "C" int mbb_sampler_run_summary(mbb_ctx *c, void *sp, int nsteps, double 
     if (p.collective)
         return fail(MBB_ERR_STATE, "a sharded sampler run cannot be summarised on the device: a rank holds only its own "
                                    "walkers' chain");
+    // (per-source values are checked before the run; everything else where it always was, in summary_run)
+    if ((spec->src_redshift || spec->src_lumdist_mpc) && (rc = summary_check_cosmology(spec, s->nsrc))) return rc;
     if (nsteps == 0) {
         if (s->resident_nsteps <= 0)
             return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");

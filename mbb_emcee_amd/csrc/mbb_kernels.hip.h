@@ -4,7 +4,7 @@
 //                half-step): n calls of likelihood.__call__ (likelihood.py:790-834)
 // k_prologue     modified_blackbody.__init__ + max_wave for n rows
 // k_sed_eval     f_nu on a frequency grid for n rows
-// k_sed_integrate  freq_integrate for n rows
+// k_sed_integrate  freq_integrate for n rows (k_sed_integrate_src: bounds per source of a chain)
 // k_fnu_explicit fnu.pyx's four functions with explicit scalars
 //
 // Included by mbb_hip.hip (the C-ABI / host side) and mbb_flow.hip (the one-launch kernels).
@@ -1484,47 +1484,71 @@ __global__ void k_sed_eval(const WalkerK *wk, const double *freq, int m, double 
     out[(size_t)blockIdx.y * m + i] = r;
 }
 
-// freq_integrate (modified_blackbody.py:639-674) for row blockIdx.x: the integral of
+// freq_integrate (modified_blackbody.py:639-674) for one row: the integral of
 // f_nu over [numin, numax] (GHz), in mJy GHz.  The reference calls scipy's adaptive
 // quad; here the integral is taken in t = log(nu), split at the merge frequency
 // and at nu0, each piece cut into npanel panels with an ngl-point Gauss-Legendre
 // rule: one node per lane, one wave per row.
 template <bool OPTHIN, bool NOALPHA>
+__device__ __forceinline__ double sed_integrate_row(const WalkerK &k, double numin, double numax, const double *glx,
+                                                    const double *glw, int ngl, int npanel, int lane)
+{
+    if (k.status != ROW_OK) return __builtin_nan("");
+    const double t0 = m_log(numin), t1 = m_log(numax);
+    // break points in t = log nu: the merge frequency (f_nu is only C1 there) and,
+    // for the optically thick model, nu0 (for large beta the optical-depth factor
+    // is nearly a step there)
+    double tm = t1, tz = t0;
+    if (!NOALPHA) tm = fmin(fmax(m_log(k.xmerge) - k.lhokt9, t0), t1);
+    if (!OPTHIN) tz = fmin(fmax(k.lx0 - k.lhokt9, t0), tm);
+    const double edge[4] = {t0, tz, tm, t1};
+    double acc = 0.0;
+    for (int piece = 0; piece < 3; ++piece) {
+        const double a = edge[piece], b = edge[piece + 1];
+        if (!(b > a)) continue;
+        // keep a node that rounds across the merge point on its own side
+        WalkerK kk = k;
+        if (!NOALPHA) kk.xmerge = (piece == 2) ? 0.0 : __builtin_inf();
+        const double pw = (b - a) / npanel, half = 0.5 * pw;
+        for (int pn = 0; pn < npanel; ++pn) {
+            const double mid = fma(pn + 0.5, pw, a);
+            for (int i = lane; i < ngl; i += 64) {
+                const double t = fma(half, glx[i], mid);
+                const double nu = m_exp(t);
+                acc = fma(fnu_sample<OPTHIN, NOALPHA>(kk, nu, t) * nu, half * glw[i], acc);
+            }
+        }
+    }
+    return wave_sum(acc);
+}
+
+// ... for n rows, row blockIdx.x, all over the same [numin, numax]
+template <bool OPTHIN, bool NOALPHA>
 __global__ void k_sed_integrate(const WalkerK *wk, double numin, double numax, const double *glx,
                                 const double *glw, int ngl, int npanel, double *out)
 {
     const WalkerK k = wk[blockIdx.x];
-    const int lane = threadIdx.x;
+    const double total = sed_integrate_row<OPTHIN, NOALPHA>(k, numin, numax, glx, glw, ngl, npanel, threadIdx.x);
+    if (threadIdx.x == 0) out[blockIdx.x] = total;
+}
+
+// ... for rows off .. off + n - 1 of a chain of sources with per_src rows each: row blockIdx.x is of source
+// (off + blockIdx.x) / per_src and takes its bounds from that source's entry of a table of `stride` doubles per
+// source, numin first, numax second.  A NaN numin marks a source whose bounds are unknown: NaN, no integral (the
+// fmin / fmax of the break points would swallow a NaN bound and give a finite number).
+template <bool OPTHIN, bool NOALPHA>
+__global__ void k_sed_integrate_src(const WalkerK *wk, const double *bounds, int stride, long long off,
+                                    long long per_src, const double *glx, const double *glw, int ngl, int npanel,
+                                    double *out)
+{
+    const double *b = bounds + (size_t)((off + (long long)blockIdx.x) / per_src) * stride;
+    const double numin = b[0], numax = b[1];
     double total = __builtin_nan("");
-    if (k.status == ROW_OK) {
-        const double t0 = m_log(numin), t1 = m_log(numax);
-        // break points in t = log nu: the merge frequency (f_nu is only C1 there) and,
-        // for the optically thick model, nu0 (for large beta the optical-depth factor
-        // is nearly a step there)
-        double tm = t1, tz = t0;
-        if (!NOALPHA) tm = fmin(fmax(m_log(k.xmerge) - k.lhokt9, t0), t1);
-        if (!OPTHIN) tz = fmin(fmax(k.lx0 - k.lhokt9, t0), tm);
-        const double edge[4] = {t0, tz, tm, t1};
-        double acc = 0.0;
-        for (int piece = 0; piece < 3; ++piece) {
-            const double a = edge[piece], b = edge[piece + 1];
-            if (!(b > a)) continue;
-            // keep a node that rounds across the merge point on its own side
-            WalkerK kk = k;
-            if (!NOALPHA) kk.xmerge = (piece == 2) ? 0.0 : __builtin_inf();
-            const double pw = (b - a) / npanel, half = 0.5 * pw;
-            for (int pn = 0; pn < npanel; ++pn) {
-                const double mid = fma(pn + 0.5, pw, a);
-                for (int i = lane; i < ngl; i += 64) {
-                    const double t = fma(half, glx[i], mid);
-                    const double nu = m_exp(t);
-                    acc = fma(fnu_sample<OPTHIN, NOALPHA>(kk, nu, t) * nu, half * glw[i], acc);
-                }
-            }
-        }
-        total = wave_sum(acc);
+    if (numin == numin) {
+        const WalkerK k = wk[blockIdx.x];
+        total = sed_integrate_row<OPTHIN, NOALPHA>(k, numin, numax, glx, glw, ngl, npanel, threadIdx.x);
     }
-    if (lane == 0) out[blockIdx.x] = total;
+    if (threadIdx.x == 0) out[blockIdx.x] = total;
 }
 
 // fnu.pyx:9-108 with explicit scalars

@@ -19,6 +19,7 @@
 //   k_sum_cov     per source and split: 15 sums of products about the mean, and the best sample
 //   k_sum_finish  interpolates the percentiles as numpy does, writes every output
 //   k_sum_take / k_sum_lir / k_sum_dustmass   fill the derived columns from the SED kernels' outputs
+//   k_sum_lir_src / k_sum_dustmass_src        ... with a redshift and a luminosity distance per source (SrcConst)
 // Eight radix passes over the order-preserving 64-bit image of the doubles select every rank at
 // once.  All floating-point sums are fixed-order trees (eight interleaved partial sums per thread,
 // a binary tree over the threads in LDS, a binary tree over the splits): the same chain gives the
@@ -468,21 +469,56 @@ __global__ void k_sum_lir(const double *integ, const int32_t *status, int n, lon
     note_status(colstatus, 6, off + i, status[i], nw, nsteps, burn, thin);
 }
 
+// What of L_IR and dust mass depends on a source's redshift and luminosity distance (mbb_summary_spec's src_redshift /
+// src_lumdist_mpc): the bounds of the L_IR integral in GHz and its prefactor, and DustArgs' members of the same names.
+// summary_fill_derived forms one entry per source on the host, in the scalar path's own expressions.  An entry of NaNs
+// is a source whose redshift or distance is unknown: its L_IR and dust mass are NaN in every cell.
+struct SrcConst { double numin, numax, prefac, opz, dl2, temp_fac, bnu_fac, knu_fac; };
+
+// ... with the prefactor of the row's source, (off + i) / (nw * nsteps).  An unknown source gets its NaN written here,
+// whatever the integral's slot holds, and its rows' status is not looked at.
+__global__ void k_sum_lir_src(const double *integ, const int32_t *status, int n, long long off, const SrcConst *src,
+                              double *col, int *colstatus, int nw, int nsteps, int burn, int thin)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double prefac = src[(off + i) / ((long long)nw * nsteps)].prefac;
+    if (prefac != prefac) { col[off + i] = __builtin_nan(""); return; }
+    col[off + i] = prefac * (1e-17 * integ[i]);
+    note_status(colstatus, 6, off + i, status[i], nw, nsteps, burn, thin);
+}
+
 // dust mass in 1e8 solar masses: the closed form of results.py:726-801 (postprocess.dustmass) per chain row
 struct DustArgs { double opz, dl2, temp_fac, bnu_fac, knu_fac, k10, msolar8, wavenorm; int opthin; };
-__global__ void k_sum_dustmass(const double *chain, long long n, DustArgs d, double *col)
+__device__ __forceinline__ double dustmass_row(const double *row, const DustArgs &d)
 {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double T = chain[i * 5 + 0] * d.opz, beta = chain[i * 5 + 1], S = chain[i * 5 + 4] * 1e-26;
+    const double T = row[0] * d.opz, beta = row[1], S = row[4] * 1e-26;
     const double B = d.bnu_fac / expm1(d.temp_fac / T);
     const double K = d.k10 * pow(d.knu_fac, -beta);
     double m = d.dl2 * S / (d.opz * K * B * d.msolar8);
     if (!d.opthin) {
-        const double tau = pow(chain[i * 5 + 2] / d.wavenorm, beta);
+        const double tau = pow(row[2] / d.wavenorm, beta);
         m = m * (-tau / expm1(-tau));
     }
-    col[i] = m;
+    return m;
+}
+__global__ void k_sum_dustmass(const double *chain, long long n, DustArgs d, double *col)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    col[i] = dustmass_row(chain + i * 5, d);
+}
+
+// ... with the redshift-dependent members of d taken from the row's source, i / per_src
+__global__ void k_sum_dustmass_src(const double *chain, long long n, long long per_src, const SrcConst *src, DustArgs d,
+                                   double *col)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const SrcConst s = src[i / per_src];
+    if (s.opz != s.opz) { col[i] = __builtin_nan(""); return; }
+    d.opz = s.opz; d.dl2 = s.dl2; d.temp_fac = s.temp_fac; d.bnu_fac = s.bnu_fac; d.knu_fac = s.knu_fac;
+    col[i] = dustmass_row(chain + i * 5, d);
 }
 
 }   // namespace mbbs

@@ -134,7 +134,8 @@ class DeviceEnsembleSampler(object):
         """N stretch-move steps from pos0 [nw, 5]; returns (pos, lnprob, rstate).
 
         summary=True, or a dict of ``results.chain_summary``'s keywords (percentile, burn, thin, derived, redshift,
-        lumdist_mpc, kappa, kappa_wave, lir_range, peak_model, clip, percentiles): the chain of this run is
+        lumdist_mpc -- a number each or one entry per source --, kappa, kappa_wave, lir_range, peak_model, clip,
+        percentiles): the chain of this run is
         summarised on the device and ``sampler.summary`` is the ``results.ChainSummary`` of it; with
         storechain=False no chain crosses the bus.  The chain stays on the device until the sampler's next run
         (or reset), so that the summary can compute further percentiles on demand.
@@ -255,7 +256,7 @@ class DeviceEnsembleSampler(object):
             if q not in qs:
                 qs.append(q)
         self._summary_percentile = cens[0]
-        req = results._Request(qs, **kw)
+        req = results._Request(qs, nsources=self.nsources, **kw)
         if nsteps < 1 or req.burn >= nsteps:
             raise ValueError("burn leaves no step of the chain")
         return req

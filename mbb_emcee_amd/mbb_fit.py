@@ -140,7 +140,8 @@ class mbb_fitter(object):
     def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
-        summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc).
+        summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
+        (``set_phot_multi``) its ``redshift`` and ``lumdist_mpc`` may be arrays with one entry per source.
         convergence (device sampler only): True or a dict of ``diagnostics.chain_diagnostics``'s keywords -- the main
         chain's autocorrelation times, effective sample sizes and split R-hat, ``mbb_fitter.convergence``."""
         if convergence is not None and convergence is not False and not hasattr(self.sampler, "convergence"):
@@ -157,10 +158,10 @@ class mbb_fitter(object):
         for i in range(5):
             if (i == 2 and self._opthin) or (i == 3 and self._noalpha):
                 continue
-            if self.has_uplim(i) and p0[:, i].max() > self.uplim(i):
+            if self.has_uplim(i) and p0[..., i].max() > self.uplim(i):
                 raise ValueError("Upper limit initial value violation for "
                                  "{:s}".format(self._parnames[i]))
-            if p0[:, i].min() < self.lowlim(i):
+            if p0[..., i].min() < self.lowlim(i):
                 raise ValueError("Lower limit initial value violation for "
                                  "{:s}".format(self._parnames[i]))
 

@@ -10,7 +10,10 @@ or ``mbb_sampler_run_summary`` (the chain of a ``DeviceEnsembleSampler`` run, wh
 the device).  Percentiles are numpy's default ("linear") of exact order statistics.
 
 HDF5, astropy and the cosmology stay out of scope, as in ``postprocess``: pass the luminosity
-distance in.
+distance in.  For a catalogue (a multi-source chain) ``redshift`` and ``lumdist_mpc`` may each be an
+array with one entry per source; NaN marks a source whose value is unknown, and its L_IR and dust
+mass are NaN.  Clip bounds, ``kappa`` / ``kappa_wave`` and ``lir_range`` stay one per call, and
+``postprocess.lir`` / ``postprocess.dustmass`` stay scalar.
 """
 import ctypes as C
 
@@ -58,7 +61,7 @@ class _Request(object):
     """What one native summary call is asked for (mbb_summary_spec)."""
 
     def __init__(self, qs, burn=0, thin=1, clip=None, derived=(), redshift=None, lumdist_mpc=None, kappa=2.64,
-                 kappa_wave=125.0, lir_range=(8.0, 1000.0), peak_model="fit"):
+                 kappa_wave=125.0, lir_range=(8.0, 1000.0), peak_model="fit", nsources=1):
         self.qs = [float(q) for q in qs]
         if not 1 <= len(self.qs) <= _native.SUMMARY_MAX_PCT:
             raise ValueError("a summary call takes 1 to {:d} percentiles".format(_native.SUMMARY_MAX_PCT))
@@ -83,8 +86,23 @@ class _Request(object):
         self.peak_model = peak_model
         if ("lir" in self.derived or "dustmass" in self.derived) and (redshift is None or lumdist_mpc is None):
             raise ValueError("L_IR and dust mass need redshift and lumdist_mpc")
-        self.redshift = 0.0 if redshift is None else float(redshift)
-        self.lumdist_mpc = 0.0 if lumdist_mpc is None else float(lumdist_mpc)
+        # one value for the call (as the reference has it), or one per source: then both go to the library as arrays
+        # [nsources] (a scalar beside an array is broadcast), which live as long as this request and its copies
+        self.nsources = int(nsources)
+        z, d = [None if v is None else np.asarray(v, dtype=np.float64) for v in (redshift, lumdist_mpc)]
+        for name, v in (("redshift", z), ("lumdist_mpc", d)):
+            if v is not None and v.ndim and v.shape != (self.nsources,):
+                raise ValueError("{} must be a number or a 1-d array with one entry per source ({:d}), not of shape "
+                                 "{}".format(name, self.nsources, v.shape))
+        self.src_redshift = self.src_lumdist_mpc = None
+        if z is not None and d is not None and (z.ndim or d.ndim):
+            self.src_redshift, self.src_lumdist_mpc = [np.ascontiguousarray(np.broadcast_to(v, (self.nsources,))).copy()
+                                                       for v in (z, d)]
+            self.src_redshift.setflags(write=False)
+            self.src_lumdist_mpc.setflags(write=False)
+            z = d = None
+        self.redshift = 0.0 if z is None or z.ndim else float(z)
+        self.lumdist_mpc = 0.0 if d is None or d.ndim else float(d)
         self.kappa, self.kappa_wave = float(kappa), float(kappa_wave)
         if self.kappa <= 0 or self.kappa_wave <= 0:
             raise ValueError("kappa and kappa_wave must be positive")
@@ -116,7 +134,16 @@ class _Request(object):
         s.redshift, s.lumdist_mpc = self.redshift, self.lumdist_mpc
         s.kappa, s.kappa_wave = self.kappa, self.kappa_wave
         s.lir_wavemin, s.lir_wavemax = self.lir_range
+        if self.src_redshift is not None:
+            # (the addresses of this request's own arrays: the request outlives the call the spec is made for)
+            s.src_redshift, s.src_lumdist_mpc = _native._d(self.src_redshift), _native._d(self.src_lumdist_mpc)
         return s
+
+    def cosmology(self):
+        """(redshift, lumdist_mpc) as used: arrays [nsources] if given per source, else the two numbers."""
+        if self.src_redshift is not None:
+            return self.src_redshift, self.src_lumdist_mpc
+        return self.redshift, self.lumdist_mpc
 
 
 class _Raw(object):
@@ -173,6 +200,9 @@ def chain_summary(like, chain, lnprob, percentile=68.3, burn=0, thin=1, derived=
     burn, thin : the steps used, ``chain[:, burn::thin]``.
     derived : any of "peaklambda", "lir", "dustmass" (the latter two need ``redshift`` and ``lumdist_mpc``);
     peak_model as ``postprocess.peak_wavelength``'s ``model``.
+    redshift, lumdist_mpc : a number each, or a 1-d array with one entry per source of the chain (length 1 for a
+    [nw, nsteps, 5] chain); a number beside an array serves every source.  A NaN entry marks a source whose value is
+    unknown: its L_IR and dust mass are NaN (status ``SUM_HAS_NAN``), everything else is unaffected.
     clip : ``{param or derived name: (lowlim, uplim)}`` applied as ``_parcen_internal`` does (either may be None).
     keep : keep the chain with the result, so that other percentiles and clip bounds can be computed on demand."""
     chain = np.ascontiguousarray(chain, dtype=np.float64)
@@ -195,7 +225,8 @@ def chain_summary(like, chain, lnprob, percentile=68.3, burn=0, thin=1, derived=
     for q in percentiles:
         if float(q) not in qs:
             qs.append(float(q))
-    req = _Request(qs, burn, thin, clip, derived, redshift, lumdist_mpc, kappa, kappa_wave, lir_range, peak_model)
+    req = _Request(qs, burn, thin, clip, derived, redshift, lumdist_mpc, kappa, kappa_wave, lir_range, peak_model,
+                   nsources=c4.shape[0])
     raw = _summarise_host(like, c4, l3, req)
     again = (lambda r: _summarise_host(like, c4, l3, r)) if keep else None
     return ChainSummary(like, req, raw, multi, again, cens[0])
@@ -246,10 +277,14 @@ class ChainSummary(object):
         failing SED row as ``postprocess`` raises it for the same chain -- when ANY source's column met that inside
         the burn / thin window, also for the sources whose own column is fine (``status`` says which those are, and
         ``mean`` / ``percentiles`` hold their numbers).  Rows outside the window never count; a NaN parameter gives NaN
-        and does not raise."""
+        and does not raise.  Nor does a source whose redshift or distance was given as NaN: its L_IR and dust mass are
+        NaN rows (also when a clip leaves that source's column empty)."""
         qs = list(_pval(percentile))
         raw, idx = self._lookup(slot, qs, lowlim, uplim)
-        if np.any(raw.status[:, slot] & _native.SUM_EMPTY):
+        empty = (raw.status[:, slot] & _native.SUM_EMPTY) != 0
+        if slot in (6, 7) and self._req.src_redshift is not None:
+            empty &= ~(np.isnan(self._req.src_redshift) | np.isnan(self._req.src_lumdist_mpc))
+        if np.any(empty):
             raise Exception(_NO_SURVIVORS)
         _native.raise_for_status(self._row_status(raw, slot))
         mn = raw.mean[:, slot]
@@ -356,7 +391,13 @@ class ChainSummary(object):
     def arrays(self, prefix="summary_"):
         """The summary as plain arrays (for an .npz)."""
         qs, pct = self.percentiles
-        return {prefix + "n_used": self.n_used, prefix + "mean": self.mean, prefix + "min": self.min,
+        extra = {}
+        if "lir" in self._req.derived or "dustmass" in self._req.derived:
+            z, d = self._req.cosmology()
+            nsrc = (self._raw.mean.shape[0],)
+            extra = {prefix + "redshift": np.array(self._squeeze(np.broadcast_to(z, nsrc))),
+                     prefix + "lumdist_mpc": np.array(self._squeeze(np.broadcast_to(d, nsrc)))}
+        return {**extra, prefix + "n_used": self.n_used, prefix + "mean": self.mean, prefix + "min": self.min,
                 prefix + "max": self.max, prefix + "q": np.array(qs), prefix + "percentiles": pct,
                 prefix + "covariance": self.covariance, prefix + "best_fit": self._squeeze(self._raw.best[:, :5]).copy(),
                 prefix + "best_fit_lnprob": self._squeeze(self._raw.best[:, 5]).copy(),
