@@ -16,7 +16,41 @@ import numpy as np
 from . import _native
 from .ensemble import integrated_time
 
-__all__ = ["DeviceEnsembleSampler"]
+__all__ = ["DeviceEnsembleSampler", "accepted_by_step"]
+
+
+def accepted_by_step(cur, steps, own_rows=None):
+    """Every walker's accepted moves after each of a run's steps, rebuilt from its positions: ``cur`` [..., nw, 5] is
+    the ensemble before the run, ``steps`` [..., nw, k, 5] the run's chain; the result [..., nw, k] is cumulative.  A
+    stretch move that is accepted changes the walker's position, one that is refused leaves every bit of it.
+    ``own_rows`` (a boolean mask over the walkers, or their indices): the walkers whose chain this rank holds -- with
+    the one-hop exchange the other rows of a rank's chain are zeros, which say nothing about a move, and stay 0."""
+    cur, steps = np.asarray(cur, dtype=np.float64), np.asarray(steps, dtype=np.float64)
+    if steps.shape[-2] == 0:
+        return np.zeros(steps.shape[:-1], dtype=np.int64)
+    prev = np.concatenate((cur[..., None, :], steps[..., :-1, :]), axis=-2)
+    moved = np.any(steps != prev, axis=-1)
+    if own_rows is not None:
+        own = np.zeros(steps.shape[-3], dtype=bool)
+        own[np.asarray(own_rows)] = True
+        moved = moved & own[:, None]
+    return np.cumsum(moved, axis=-1)
+
+
+def _own_rows(nw, rank, nranks):
+    """The walkers rank ``rank`` of ``nranks`` moves in a sharded run, as a mask: its block of either half."""
+    from .parallel import block_bounds
+    half = nw // 2
+    lo, hi = block_bounds(half, nranks)[1][rank]
+    own = np.zeros(nw, dtype=bool)
+    own[lo:hi] = own[half + lo:half + hi] = True
+    return own
+
+
+class _OpenSample(object):
+    """What a suspended sample() generator has to leave behind when it ends or is retired."""
+    __slots__ = ("live", "it_prev", "n_prev", "made", "acc_made", "storechain", "big_c", "big_l", "kept_c", "kept_l",
+                 "single")
 
 
 class DeviceEnsembleSampler(object):
@@ -43,6 +77,7 @@ class DeviceEnsembleSampler(object):
         self._h = None
         self._ctx = None
         self._ns = 1
+        self._open = None                     # the state of the sample() generator that is suspended, if one is
         self.reset()
 
     @property
@@ -62,6 +97,14 @@ class DeviceEnsembleSampler(object):
         return ctx, self._h
 
     def reset(self):
+        """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
+        shape, ``iterations`` 0, no ``summary`` and no ``convergence_``, nothing resident for ``convergence()``, and no
+        state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
+        random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
+        ``pos, lnp, _ = s.run_mcmc(p0, nburn); s.reset(); s.run_mcmc(pos, n, lnprob0=lnp)`` -- emcee's burn-in idiom --
+        makes bit for bit the steps ``s.run_mcmc(p0, nburn + n)`` makes.  A sample() generator that is still suspended
+        is retired first (see run_mcmc)."""
+        self._retire()
         ns = self.nsources
         lead = (ns, self.k) if ns > 1 else (self.k,)
         self.naccepted = np.zeros(lead)
@@ -131,7 +174,22 @@ class DeviceEnsembleSampler(object):
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
                  **unused):
-        """N stretch-move steps from pos0 [nw, 5]; returns (pos, lnprob, rstate).
+        """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
+
+        One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
+        ``pos0`` / ``p0`` None walk one trajectory -- that of a single ``run_mcmc(p0, T)`` of a fresh sampler with the
+        same seed, bit for bit -- however the steps are grouped into calls, whatever sample()'s chunk and whatever
+        ``storechain``.
+
+        ``lnprob0`` (with ``pos0``; ignored without): the log-probabilities of ``pos0``, taken as given and not
+        computed again.  Exactly the ensemble's leading shape, (nw,) or (nsources, nw): anything else is a ValueError,
+        and so is a NaN; -inf and +inf are legal (a walker at -inf leaves at its first finite proposal, one at +inf
+        never moves).
+
+        A sample() generator of this sampler that is still suspended is retired first: ``chain``, ``lnprobability``,
+        ``iterations`` and ``naccepted`` are brought to the end of the chunk the device had made for it, as closing it
+        would, and this run goes on from there.  The retired generator raises RuntimeError when it is resumed and
+        changes nothing when it is closed or collected.  reset() and another sample() do the same.
 
         summary=True, or a dict of ``results.chain_summary``'s keywords (percentile, burn, thin, derived, redshift,
         lumdist_mpc -- a number each or one entry per source --, kappa, kappa_wave, lir_range, peak_model, clip,
@@ -144,6 +202,27 @@ class DeviceEnsembleSampler(object):
         and ``sampler.convergence_`` is the ``diagnostics.ChainDiagnostics`` of it (None again after reset() and at the
         start of the next run).  With storechain=False it needs summary= too: that is what keeps the chain of a run on
         the device."""
+        self._retire()
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence)
+
+    def _retire(self):
+        """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
+        st, self._open = getattr(self, "_open", None), None
+        if st is not None and st.live:
+            st.live = False
+            self._leave(st)
+
+    def _leave(self, st):
+        # the device made the whole chunk and run_mcmc(None, n) goes on from its end: the attributes show all of it
+        self.iterations, self.naccepted = st.it_prev + st.made, st.acc_made
+        if st.storechain:
+            self._chain, self._lnprob = st.big_c[..., :st.n_prev + st.made, :], st.big_l[..., :st.n_prev + st.made]
+        else:
+            self._chain, self._lnprob = st.kept_c, st.kept_l
+        if not st.single:
+            self._resident = 0                # (what is resident is the last chunk: a part)
+
+    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None):
         creq = None
         self.convergence_ = None
         if convergence is not None and convergence is not False:
@@ -183,6 +262,12 @@ class DeviceEnsembleSampler(object):
             if np.any(np.isnan(p0)):
                 raise ValueError("At least one parameter value was NaN.")
             l0 = None if lnprob0 is None else np.ascontiguousarray(lnprob0, dtype=np.float64)
+            if l0 is not None:
+                # (the native side reads nsources * nw doubles from it and takes them as they are)
+                if l0.shape != want[:-1]:
+                    raise ValueError("lnprob0 must have shape {}".format(want[:-1]))
+                if np.any(np.isnan(l0)):
+                    raise ValueError("The initial lnprob was NaN.")
             try:
                 _native._check(ctx.lib.mbb_sampler_set_state(
                     ctx.h, h, _native._d(p0), _native._d(l0) if l0 is not None else None))
@@ -276,63 +361,104 @@ class DeviceEnsembleSampler(object):
     def sample(self, p0, lnprob0=None, rstate0=None, iterations=1, storechain=True, chunk=64):
         """emcee's generator form (``for pos, lnprob, rstate in sampler.sample(p0, iterations=N)``): the ensemble after
         every step.  The steps are made ``chunk`` at a time in one launch on the device -- a launch has a fixed cost of
-        ~20 us beside ~6 us per step -- and handed out one by one.  The chain is run_mcmc(p0, iterations)'s whatever the
-        chunk: a step's draws are keyed by its number in the sampler's life, not by its place in a launch.  While step j is
-        out, ``chain``, ``lnprobability``, ``iterations`` and ``naccepted`` are those of the steps handed out so far -- as
-        with emcee, where a step exists only once it has been yielded -- although the device is up to ``chunk`` - 1 steps
-        ahead; breaking out of the loop early leaves the sampler at the end of the chunk it was in (``run_mcmc(None, n)``
-        goes on from there, and the attributes then show that whole chunk).  ``rstate0`` is accepted for emcee's call
-        convention and ignored: the random stream is the sampler's ``seed`` (Philox, counted by step and row)."""
-        iterations, chunk = int(iterations), max(1, int(chunk))
+        ~20 us beside ~6 us per step -- and handed out one by one.  ``rstate0`` is accepted for emcee's call
+        convention and ignored: the random stream is the sampler's ``seed`` (Philox, counted by step and row).
+
+        One trajectory.  The chain is run_mcmc(p0, iterations)'s whatever the chunk and whatever ``storechain``: a
+        step's draws are keyed by its number in the sampler's life, not by its place in a launch; with ``p0`` None
+        the call goes on where the last run or sample() left the device (run_mcmc's docstring).
+
+        While step j is out, ``chain``, ``lnprobability``, ``iterations``, ``naccepted`` and ``acceptance_fraction``
+        are those after the steps handed out so far -- as with emcee, where a step exists only once it has been yielded
+        -- although the device is up to ``chunk`` - 1 steps ahead.  That holds on top of a chain stored before, and with
+        ``storechain=False``, where ``chain`` stays what it was.  On a sampler sharded with the one-hop exchange the
+        per-step ``naccepted`` counts this rank's walkers only; the other rows stay 0, as the chain does there.
+
+        Leaving early (``break``, ``close()``) leaves the sampler at the end of the chunk the device made:
+        ``run_mcmc(None, n)`` goes on from there, and the attributes then show that whole chunk.
+
+        run_mcmc, reset or another sample() on a sampler whose generator is still suspended retire that generator
+        first: the attributes go to the end of the chunk the device made, exactly as closing it would, and the call
+        proceeds.  The retired generator raises RuntimeError when it is resumed and changes nothing when it is closed
+        or collected.
+
+        ``lnprob0`` is run_mcmc's (exact shape, no NaN, taken as given) and applies to the first chunk only.  What
+        run_mcmc refuses -- a wrong shape, NaN or inf in ``p0``, ``p0`` None without a state -- sample() refuses at
+        the first ``next()``; ``iterations=0`` sets the state as ``run_mcmc(p0, 0)`` does and yields nothing.
+
+        Afterwards ``summary`` and ``convergence_`` are None.  ``convergence()`` describes all the steps this call
+        made where the whole run was one chunk (``iterations`` <= ``chunk``), which is then resident on the device;
+        otherwise it raises its "no chain of this sampler is resident" ValueError: it never describes a part."""
+        self._retire()
+        return self._sample(p0, lnprob0, max(0, int(iterations)), bool(storechain), max(1, int(chunk)))
+
+    def _sample(self, p0, lnprob0, iterations, storechain, chunk):
+        self._retire()                        # (one that was begun between the call and this first next())
         ax = 1 if self.nsources == 1 else 2
-        kept_c, kept_l = self._chain, self._lnprob
-        n_prev = kept_c.shape[ax]
-        it_prev = self.iterations
+        st = _OpenSample()
+        st.live, st.storechain, st.single = True, storechain, iterations <= chunk
+        st.kept_c, st.kept_l = self._chain, self._lnprob
+        n_prev = st.n_prev = st.kept_c.shape[ax]
+        it_prev = st.it_prev = self.iterations
+        st.big_c = st.big_l = None
         if storechain:
             # (room for the whole run once, filled chunk by chunk: no chain is copied more than that)
-            big_c = np.empty(kept_c.shape[:ax] + (n_prev + iterations, self.dim))
-            big_l = np.empty(kept_l.shape[:ax] + (n_prev + iterations,))
-            big_c[..., :n_prev, :] = kept_c
-            big_l[..., :n_prev] = kept_l
+            st.big_c = np.empty(st.kept_c.shape[:ax] + (n_prev + iterations, self.dim))
+            st.big_l = np.empty(st.kept_l.shape[:ax] + (n_prev + iterations,))
+            st.big_c[..., :n_prev, :] = st.kept_c
+            st.big_l[..., :n_prev] = st.kept_l
         pos0, l0 = p0, lnprob0
-        done = made = 0                       # steps handed out / made on the device by this call
-        acc_made = self.naccepted
+        done = st.made = 0                    # steps handed out / made on the device by this call
+        st.acc_made = self.naccepted
         cur = None if p0 is None else np.asarray(p0, dtype=np.float64)
         if cur is None and self._last is not None:
             cur = self._last[0]
+        own = None
+        self._open = st
         try:
-            while done < iterations:
+            while True:
                 k = min(chunk, iterations - done)
                 acc_before = np.array(self.naccepted, dtype=np.float64, copy=True)
-                self._chain, self._lnprob = kept_c[..., :0, :], kept_l[..., :0]
-                self.run_mcmc(pos0, k, lnprob0=l0, storechain=True)
+                self._chain, self._lnprob = st.kept_c[..., :0, :], st.kept_l[..., :0]
+                self._run(pos0, k, lnprob0=l0, storechain=True)
                 steps, lnps = self._chain, self._lnprob          # (this chunk's own arrays)
-                made, acc_made = made + k, self.naccepted
+                st.made, st.acc_made = st.made + k, self.naccepted
+                if not st.single:
+                    self._resident = 0                            # (one chunk of several: a part of the run)
+                if st.made == k:
+                    # sharded with the one-hop exchange: the rows of the other ranks' walkers are zeros
+                    ctx = self._ctx
+                    if hasattr(ctx, "xchg_barrier") and ctx.info("nranks") > 1:
+                        own = _own_rows(self.k, ctx.info("rank"), ctx.info("nranks"))
                 pos0 = l0 = None
                 if storechain:
-                    big_c[..., n_prev + done:n_prev + done + k, :] = steps
-                    big_l[..., n_prev + done:n_prev + done + k] = lnps
-                # a walker's accepted moves step by step: a stretch move that is accepted changes the walker's position
-                prev = np.concatenate((cur[..., None, :], steps[..., :-1, :]), axis=ax)
-                moved = np.cumsum(np.any(steps != prev, axis=-1), axis=-1)
-                cur = steps[..., k - 1, :]
+                    st.big_c[..., n_prev + done:n_prev + done + k, :] = steps
+                    st.big_l[..., n_prev + done:n_prev + done + k] = lnps
+                moved = accepted_by_step(cur, steps, own)
+                if k > 0:
+                    cur = steps[..., k - 1, :]
                 for j in range(k):
                     done += 1
                     if storechain:
-                        self._chain, self._lnprob = big_c[..., :n_prev + done, :], big_l[..., :n_prev + done]
+                        self._chain, self._lnprob = st.big_c[..., :n_prev + done, :], st.big_l[..., :n_prev + done]
                     else:
-                        self._chain, self._lnprob = kept_c, kept_l
+                        self._chain, self._lnprob = st.kept_c, st.kept_l
                     self.iterations = it_prev + done
-                    self.naccepted = acc_made if j == k - 1 else acc_before + moved[..., j]
+                    self.naccepted = st.acc_made if j == k - 1 else acc_before + moved[..., j]
                     yield steps[..., j, :], lnps[..., j], self.seed
+                    if not st.live:
+                        raise RuntimeError("this sample() generator was retired by a later run_mcmc, reset or sample() "
+                                           "of its sampler: the sampler has gone on from the end of its chunk")
+                if done >= iterations:
+                    break
         finally:
             # (left early, inside a chunk: the device made the whole chunk and run_mcmc(None, n) goes on from its end --
-            # the attributes then show all of it)
-            self.iterations, self.naccepted = it_prev + made, acc_made
-            if storechain:
-                self._chain, self._lnprob = big_c[..., :n_prev + made, :], big_l[..., :n_prev + made]
-            else:
-                self._chain, self._lnprob = kept_c, kept_l
+            # the attributes then show all of it; a retired generator has handed that over already and touches nothing)
+            if st.live:
+                st.live = False
+                self._leave(st)
+                if self._open is st:
+                    self._open = None
 
     def advance_async(self, N):
         """Enqueue N steps without storing or synchronising (benchmarks)."""

@@ -149,6 +149,8 @@ class EnsembleSampler(object):
             raise ValueError("p0 must have shape (nwalkers, dim)")
         lnprob = lnprob0 if lnprob0 is not None else self._get_lnprob(p)
         lnprob = np.array(lnprob, dtype=np.float64)
+        if lnprob.shape != (self.k,):
+            raise ValueError("lnprob0 must have shape (nwalkers,)")
         if np.any(np.isnan(lnprob)):
             raise ValueError("The initial lnprob was NaN.")
         # the Jacobian of the stretch move is z^(d - 1), d the dimension of the space the walkers span: a column

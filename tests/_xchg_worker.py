@@ -63,6 +63,18 @@ def main():
         # continuing the chain, and the asynchronous form the benchmark uses
         pos2, lnp2, _ = smp.run_mcmc(None, 5)
         assert np.array_equal(pos2, rpos2) and np.array_equal(lnp2, rlnp2)
+        # the generator form on the sharded sampler: while a step is out, the acceptance counts are those of this
+        # rank's walkers after it -- the unsharded run's, made one step per call -- and 0 in the rows of the others, whose
+        # chain this rank does not hold (every rank makes the same calls: the exchange stays in step)
+        seen = 0
+        for spos, slnp, _ in smp.sample(None, iterations=7, chunk=3):
+            upos, ulnp, _ = ref.run_mcmc(None, 1)
+            seen += 1
+            assert np.array_equal(smp.naccepted[mine], ref.naccepted[mine]), "counts differ at step %d on rank %d" % (seen, rank)
+            assert not smp.naccepted[others].any(), "rows of other ranks counted at step %d on rank %d" % (seen, rank)
+            assert np.array_equal(spos[mine], upos[mine]) and np.array_equal(slnp[mine], ulnp[mine])
+            assert smp.iterations == nsteps + 5 + seen and smp.chain.shape == (nw, nsteps + 5 + seen, 5)
+        assert seen == 7
         dist.barrier()
         smp.advance_async(40)
         ctx.sync()
