@@ -291,6 +291,62 @@ int mbb_chain_diagnostics(mbb_ctx *ctx, const double *chain, int nsrc, int nw, i
  * communicator or the one-hop exchange with more than one rank): a rank holds only its own walkers' chain. */
 int mbb_sampler_diagnostics(mbb_ctx *ctx, void *sampler, const mbb_diag_spec *spec, const mbb_diag_out *out);
 
+/* ---- binned posterior marginals of a chain, computed where the chain is ---- */
+/* Replaces: numpy.histogram / numpy.histogram2d (or corner) on mbb_results.parameter_chain, which is how a user of
+ * the reference gets per-parameter PDFs and the T-beta contours: the reference has no code for it.  Per (source,
+ * column slot of a summary) a histogram of nbins bins; per (source, requested pair of slots a < b) a table of
+ * nbins2 x nbins2 bins, [bin of a][bin of b].  A column's samples are a summary's: steps burn, burn + thin, ... of
+ * every walker; the derived columns are the summary's, with the summary spec's settings.
+ *   range   given (has_range[slot]): lo[slot], hi[slot], one pair for every source; else per source the min and max
+ *           of the column's finite samples, min - 0.5 and max + 0.5 when they are equal (numpy.histogram's rule)
+ *   edges   numpy.linspace(lo, hi, nbins + 1) bit for bit: e[i] = i * ((hi - lo) / nbins) + lo, the product and the sum
+ *           rounded separately, e[nbins] = hi
+ *   bins    x is counted in bin i iff e[i] <= x < e[i + 1]; the last bin also takes x == hi.  The comparisons decide.
+ *   below lo, above hi, not finite (NaN, +-inf): counted in n_below, n_above, n_nonfinite, never binned;
+ *           n_used is the number binned, and the four add up to the samples of the column
+ *   2-D     over the two columns' own ranges and numpy.linspace(lo, hi, nbins2 + 1): a sample is counted when it is
+ *           binned in both; numpy.histogram2d's [i][j]
+ * Counts are exactly numpy's.  All accumulation is integer: a chain gives the same bits every time.  A column may
+ * have 2^32 - 1 samples. */
+#define MBB_MARG_MAX_BINS 4096
+#define MBB_MARG_MAX_BINS2 100
+#define MBB_MARG_MAX_PAIRS 28
+/* status of a column: bits (MBB_MARG_EMPTY, _ABSENT and the row shift are the summary's values) */
+enum mbb_marginals_status {
+    MBB_MARG_EMPTY = 1,       /* no finite sample: all counts 0, NaN edges                                         */
+    MBB_MARG_NONFINITE = 2,   /* the column holds a NaN or an infinity inside the window (n_nonfinite > 0)         */
+    MBB_MARG_ABSENT = 4,      /* a derived column that was not asked for: all counts 0, NaN edges                  */
+    MBB_MARG_ROW_SHIFT = 8    /* bit 8 + s: a sample's SED kernel row had mbb_row_status s (derived columns)       */
+};
+typedef struct mbb_marginals_spec {
+    int32_t nbins;                         /* 1 .. MBB_MARG_MAX_BINS                                          */
+    int32_t nbins2;                        /* 0 .. MBB_MARG_MAX_BINS2 per axis; 0: no 2-D tables               */
+    int32_t npairs;                        /* 0 .. MBB_MARG_MAX_PAIRS (0 when nbins2 is 0)                     */
+    int32_t pairs[MBB_MARG_MAX_PAIRS][2];  /* slots (a, b), a < b, both columns present                       */
+    int32_t has_range[MBB_SUMMARY_COLS];
+    double lo[MBB_SUMMARY_COLS], hi[MBB_SUMMARY_COLS];   /* finite, lo < hi, hi - lo finite                    */
+    /* burn, thin, derived, peak_model, redshift / lumdist_mpc (scalar or per source), kappa, kappa_wave and the L_IR
+     * range are taken from here; its percentiles and clips are ignored.  Required. */
+    const mbb_summary_spec *summary;
+} mbb_marginals_spec;
+/* Where marginals go; every pointer is the caller's, host memory, required (counts2 and edges2 unless nbins2 or
+ * npairs is 0). */
+typedef struct mbb_marginals_out {
+    uint32_t *counts1;                     /* [nsrc][8][nbins]                                                */
+    double *edges1;                        /* [nsrc][8][nbins + 1]                                            */
+    uint32_t *counts2;                     /* [nsrc][npairs][nbins2][nbins2]                                  */
+    double *edges2;                        /* [nsrc][8][nbins2 + 1]                                           */
+    int64_t *n_used, *n_below, *n_above, *n_nonfinite;   /* [nsrc][8]                                        */
+    int32_t *status;                       /* [nsrc][8] mbb_marginals_status bits                             */
+} mbb_marginals_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5]: upload, bin on the device, download the tables.  Arguments
+ * are checked before anything is uploaded (MBB_ERR_ARG with a message). */
+int mbb_chain_marginals(mbb_ctx *ctx, const double *chain, int nsrc, int nw, int nsteps,
+                        const mbb_marginals_spec *spec, const mbb_marginals_out *out);
+/* The same of the chain the sampler's last stored or summarised run left on the device.  MBB_ERR_STATE when there is
+ * none, and for a sharded run, as mbb_sampler_diagnostics. */
+int mbb_sampler_marginals(mbb_ctx *ctx, void *sampler, const mbb_marginals_spec *spec, const mbb_marginals_out *out);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

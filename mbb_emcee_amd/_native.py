@@ -57,6 +57,27 @@ class DiagOut(C.Structure):
     _fields_ = [("tau", _dp), ("ess", _dp), ("rhat", _dp), ("window", _ip), ("status", _ip), ("acf", _dp)]
 
 
+MARG_MAX_BINS, MARG_MAX_BINS2, MARG_MAX_PAIRS = 4096, 100, 28
+MARG_EMPTY, MARG_NONFINITE, MARG_ABSENT, MARG_ROW_SHIFT = 1, 2, 4, 8
+_up = C.POINTER(C.c_uint32)
+_lp = C.POINTER(C.c_int64)
+
+
+class MarginalsSpec(C.Structure):
+    """mbb_marginals_spec (include/mbb_hip.h)"""
+    _fields_ = [("nbins", C.c_int32), ("nbins2", C.c_int32), ("npairs", C.c_int32),
+                ("pairs", (C.c_int32 * 2) * MARG_MAX_PAIRS),
+                ("has_range", C.c_int32 * SUMMARY_COLS),
+                ("lo", C.c_double * SUMMARY_COLS), ("hi", C.c_double * SUMMARY_COLS),
+                ("summary", C.POINTER(SummarySpec))]
+
+
+class MarginalsOut(C.Structure):
+    """mbb_marginals_out (include/mbb_hip.h)"""
+    _fields_ = [("counts1", _up), ("edges1", _dp), ("counts2", _up), ("edges2", _dp),
+                ("n_used", _lp), ("n_below", _lp), ("n_above", _lp), ("n_nonfinite", _lp), ("status", _ip)]
+
+
 # name -> (restype, argtypes); mirrors include/mbb_hip.h one to one
 SIGNATURES = {
     "mbb_last_error": (C.c_char_p, []),
@@ -87,6 +108,9 @@ SIGNATURES = {
                                           C.POINTER(SummaryOut), _dp, _dp, _dp, _dp, _dp]),
     "mbb_chain_diagnostics": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(DiagSpec), C.POINTER(DiagOut)]),
     "mbb_sampler_diagnostics": (C.c_int, [_vp, _vp, C.POINTER(DiagSpec), C.POINTER(DiagOut)]),
+    "mbb_chain_marginals": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(MarginalsSpec),
+                                      C.POINTER(MarginalsOut)]),
+    "mbb_sampler_marginals": (C.c_int, [_vp, _vp, C.POINTER(MarginalsSpec), C.POINTER(MarginalsOut)]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

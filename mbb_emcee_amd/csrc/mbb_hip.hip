@@ -31,6 +31,7 @@
 #include "mbb_kernels.hip.h"
 #include "mbb_summary.hip.h"
 #include "mbb_diag.hip.h"
+#include "mbb_marginals.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
 #define MBB_FLOW_EXT(OT, NA)                                                    \
@@ -278,6 +279,11 @@ struct mbb_ctx {
         size_t c_mean = 0, c_seq = 0, c_outbuf = 0;
         size_t lds_granted = 0;               // dynamic-LDS ceiling already requested for k_diag_acf
     } diag;
+    // ... and of the chain marginals (marg_run)
+    struct MargWork {
+        void *extent = nullptr, *range = nullptr, *part1 = nullptr, *part2 = nullptr, *outbuf = nullptr;
+        size_t c_extent = 0, c_range = 0, c_part1 = 0, c_part2 = 0, c_outbuf = 0;
+    } marg;
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -526,6 +532,8 @@ extern "C" void mbb_ctx_destroy(mbb_ctx *c)
     free_dev(c->sum.part); free_dev(c->sum.state); free_dev(c->sum.hist); free_dev(c->sum.covpart);
     free_dev(c->sum.colstatus); free_dev(c->sum.outbuf); free_dev(c->sum.der); free_dev(c->sum.src);
     free_dev(c->diag.mean); free_dev(c->diag.seq); free_dev(c->diag.outbuf);
+    free_dev(c->marg.extent); free_dev(c->marg.range); free_dev(c->marg.part1); free_dev(c->marg.part2);
+    free_dev(c->marg.outbuf);
     for (int i = 0; i < 2; ++i)
         if (c->ev_timed[i]) (void)hipEventDestroy(c->ev_timed[i]);
     if (c->stream) {
@@ -2608,6 +2616,168 @@ extern "C" int mbb_sampler_diagnostics(mbb_ctx *c, void *sp, const mbb_diag_spec
     if (s->resident_nsteps <= 0 || !s->d_chain_out)
         return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
     return diag_run(c, s->d_chain_out, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+}
+
+// ---- binned marginals of a chain (mbb_marginals.hip.h) ------------------------
+// The argument checks of a marginals call: before anything is allocated or uploaded.
+static int marg_check(int nsrc, int nw, int nsteps, const mbb_marginals_spec *sp, const mbb_marginals_out *o)
+{
+    using namespace mbbm;
+    static_assert(kCols == MBB_SUMMARY_COLS && kMaxBins == MBB_MARG_MAX_BINS && kMaxBins2 == MBB_MARG_MAX_BINS2 &&
+                  kMaxPairs == MBB_MARG_MAX_PAIRS, "marginals sizes");
+    static_assert(kStEmpty == MBB_MARG_EMPTY && kStNonfinite == MBB_MARG_NONFINITE && kStAbsent == MBB_MARG_ABSENT &&
+                  kStRowShift == MBB_MARG_ROW_SHIFT && kStRowShift == mbbs::kStRowShift, "marginals status bits");
+    if (!sp || !o || !sp->summary) return fail(MBB_ERR_ARG, "null marginals argument");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    if (sp->nbins < 1 || sp->nbins > kMaxBins) return fail(MBB_ERR_ARG, "nbins must be between 1 and 4096");
+    if (sp->nbins2 < 0 || sp->nbins2 > kMaxBins2) return fail(MBB_ERR_ARG, "nbins2 must be between 0 and 100");
+    if (sp->npairs < 0 || sp->npairs > kMaxPairs) return fail(MBB_ERR_ARG, "0 to 28 pairs per call");
+    if (sp->npairs > 0 && sp->nbins2 == 0) return fail(MBB_ERR_ARG, "pairs need nbins2 > 0");
+    const bool two = sp->nbins2 > 0 && sp->npairs > 0;
+    if (!o->counts1 || !o->edges1 || !o->n_used || !o->n_below || !o->n_above || !o->n_nonfinite || !o->status ||
+        (two && !o->counts2) || (sp->nbins2 > 0 && !o->edges2))
+        return fail(MBB_ERR_ARG, "null marginals argument");
+    const mbb_summary_spec *ss = sp->summary;
+    if (ss->burn < 0 || ss->burn >= nsteps || ss->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    if (ss->derived & ~7) return fail(MBB_ERR_ARG, "unknown derived column");
+    const auto present = [&](int slot) { return slot >= 0 && slot < kCols && (slot < 5 || ((ss->derived >> (slot - 5)) & 1)); };
+    for (int k = 0; k < sp->npairs; ++k) {
+        const int a = sp->pairs[k][0], b = sp->pairs[k][1];
+        if (!present(a) || !present(b)) return fail(MBB_ERR_ARG, "a pair names a column that is absent");
+        if (a >= b) return fail(MBB_ERR_ARG, "a pair (a, b) needs a < b");
+    }
+    for (int k = 0; k < kCols; ++k) {
+        if (!sp->has_range[k]) continue;
+        const double lo = sp->lo[k], hi = sp->hi[k];
+        if (!(lo - lo == 0.0 && hi - hi == 0.0 && lo < hi && (hi - lo) - (hi - lo) == 0.0))
+            return fail(MBB_ERR_ARG, "a range must be finite with lo < hi");
+    }
+    int rc;
+    if ((rc = summary_check_cosmology(ss, nsrc))) return rc;
+    if ((ss->derived & MBB_SUM_LIR) && !(ss->lir_wavemin > 0.0 && ss->lir_wavemax > 0.0))
+        return fail(MBB_ERR_ARG, "wavelengths must be positive");
+    if ((ss->derived & MBB_SUM_DUSTMASS) && !(ss->kappa > 0.0 && ss->kappa_wave > 0.0))
+        return fail(MBB_ERR_ARG, "kappa and kappa_wave must be positive");
+    const int nkept = (nsteps - ss->burn + ss->thin - 1) / ss->thin;
+    if ((long long)nw * nkept > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 samples per column");
+    if ((size_t)nsrc * (kCols + kMaxPairs) > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    return MBB_OK;
+}
+
+// Bin a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
+static int marg_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nsteps, const mbb_marginals_spec *sp,
+                    const mbb_marginals_out *o)
+{
+    using namespace mbbm;
+    int rc;
+    if ((rc = marg_check(nsrc, nw, nsteps, sp, o))) return rc;
+    const mbb_summary_spec *ss = sp->summary;
+    const int nkept = (nsteps - ss->burn + ss->thin - 1) / ss->thin;
+    const long long n = (long long)nw * nkept;
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    MargArgs a;
+    memset(&a, 0, sizeof a);
+    a.chain = d_chain;
+    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = ss->burn; a.thin = ss->thin; a.nkept = nkept; a.n = n;
+    a.ncol = 5;
+    for (int k = 0; k < 5; ++k) a.col[k] = k;
+    for (int k = 0; k < 3; ++k) if ((ss->derived >> k) & 1) a.col[a.ncol++] = 5 + k;
+    a.nbins = sp->nbins;
+    a.nbins2 = sp->nbins2;
+    a.npairs = sp->nbins2 > 0 ? sp->npairs : 0;
+    for (int k = 0; k < a.npairs; ++k) { a.pair[k][0] = sp->pairs[k][0]; a.pair[k][1] = sp->pairs[k][1]; }
+    for (int k = 0; k < kCols; ++k) { a.has_range[k] = sp->has_range[k] != 0; a.lo[k] = sp->lo[k]; a.hi[k] = sp->hi[k]; }
+    // One workgroup per (source, column or pair) when those fill the device by themselves; else a column is cut into
+    // splits of at most kSplitSamples samples whose tables are merged (summary_run's scheme at a finer grain: a
+    // table costs no floating-point tree, and a single source's five columns are otherwise twenty workgroups).
+    const size_t ncolumns = (size_t)nsrc * a.ncol, npairs = (size_t)nsrc * a.npairs;
+    a.splits = ncolumns >= 1024 ? 1 : (int)std::min<long long>(kMaxSplits, (n + kSplitSamples - 1) / kSplitSamples);
+    a.per_split = (n + a.splits - 1) / a.splits;
+    const size_t sc = (size_t)nsrc * kCols, nb = (size_t)a.nbins, nb2 = (size_t)a.nbins2;
+    // the result block: doubles, 64-bit counts, 32-bit words
+    const size_t n_e1 = sc * (nb + 1), n_e2 = nb2 ? sc * (nb2 + 1) : 0, n_c1 = sc * nb, n_c2 = npairs * nb2 * nb2;
+    const size_t out_bytes = (n_e1 + n_e2) * sizeof(double) + 4 * sc * sizeof(long long) +
+                             (n_c1 + n_c2) * sizeof(unsigned int) + sc * sizeof(int);
+    mbb_ctx::MargWork &w = c->marg;
+    if ((rc = sum_grow(c, &w.extent, &w.c_extent, ncolumns * a.splits * 2 * sizeof(double)))) return rc;
+    if ((rc = sum_grow(c, &w.range, &w.c_range, sc * sizeof(Range)))) return rc;
+    if ((rc = sum_grow(c, &w.part1, &w.c_part1, ncolumns * a.splits * (nb + kTail) * sizeof(unsigned int)))) return rc;
+    if (npairs && (rc = sum_grow(c, &w.part2, &w.c_part2, npairs * a.splits * nb2 * nb2 * sizeof(unsigned int)))) return rc;
+    if ((rc = sum_grow(c, &w.outbuf, &w.c_outbuf, out_bytes))) return rc;
+    if ((rc = sum_grow(c, &c->sum.colstatus, &c->sum.c_colstatus, sc * sizeof(int)))) return rc;
+    a.extent = (double *)w.extent; a.range = (Range *)w.range;
+    a.part1 = (unsigned int *)w.part1; a.part2 = (unsigned int *)w.part2;
+    a.colstatus = (const int *)c->sum.colstatus;
+    a.o_edges1 = (double *)w.outbuf;
+    a.o_edges2 = a.o_edges1 + n_e1;
+    a.o_used = (long long *)(a.o_edges2 + n_e2);
+    a.o_below = a.o_used + sc; a.o_above = a.o_below + sc; a.o_nonfinite = a.o_above + sc;
+    a.o_counts1 = (unsigned int *)(a.o_nonfinite + sc);
+    a.o_counts2 = a.o_counts1 + n_c1;
+    a.o_status = (int *)(a.o_counts2 + n_c2);
+    HIPCHK(hipMemsetAsync(c->sum.colstatus, 0, sc * sizeof(int), c->stream));
+    // the derived columns: the summary's own fill, through a SumArgs that carries what it reads
+    mbbs::SumArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.chain = d_chain;
+    sa.nsrc = nsrc; sa.nw = nw; sa.nsteps = nsteps; sa.burn = ss->burn; sa.thin = ss->thin;
+    if ((rc = summary_fill_derived(c, ss, sa, cells))) return rc;
+    for (int k = 0; k < 3; ++k) a.der[k] = sa.der[k];
+    const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
+    hipLaunchKernelGGL(k_marg_extent, gcol, dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_marg_edges, dim3((unsigned)sc), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_marg_hist1, gcol, dim3(kThreads), 0, c->stream, a);
+    if (npairs)
+        hipLaunchKernelGGL(k_marg_hist2, dim3((unsigned)npairs, (unsigned)a.splits), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_marg_merge, dim3((unsigned)(sc + npairs)), dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(o->edges1, a.o_edges1, n_e1 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_e2) HIPCHK(hipMemcpyAsync(o->edges2, a.o_edges2, n_e2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->n_used, a.o_used, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->n_below, a.o_below, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->n_above, a.o_above, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->n_nonfinite, a.o_nonfinite, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->counts1, a.o_counts1, n_c1 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    if (n_c2) HIPCHK(hipMemcpyAsync(o->counts2, a.o_counts2, n_c2 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->status, a.o_status, sc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->sum.src_in_flight = false;
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_marginals(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
+                                   const mbb_marginals_spec *spec, const mbb_marginals_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = marg_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    double *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, cells * 5 * sizeof(double)));
+    hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(MBB_ERR_HIP, "upload of the chain", e); }
+    rc = marg_run(c, d, nsrc, nw, nsteps, spec, out);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int mbb_sampler_marginals(mbb_ctx *c, void *sp, const mbb_marginals_spec *spec, const mbb_marginals_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    mbb_sampler_state *s = (mbb_sampler_state *)sp;
+    if (!s || !spec || !out) return fail(MBB_ERR_ARG, "bad sampler arguments");
+    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
+    ShardPlan p;
+    if ((rc = shard_plan(c, s, p))) return rc;
+    if (p.collective)
+        return fail(MBB_ERR_STATE, "a sharded sampler run cannot be binned on the device: a rank holds only its own "
+                                   "walkers' chain");
+    if (s->resident_nsteps <= 0 || !s->d_chain_out)
+        return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
+    return marg_run(c, s->d_chain_out, s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

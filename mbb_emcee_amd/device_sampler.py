@@ -98,7 +98,8 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary`` and no ``convergence_``, nothing resident for ``convergence()``, and no
+        shape, ``iterations`` 0, no ``summary``, ``convergence_`` or ``marginals_``, nothing resident for ``convergence()`` or
+        ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
         ``pos, lnp, _ = s.run_mcmc(p0, nburn); s.reset(); s.run_mcmc(pos, n, lnprob0=lnp)`` -- emcee's burn-in idiom --
@@ -116,6 +117,7 @@ class DeviceEnsembleSampler(object):
             self.summary.drop_chain()
         self.summary = None
         self.convergence_ = None
+        self.marginals_ = None
         self._resident = 0                    # steps of the last run's chain that are resident on the device
         if self._h is not None:
             _native._check(self._ctx.lib.mbb_sampler_reset(self._ctx.h, self._h))
@@ -172,8 +174,24 @@ class DeviceEnsembleSampler(object):
         diagnostics._native_call(ctx.lib.mbb_sampler_diagnostics(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return diagnostics.ChainDiagnostics(req, raw, self.nsources > 1, self.k, n)
 
+    def marginals(self, **kw):
+        """``marginals.ChainMarginals`` (1-d and 2-d histograms per source and column) of the chain the last run left on
+        the device -- a run with storechain=True or with summary= --; the keywords are ``marginals.chain_marginals``'s.
+        No chain crosses the bus."""
+        from . import marginals
+        req = marginals._Request(nsources=self.nsources, **kw)
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: marginals() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset")
+        nkept = req.check_steps(self._resident)
+        ctx, h = self._handle()
+        raw = marginals._Raw(self.nsources, req.bins, req.bins2d, len(req.pairs))
+        spec, out = req.spec(), raw.out()
+        marginals._native_call(ctx.lib.mbb_sampler_marginals(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return marginals.ChainMarginals(req, raw, self.nsources > 1, self.k, nkept)
+
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
-                 **unused):
+                 marginals=None, **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -201,9 +219,14 @@ class DeviceEnsembleSampler(object):
         convergence=True, or a dict of ``convergence()``'s keywords: the chain of this run is diagnosed on the device
         and ``sampler.convergence_`` is the ``diagnostics.ChainDiagnostics`` of it (None again after reset() and at the
         start of the next run).  With storechain=False it needs summary= too: that is what keeps the chain of a run on
-        the device."""
+        the device.
+
+        marginals=True, or a dict of ``marginals()``'s keywords: the chain of this run is binned on the device and
+        ``sampler.marginals_`` is the ``marginals.ChainMarginals`` of it (None again after reset() and at the start of
+        the next run).  With storechain=False it needs summary= too; burn, thin, derived and the derived columns'
+        settings default to those given with summary=."""
         self._retire()
-        return self._run(pos0, N, lnprob0, storechain, summary, convergence)
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
@@ -222,9 +245,22 @@ class DeviceEnsembleSampler(object):
         if not st.single:
             self._resident = 0                # (what is resident is the last chunk: a part)
 
-    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None):
-        creq = None
+    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None):
+        creq = mkw = None
         self.convergence_ = None
+        self.marginals_ = None
+        if marginals is not None and marginals is not False:
+            from . import marginals as _marginals
+            mkw = {} if marginals is True else dict(marginals)
+            if summary is not None and summary is not False and summary is not True:
+                for key in _marginals._SUMMARY_KEYS:
+                    if key in summary:
+                        mkw.setdefault(key, summary[key])
+            mreq = _marginals._Request(nsources=self.nsources, **mkw)
+            if not storechain and (summary is None or summary is False):
+                raise ValueError("marginals= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device")
+            mreq.check_steps(int(N))
         if convergence is not None and convergence is not False:
             from . import diagnostics
             ckw = {} if convergence is True else dict(convergence)
@@ -236,6 +272,9 @@ class DeviceEnsembleSampler(object):
         ctx, h = self._handle()
         if creq is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be diagnosed on the device: a rank holds only its own "
+                             "walkers' chain")
+        if mkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be binned on the device: a rank holds only its own "
                              "walkers' chain")
         req = None
         if summary is not None and summary is not False:
@@ -331,6 +370,8 @@ class DeviceEnsembleSampler(object):
                                                 self._summary_percentile)
         if creq is not None:
             self.convergence_ = self.convergence(creq.burn, creq.c, creq.tol, creq.method, creq.nacf)
+        if mkw is not None:
+            self.marginals_ = self.marginals(**mkw)
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):
@@ -386,7 +427,7 @@ class DeviceEnsembleSampler(object):
         run_mcmc refuses -- a wrong shape, NaN or inf in ``p0``, ``p0`` None without a state -- sample() refuses at
         the first ``next()``; ``iterations=0`` sets the state as ``run_mcmc(p0, 0)`` does and yields nothing.
 
-        Afterwards ``summary`` and ``convergence_`` are None.  ``convergence()`` describes all the steps this call
+        Afterwards ``summary``, ``convergence_`` and ``marginals_`` are None.  ``convergence()`` describes all the steps this call
         made where the whole run was one chunk (``iterations`` <= ``chunk``), which is then resident on the device;
         otherwise it raises its "no chain of this sampler is resident" ValueError: it never describes a part."""
         self._retire()

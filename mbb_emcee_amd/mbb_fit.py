@@ -137,13 +137,17 @@ class mbb_fitter(object):
                                                                 lo[worst], hi[worst]))
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
-    def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None):
+    def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
         (``set_phot_multi``) its ``redshift`` and ``lumdist_mpc`` may be arrays with one entry per source.
         convergence (device sampler only): True or a dict of ``diagnostics.chain_diagnostics``'s keywords -- the main
-        chain's autocorrelation times, effective sample sizes and split R-hat, ``mbb_fitter.convergence``."""
+        chain's autocorrelation times, effective sample sizes and split R-hat, ``mbb_fitter.convergence``.
+        marginals (device sampler only): True or a dict of ``marginals.chain_marginals``'s keywords -- the main chain's
+        1-d and 2-d histograms, ``mbb_fitter.marginals``."""
+        if marginals is not None and marginals is not False and not hasattr(self.sampler, "marginals"):
+            raise ValueError("marginals= needs sampler=\"device\"")
         if convergence is not None and convergence is not False and not hasattr(self.sampler, "convergence"):
             raise ValueError("convergence= needs sampler=\"device\"")
         if summary is not None and summary is not False and not hasattr(self.sampler, "_summarise_again"):
@@ -184,6 +188,8 @@ class mbb_fitter(object):
             extra["summary"] = summary
         if convergence is not None and convergence is not False:
             extra["convergence"] = convergence
+        if marginals is not None and marginals is not False:
+            extra["marginals"] = marginals
         self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, **extra)
         self._sampled = True
 
@@ -223,6 +229,8 @@ mbb_fitter.summary = property(lambda self: getattr(self.sampler, "summary", None
 mbb_fitter.convergence = property(lambda self: getattr(self.sampler, "convergence_", None),
                                   doc="diagnostics.ChainDiagnostics of the main chain when run() was given convergence=, "
                                       "else None")
+mbb_fitter.marginals = property(lambda self: getattr(self.sampler, "marginals_", None),
+                                doc="marginals.ChainMarginals of the main chain when run() was given marginals=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,
                                          doc="Is passband integration in use?")
 

@@ -45,6 +45,11 @@ def build_parser():
     p.add_argument("--convergence", action="store_true",
                    help="diagnose the chain on the device (autocorrelation time, effective sample size, split R-hat "
                         "per parameter; needs --sampler device): printed, and added to the .npz as convergence_*")
+    p.add_argument("--marginals", type=int, default=0, metavar="NBINS",
+                   help="bin the chain on the device (a histogram of NBINS bins per parameter, with --get_peaklambda of "
+                        "the peak wavelength too; needs --sampler device): printed, and added to the .npz as marginals_*")
+    p.add_argument("--marginals2d", type=int, default=0, metavar="NBINS2",
+                   help="with --marginals: also the 2-d histograms of all pairs of columns, NBINS2 bins per axis")
     p.add_argument("-v", "--verbose", action="store_true")
     for nm, dflt in zip(NAMES, (10.0, 2.0, 2500.0, 4.0, 40.0)):
         p.add_argument("--init" + nm, type=float, default=dflt)
@@ -89,6 +94,11 @@ def main(argv=None):
     if a.summary:
         summary = dict(percentile=(68.3, 95.4), derived=("peaklambda",) if a.get_peaklambda else ())
     extra = dict(convergence=True) if a.convergence else {}
+    if a.marginals2d and not a.marginals:
+        raise ValueError("--marginals2d needs --marginals")
+    if a.marginals:
+        extra["marginals"] = dict(bins=a.marginals, bins2d=a.marginals2d, pairs="all",
+                                  derived=("peaklambda",) if a.get_peaklambda else ())
     fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary, **extra)
     chain, lnp = fit.sampler.chain, fit.sampler.lnprobability
     out = dict(chain=chain, lnprobability=lnp, acceptance_fraction=fit.sampler.acceptance_fraction,
@@ -103,6 +113,9 @@ def main(argv=None):
     if a.convergence:
         out.update(fit.convergence.arrays())
         print(fit.convergence)
+    if a.marginals:
+        out.update(fit.marginals.arrays())
+        print(fit.marginals)
     np.savez_compressed(a.outfile, **out)
     if a.verbose:
         flat = chain.reshape(-1, 5)
