@@ -176,6 +176,30 @@ def _check(rc):
         raise NativeError("mbb_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
 
 
+def check_arg(rc, ctx):
+    """A native call's return code: MBB_ERR_ARG is a ValueError with the library's message, the rest as _check."""
+    if rc == -2:
+        raise ValueError(ctx.lib.mbb_last_error().decode())
+    _check(rc)
+
+
+def chain4(chain):
+    """A stored chain as a contiguous [nsources, nwalkers, nsteps, 5] array, and whether it came with a source axis."""
+    chain = np.ascontiguousarray(chain, dtype=np.float64)
+    if chain.ndim not in (3, 4) or chain.shape[-1] != 5:
+        raise ValueError("chain must be [nwalkers, nsteps, 5] or [nsources, nwalkers, nsteps, 5]")
+    multi = chain.ndim == 4
+    return (chain if multi else chain[None]), multi
+
+
+def analysis_context(like, model=True):
+    """The context of ``like`` for an analysis of a stored chain: its data in place, or (model) just its model."""
+    ctx = like._sync_device() if like.data_read else like.context
+    if model and not like.data_read:
+        ctx.set_model(like.opthin, like.noalpha, like.wavenorm)
+    return ctx
+
+
 def _d(a):
     return a.ctypes.data_as(_dp)
 

@@ -37,6 +37,7 @@ DEPS = [SRC, SRC_HOST, SRC_FLOW, SRC_REG, os.path.join(HERE, "csrc", "mbb_host_t
         os.path.join(HERE, "csrc", "mbb_flowm.hip.h"),
         os.path.join(HERE, "csrc", "mbb_flowa.hip.h"),
         os.path.join(HERE, "csrc", "mbb_serve.hip.h"),
+        os.path.join(HERE, "csrc", "mbb_chain_view.hip.h"),
         os.path.join(HERE, "csrc", "mbb_summary.hip.h"),
         os.path.join(HERE, "csrc", "mbb_diag.hip.h"),
         os.path.join(HERE, "csrc", "mbb_marginals.hip.h"),

@@ -179,6 +179,16 @@ static int load_rccl()
     return MBB_OK;
 }
 
+// A device buffer that is grown when a call needs more (grow), never shrinks and is freed with the context it is in.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
 struct mbb_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -265,25 +275,19 @@ struct mbb_ctx {
     double *d_sed_pars = nullptr, *d_sed_out = nullptr;
     int32_t *d_sed_status = nullptr;
     WalkerK *d_sed_wk = nullptr;
-    // work buffers of the chain summary (summary_run): grown as needed, kept for the next call
-    struct SumWork {
-        void *part = nullptr, *state = nullptr, *hist = nullptr, *covpart = nullptr, *colstatus = nullptr,
-             *outbuf = nullptr, *der = nullptr, *src = nullptr;
-        size_t c_part = 0, c_state = 0, c_hist = 0, c_covpart = 0, c_colstatus = 0, c_outbuf = 0, c_der = 0, c_src = 0;
+    // Work buffers of the chain analyses: grown as needed (grow), kept for the next call.  The derived columns of a
+    // chain (summary_fill_derived), for the summary and the marginals alike:
+    struct DerWork {
+        DevBuf der, src, colstatus;           // the columns, the per-source constants, [nsrc][kCols] row-status bits
         std::vector<mbbs::SrcConst> h_src;    // the per-source constants as uploaded (kept until the next call's)
         bool src_in_flight = false;           // ... and whether that upload may still be reading them
-    } sum;
-    // ... and of the chain diagnostics (diag_run)
-    struct DiagWork {
-        void *mean = nullptr, *seq = nullptr, *outbuf = nullptr;
-        size_t c_mean = 0, c_seq = 0, c_outbuf = 0;
+    } der;
+    struct SumWork { DevBuf part, state, hist, covpart, outbuf; } sum;          // ... the chain summary (summary_run)
+    struct DiagWork {                                                           // ... the chain diagnostics (diag_run)
+        DevBuf mean, seq, outbuf;
         size_t lds_granted = 0;               // dynamic-LDS ceiling already requested for k_diag_acf
     } diag;
-    // ... and of the chain marginals (marg_run)
-    struct MargWork {
-        void *extent = nullptr, *range = nullptr, *part1 = nullptr, *part2 = nullptr, *outbuf = nullptr;
-        size_t c_extent = 0, c_range = 0, c_part1 = 0, c_part2 = 0, c_outbuf = 0;
-    } marg;
+    struct MargWork { DevBuf extent, range, part1, part2, outbuf; } marg;       // ... and the chain marginals (marg_run)
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -529,11 +533,7 @@ extern "C" void mbb_ctx_destroy(mbb_ctx *c)
     free_dev(c->d_pre);
     free_dev(c->d_sed_pars); free_dev(c->d_sed_out); free_dev(c->d_sed_status);
     free_dev(c->d_sed_wk);
-    free_dev(c->sum.part); free_dev(c->sum.state); free_dev(c->sum.hist); free_dev(c->sum.covpart);
-    free_dev(c->sum.colstatus); free_dev(c->sum.outbuf); free_dev(c->sum.der); free_dev(c->sum.src);
-    free_dev(c->diag.mean); free_dev(c->diag.seq); free_dev(c->diag.outbuf);
-    free_dev(c->marg.extent); free_dev(c->marg.range); free_dev(c->marg.part1); free_dev(c->marg.part2);
-    free_dev(c->marg.outbuf);
+    // (the work buffers of the chain analyses are DevBufs: freed with the context, below)
     for (int i = 0; i < 2; ++i)
         if (c->ev_timed[i]) (void)hipEventDestroy(c->ev_timed[i]);
     if (c->stream) {
@@ -2185,17 +2185,101 @@ extern "C" int mbb_sed_integrate_batch(mbb_ctx *c, const double *pars, int n, in
     return MBB_OK;
 }
 
-// ---- posterior summaries of a chain (mbb_summary.hip.h) ------------------------
-static int sum_grow(mbb_ctx *c, void **p, size_t *cap, size_t bytes)
+// ---- analyses of a resident chain: what the summary, the diagnostics and the marginals share ------------------------
+static int grow(mbb_ctx *c, DevBuf &b, size_t bytes)
 {
-    if (bytes <= *cap) return MBB_OK;
+    if (bytes <= b.cap) return MBB_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
-    free_dev(*p); *p = nullptr; *cap = 0;
-    HIPCHK(hipMalloc(p, bytes));
-    *cap = bytes;
+    b.release();
+    HIPCHK(hipMalloc(&b.p, bytes));
+    b.cap = bytes;
     return MBB_OK;
 }
 
+// A result block handed out array by array: take<T>(n) is its next n values of T, put(dst, n) copies them out of a
+// host image of the block.  (The callers list their arrays by falling alignment, the same list on either side.)
+struct Carve {
+    char *p;
+    template <typename T> T *take(size_t n) { T *r = (T *)p; p += n * sizeof(T); return r; }
+    template <typename T> void put(T *dst, size_t n) { memcpy(dst, take<T>(n), n * sizeof(T)); }
+};
+
+// A host chain [cells][5], its lnprob [cells] behind it where given, on the device for as long as run(d_chain) takes.
+template <typename F>
+static int with_uploaded_chain(mbb_ctx *c, const double *chain, const double *lnprob, size_t cells, F &&run)
+{
+    double *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, cells * (lnprob ? 6 : 5) * sizeof(double)));
+    hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && lnprob)
+        e = hipMemcpyAsync(d + cells * 5, lnprob, cells * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    const int rc = e != hipSuccess ? fail(MBB_ERR_HIP, "upload of the chain", e) : run((const double *)d);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+// The sampler behind a handle whose run can be analysed on this device (verb: what the caller would do to its chain).
+static int analysed_sampler(mbb_ctx *c, void *sp, bool args_ok, const char *verb, mbb_sampler_state *&s)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    s = (mbb_sampler_state *)sp;
+    if (!s || !args_ok) return fail(MBB_ERR_ARG, "bad sampler arguments");
+    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
+    ShardPlan p;
+    if ((rc = shard_plan(c, s, p))) return rc;
+    if (!p.collective) return MBB_OK;
+    char buf[160];
+    snprintf(buf, sizeof buf, "a sharded sampler run cannot be %s on the device: a rank holds only its own walkers' chain",
+             verb);
+    return fail(MBB_ERR_STATE, buf);
+}
+
+// ... and whether its last stored run is still there in the caller's layout.  (resident_nsteps is made positive by
+// sampler_run alone, after k_chain_reorder has written d_chain_out: the chain is never null when it is.)
+static int resident_chain(const mbb_sampler_state *s)
+{
+    if (s->resident_nsteps > 0 && s->d_chain_out) return MBB_OK;
+    return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
+}
+
+// The checks of an mbb_summary_spec that every analysis with derived columns makes, in the order they are made.
+static int check_window(const mbb_summary_spec *sp, int nsteps)
+{
+    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    if (sp->derived & ~7) return fail(MBB_ERR_ARG, "unknown derived column");
+    return MBB_OK;
+}
+
+static int kept_steps(const mbb_summary_spec *sp, int nsteps) { return (nsteps - sp->burn + sp->thin - 1) / sp->thin; }
+
+static int check_sample_cap(const mbb_summary_spec *sp, int nw, int nsteps)
+{
+    if ((long long)nw * kept_steps(sp, nsteps) > 0xffffffffll)
+        return fail(MBB_ERR_ARG, "more than 2^32 samples per column");
+    return MBB_OK;
+}
+
+// The columns of a checked spec's window of a chain: the active slots, and each column cut into splits of at most
+// split_samples samples whose partial results are merged -- unless the (source, column) pairs fill the device by
+// themselves: then one workgroup per column.
+static void fill_chain_view(mbbc::ChainView &v, const double *d_chain, int nsrc, int nw, int nsteps,
+                            const mbb_summary_spec *sp, int split_samples)
+{
+    v.chain = d_chain;
+    v.nsrc = nsrc; v.nw = nw; v.nsteps = nsteps; v.burn = sp->burn; v.thin = sp->thin;
+    v.nkept = kept_steps(sp, nsteps);
+    v.n = (long long)nw * v.nkept;
+    v.ncol = 5;
+    for (int k = 0; k < 5; ++k) v.col[k] = k;
+    for (int k = 0; k < 3; ++k) if ((sp->derived >> k) & 1) v.col[v.ncol++] = 5 + k;
+    v.splits = (size_t)nsrc * v.ncol >= 1024
+                   ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (v.n + split_samples - 1) / split_samples);
+    v.per_split = (v.n + v.splits - 1) / v.splits;
+}
+
+// ---- the derived columns of a chain, for its summary and its marginals ------------------------
 constexpr int kSumChunkRows = 1 << 18;      // chain rows a derived column is filled by at a time (bounds the WalkerK buffer)
 
 // What of L_IR and dust mass depends on redshift z and luminosity distance lumdist [Mpc], as postprocess.lir and
@@ -2222,18 +2306,25 @@ static mbbs::SrcConst summary_src_const(const mbb_ctx *c, const mbb_summary_spec
 }
 
 // The derived columns of spec sp for the resident chain, into a.der[]: the SED kernels are fed the chain's own rows
-// (emcee's layout IS an array of 5-parameter rows), a chunk at a time.
-static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::SumArgs &a, size_t cells)
+// (emcee's layout IS an array of 5-parameter rows), a chunk at a time.  The row-status bits met on the way are
+// gathered in c->der.colstatus [nsrc][kCols], cleared here first (also when no column is asked for).
+static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbc::ChainView &a)
 {
+    using mbbc::kCols;
     int rc, nder = 0;
+    mbb_ctx::DerWork &w = c->der;
+    const size_t cells = (size_t)a.nsrc * a.nw * a.nsteps;
     const bool per_src = sp->src_redshift && (sp->derived & (MBB_SUM_LIR | MBB_SUM_DUSTMASS));
     const long long per = (long long)a.nw * a.nsteps;      // rows per source
+    if ((rc = grow(c, w.colstatus, (size_t)a.nsrc * kCols * sizeof(int)))) return rc;
+    int *const colstatus = (int *)w.colstatus.p;
+    HIPCHK(hipMemsetAsync(colstatus, 0, (size_t)a.nsrc * kCols * sizeof(int), c->stream));
     for (int k = 0; k < 3; ++k) nder += (sp->derived >> k) & 1;
     if (!nder) return MBB_OK;
-    if ((rc = sum_grow(c, &c->sum.der, &c->sum.c_der, (size_t)nder * cells * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.der, (size_t)nder * cells * sizeof(double)))) return rc;
     double *der[3] = {nullptr, nullptr, nullptr};
     for (int k = 0, i = 0; k < 3; ++k)
-        if ((sp->derived >> k) & 1) { der[k] = (double *)c->sum.der + (size_t)(i++) * cells; a.der[k] = der[k]; }
+        if ((sp->derived >> k) & 1) { der[k] = (double *)w.der.p + (size_t)(i++) * cells; a.der[k] = der[k]; }
     const int ngl = 64;
     const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
     if ((rc = ensure_sed(c, chunk, chunk * 6 + 2 * ngl))) return rc;
@@ -2244,12 +2335,12 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::Su
     if (!per_src) {
         if (der[1] || der[2]) one = summary_src_const(c, sp, sp->redshift, sp->lumdist_mpc);
     } else {
-        std::vector<mbbs::SrcConst> &h = c->sum.h_src;
-        if ((rc = sum_grow(c, &c->sum.src, &c->sum.c_src, (size_t)a.nsrc * sizeof(mbbs::SrcConst)))) return rc;
+        std::vector<mbbs::SrcConst> &h = w.h_src;
+        if ((rc = grow(c, w.src, (size_t)a.nsrc * sizeof(mbbs::SrcConst)))) return rc;
         // (h is the pageable source of the upload below: a call that returned early on an error may have left its
         // copy in flight)
-        if (c->sum.src_in_flight) HIPCHK(hipStreamSynchronize(c->stream));
-        c->sum.src_in_flight = false;
+        if (w.src_in_flight) HIPCHK(hipStreamSynchronize(c->stream));
+        w.src_in_flight = false;
         h.resize((size_t)a.nsrc);
         for (int s = 0; s < a.nsrc; ++s) {
             const double z = sp->src_redshift[s], lumdist = sp->src_lumdist_mpc[s];
@@ -2260,8 +2351,8 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::Su
                 h[(size_t)s] = summary_src_const(c, sp, z, lumdist);
             }
         }
-        d_src = (mbbs::SrcConst *)c->sum.src;
-        c->sum.src_in_flight = true;
+        d_src = (mbbs::SrcConst *)w.src.p;
+        w.src_in_flight = true;
         HIPCHK(hipMemcpyAsync(d_src, h.data(), (size_t)a.nsrc * sizeof(mbbs::SrcConst), hipMemcpyHostToDevice, c->stream));
     }
     if (der[1]) {
@@ -2279,7 +2370,7 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::Su
             const int ot = sp->peak_model ? 0 : c->opthin, na = sp->peak_model ? 0 : c->noalpha;
             if ((rc = launch_prologue(c, rows, n, ot, na, c->wavenorm, 1, c->d_sed_out))) return rc;
             hipLaunchKernelGGL(mbbs::k_sum_take, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
-                               (const int32_t *)c->d_sed_status, n, (long long)off, der[0], (int *)c->sum.colstatus,
+                               (const int32_t *)c->d_sed_status, n, (long long)off, der[0], colstatus,
                                a.nw, a.nsteps, a.burn, a.thin);
             HIPCHK(hipGetLastError());
         }
@@ -2301,12 +2392,12 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbs::Su
             if (per_src)
                 hipLaunchKernelGGL(mbbs::k_sum_lir_src, dim3(grid), dim3(256), 0, c->stream,
                                    (const double *)c->d_sed_out, (const int32_t *)c->d_sed_status, n, (long long)off,
-                                   (const mbbs::SrcConst *)d_src, der[1], (int *)c->sum.colstatus, a.nw, a.nsteps,
+                                   (const mbbs::SrcConst *)d_src, der[1], colstatus, a.nw, a.nsteps,
                                    a.burn, a.thin);
             else
                 hipLaunchKernelGGL(mbbs::k_sum_lir, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
                                    (const int32_t *)c->d_sed_status, n, (long long)off, one.prefac, der[1],
-                                   (int *)c->sum.colstatus, a.nw, a.nsteps, a.burn, a.thin);
+                                   colstatus, a.nw, a.nsteps, a.burn, a.thin);
             HIPCHK(hipGetLastError());
         }
     }
@@ -2357,6 +2448,27 @@ static int summary_check_cosmology(const mbb_summary_spec *sp, int nsrc)
     return MBB_OK;
 }
 
+// ... and everything else the derived columns are computed with.
+static int check_derived_settings(const mbb_summary_spec *sp, int nsrc)
+{
+    int rc;
+    if ((rc = summary_check_cosmology(sp, nsrc))) return rc;
+    if ((sp->derived & MBB_SUM_LIR) && !(sp->lir_wavemin > 0.0 && sp->lir_wavemax > 0.0))
+        return fail(MBB_ERR_ARG, "wavelengths must be positive");
+    if ((sp->derived & MBB_SUM_DUSTMASS) && !(sp->kappa > 0.0 && sp->kappa_wave > 0.0))
+        return fail(MBB_ERR_ARG, "kappa and kappa_wave must be positive");
+    return MBB_OK;
+}
+
+// The end of a call that filled derived columns: once the stream is idle, the upload of the per-source constants is over.
+static int derived_sync(mbb_ctx *c)
+{
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->der.src_in_flight = false;
+    return MBB_OK;
+}
+
+// ---- posterior summaries of a chain (mbb_summary.hip.h) ------------------------
 // Summarise a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
 static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
                        const mbb_summary_spec *sp, const mbb_summary_out *o)
@@ -2372,61 +2484,41 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
     if (sp->npct < 1 || sp->npct > kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per summary");
     for (int k = 0; k < sp->npct; ++k)
         if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
-    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
-    if (sp->derived & ~7) return fail(MBB_ERR_ARG, "unknown derived column");
     int rc;
-    if ((rc = summary_check_cosmology(sp, nsrc))) return rc;
-    if ((sp->derived & MBB_SUM_LIR) && !(sp->lir_wavemin > 0.0 && sp->lir_wavemax > 0.0))
-        return fail(MBB_ERR_ARG, "wavelengths must be positive");
-    if ((sp->derived & MBB_SUM_DUSTMASS) && !(sp->kappa > 0.0 && sp->kappa_wave > 0.0))
-        return fail(MBB_ERR_ARG, "kappa and kappa_wave must be positive");
-    const int nkept = (nsteps - sp->burn + sp->thin - 1) / sp->thin;
-    const long long n = (long long)nw * nkept;
-    if (n > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 samples per column");
-    const size_t cells = (size_t)nsrc * nw * nsteps;
+    if ((rc = check_window(sp, nsteps)) || (rc = check_derived_settings(sp, nsrc)) ||
+        (rc = check_sample_cap(sp, nw, nsteps)))
+        return rc;
     SumArgs a;
     memset(&a, 0, sizeof a);
-    a.chain = d_chain; a.lnprob = d_lnprob;
-    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin; a.nkept = nkept; a.n = n;
-    a.ncol = 5;
-    for (int k = 0; k < 5; ++k) a.col[k] = k;
-    for (int k = 0; k < 3; ++k) if ((sp->derived >> k) & 1) a.col[a.ncol++] = 5 + k;
+    fill_chain_view(a, d_chain, nsrc, nw, nsteps, sp, 16384);            // (splits of 64 samples per thread)
+    a.lnprob = d_lnprob;
     a.npct = sp->npct;
     for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
     for (int k = 0; k < kCols; ++k) {
         a.has_lo[k] = sp->has_lo[k] != 0; a.has_hi[k] = sp->has_hi[k] != 0;
         a.lo[k] = sp->lo[k]; a.hi[k] = sp->hi[k];
     }
-    // One workgroup per (source, column) when those fill the device by themselves; else a column is cut into
-    // splits of at most 16384 samples (64 per thread) whose partial sums and histograms are merged.
-    const size_t ncolumns = (size_t)nsrc * a.ncol;
-    a.splits = ncolumns >= 1024 ? 1 : (int)std::min<long long>(kMaxSplits, (n + 16383) / 16384);
-    a.per_split = (n + a.splits - 1) / a.splits;
+    const size_t ncolumns = (size_t)nsrc * a.ncol, sc = (size_t)nsrc * kCols, ns = (size_t)nsrc;
     mbb_ctx::SumWork &w = c->sum;
     const size_t np = (size_t)sp->npct;
-    const size_t nd = (size_t)nsrc * (kCols * (3 + np) + 25 + 6);           // doubles of the result block
-    const size_t out_bytes = (size_t)nsrc * kCols * sizeof(long long) + nd * sizeof(double) +
-                             (size_t)nsrc * (kCols + 2) * sizeof(int);
-    if ((rc = sum_grow(c, &w.part, &w.c_part, ncolumns * a.splits * kStatWords * sizeof(double)))) return rc;
-    if ((rc = sum_grow(c, &w.state, &w.c_state, ncolumns * sizeof(ColState)))) return rc;
-    if ((rc = sum_grow(c, &w.hist, &w.c_hist, ncolumns * a.splits * kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
-    if ((rc = sum_grow(c, &w.covpart, &w.c_covpart, (size_t)nsrc * a.splits * kCovWords * sizeof(double)))) return rc;
-    if ((rc = sum_grow(c, &w.colstatus, &w.c_colstatus, (size_t)nsrc * kCols * sizeof(int)))) return rc;
-    if ((rc = sum_grow(c, &w.outbuf, &w.c_outbuf, out_bytes))) return rc;
-    a.part = (double *)w.part; a.state = (ColState *)w.state; a.hist = (unsigned int *)w.hist;
-    a.covpart = (double *)w.covpart; a.colstatus = (int *)w.colstatus;
-    char *ob = (char *)w.outbuf;
-    a.o_nused = (long long *)ob;
-    a.o_mean = (double *)(ob + (size_t)nsrc * kCols * sizeof(long long));
-    a.o_min = a.o_mean + (size_t)nsrc * kCols;
-    a.o_max = a.o_min + (size_t)nsrc * kCols;
-    a.o_pct = a.o_max + (size_t)nsrc * kCols;
-    a.o_cov = a.o_pct + (size_t)nsrc * kCols * np;
-    a.o_best = a.o_cov + (size_t)nsrc * 25;
-    a.o_status = (int *)(a.o_best + (size_t)nsrc * 6);
-    a.o_bestidx = a.o_status + (size_t)nsrc * kCols;
-    HIPCHK(hipMemsetAsync(w.colstatus, 0, (size_t)nsrc * kCols * sizeof(int), c->stream));
-    if ((rc = summary_fill_derived(c, sp, a, cells))) return rc;
+    // the result block: 64-bit counts, doubles, 32-bit words
+    const size_t out_bytes = sc * sizeof(long long) + (sc * (3 + np) + ns * (25 + 6)) * sizeof(double) +
+                             (sc + ns * 2) * sizeof(int);
+    if ((rc = grow(c, w.part, ncolumns * a.splits * kStatWords * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.state, ncolumns * sizeof(ColState)))) return rc;
+    if ((rc = grow(c, w.hist, ncolumns * a.splits * kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    if ((rc = grow(c, w.covpart, ns * a.splits * kCovWords * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    a.part = (double *)w.part.p; a.state = (ColState *)w.state.p; a.hist = (unsigned int *)w.hist.p;
+    a.covpart = (double *)w.covpart.p;
+    Carve ob{(char *)w.outbuf.p};
+    a.o_nused = ob.take<long long>(sc);
+    a.o_mean = ob.take<double>(sc); a.o_min = ob.take<double>(sc); a.o_max = ob.take<double>(sc);
+    a.o_pct = ob.take<double>(sc * np);
+    a.o_cov = ob.take<double>(ns * 25); a.o_best = ob.take<double>(ns * 6);
+    a.o_status = ob.take<int>(sc); a.o_bestidx = ob.take<int>(ns * 2);
+    if ((rc = summary_fill_derived(c, sp, a))) return rc;
+    a.colstatus = (int *)c->der.colstatus.p;
     const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits), gsrc((unsigned)nsrc, (unsigned)a.splits);
     hipLaunchKernelGGL(k_sum_stats, gcol, dim3(kThreads), 0, c->stream, a);
     hipLaunchKernelGGL(k_sum_begin, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a);
@@ -2438,22 +2530,14 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
     hipLaunchKernelGGL(k_sum_finish, dim3((unsigned)(((size_t)nsrc * kCols + 63) / 64)), dim3(64), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    w.src_in_flight = false;
-    const char *hb = host.data();
-    const size_t sc = (size_t)nsrc * kCols;
-    memcpy(o->n_used, hb, sc * sizeof(long long));
-    const double *hd = (const double *)(hb + sc * sizeof(long long));
-    memcpy(o->mean, hd, sc * sizeof(double));
-    memcpy(o->min, hd + sc, sc * sizeof(double));
-    memcpy(o->max, hd + 2 * sc, sc * sizeof(double));
-    memcpy(o->pct, hd + 3 * sc, sc * np * sizeof(double));
-    memcpy(o->cov, hd + 3 * sc + sc * np, (size_t)nsrc * 25 * sizeof(double));
-    memcpy(o->best, hd + 3 * sc + sc * np + (size_t)nsrc * 25, (size_t)nsrc * 6 * sizeof(double));
-    const int *hi = (const int *)(hd + nd);
-    memcpy(o->status, hi, sc * sizeof(int));
-    memcpy(o->best_index, hi + sc, (size_t)nsrc * 2 * sizeof(int));
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = derived_sync(c))) return rc;
+    Carve hb{host.data()};
+    hb.put(o->n_used, sc);
+    hb.put(o->mean, sc); hb.put(o->min, sc); hb.put(o->max, sc);
+    hb.put(o->pct, sc * np);
+    hb.put(o->cov, ns * 25); hb.put(o->best, ns * 6);
+    hb.put(o->status, sc); hb.put(o->best_index, ns * 2);
     return MBB_OK;
 }
 
@@ -2466,36 +2550,22 @@ extern "C" int mbb_chain_summary(mbb_ctx *c, const double *chain, const double *
     // (per-source values are checked before the chain goes up; everything else where it always was, in summary_run)
     if (spec && (spec->src_redshift || spec->src_lumdist_mpc) && (rc = summary_check_cosmology(spec, nsrc))) return rc;
     const size_t cells = (size_t)nsrc * nw * nsteps;
-    double *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, cells * 6 * sizeof(double)));
-    hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + cells * 5, lnprob, cells * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(MBB_ERR_HIP, "upload of the chain", e); }
-    rc = summary_run(c, d, d + cells * 5, nsrc, nw, nsteps, spec, out);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    return rc;
+    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
+        return summary_run(c, d, d + cells * 5, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 extern "C" int mbb_sampler_run_summary(mbb_ctx *c, void *sp, int nsteps, double stretch_a, const mbb_summary_spec *spec,
                                        const mbb_summary_out *out, double *chain, double *lnprob, double *pos_out,
                                        double *lnprob_out, double *naccepted)
 {
-    int rc = use(c);
+    mbb_sampler_state *s;
+    int rc = analysed_sampler(c, sp, nsteps >= 0 && stretch_a > 1.0 && spec && out, "summarised", s);
     if (rc) return rc;
-    mbb_sampler_state *s = (mbb_sampler_state *)sp;
-    if (!s || nsteps < 0 || !(stretch_a > 1.0) || !spec || !out) return fail(MBB_ERR_ARG, "bad sampler arguments");
-    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
-    ShardPlan p;
-    if ((rc = shard_plan(c, s, p))) return rc;
-    if (p.collective)
-        return fail(MBB_ERR_STATE, "a sharded sampler run cannot be summarised on the device: a rank holds only its own "
-                                   "walkers' chain");
     // (per-source values are checked before the run; everything else where it always was, in summary_run)
     if ((spec->src_redshift || spec->src_lumdist_mpc) && (rc = summary_check_cosmology(spec, s->nsrc))) return rc;
     if (nsteps == 0) {
-        if (s->resident_nsteps <= 0)
-            return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
+        if ((rc = resident_chain(s))) return rc;
         const size_t cells = (size_t)s->rows() * s->resident_nsteps;
         return summary_run(c, s->d_chain_out, s->d_chain_out + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
     }
@@ -2538,17 +2608,15 @@ static int diag_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.n = n;
     a.method = sp->method; a.nacf = (int)nacf; a.c = sp->c; a.tol = sp->tol;
     mbb_ctx::DiagWork &w = c->diag;
-    const size_t nd = ncol * (3 + nacf), out_bytes = nd * sizeof(double) + ncol * 2 * sizeof(int);
-    if (sp->method == MBB_DIAG_MEAN && (rc = sum_grow(c, &w.mean, &w.c_mean, ncol * n * sizeof(double)))) return rc;
-    if ((rc = sum_grow(c, &w.seq, &w.c_seq, ncol * nw * 4 * sizeof(double)))) return rc;
-    if ((rc = sum_grow(c, &w.outbuf, &w.c_outbuf, out_bytes))) return rc;
-    a.mean = (double *)w.mean; a.seq = (double *)w.seq;
-    a.o_tau = (double *)w.outbuf;
-    a.o_ess = a.o_tau + ncol;
-    a.o_rhat = a.o_ess + ncol;
-    a.o_acf = nacf ? a.o_rhat + ncol : nullptr;
-    a.o_window = (int *)((double *)w.outbuf + nd);
-    a.o_status = a.o_window + ncol;
+    const size_t out_bytes = ncol * (3 + nacf) * sizeof(double) + ncol * 2 * sizeof(int);   // the result block
+    if (sp->method == MBB_DIAG_MEAN && (rc = grow(c, w.mean, ncol * n * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.seq, ncol * nw * 4 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    a.mean = (double *)w.mean.p; a.seq = (double *)w.seq.p;
+    Carve ob{(char *)w.outbuf.p};
+    a.o_tau = ob.take<double>(ncol); a.o_ess = ob.take<double>(ncol); a.o_rhat = ob.take<double>(ncol);
+    a.o_acf = nacf ? ob.take<double>(ncol * nacf) : nullptr;
+    a.o_window = ob.take<int>(ncol); a.o_status = ob.take<int>(ncol);
     const size_t lds = acf_lds_bytes(n);
     if (lds > 60 * 1024 && lds > w.lds_granted) {
         // (beyond 64 KB of LDS per workgroup, the kernel's 2.3 KB of static LDS included, its dynamic-LDS ceiling has
@@ -2570,16 +2638,12 @@ static int diag_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     hipLaunchKernelGGL(k_diag_rhat, dim3((unsigned)ncol), dim3(kThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    const double *hd = (const double *)host.data();
-    memcpy(o->tau, hd, ncol * sizeof(double));
-    memcpy(o->ess, hd + ncol, ncol * sizeof(double));
-    memcpy(o->rhat, hd + 2 * ncol, ncol * sizeof(double));
-    if (nacf) memcpy(o->acf, hd + 3 * ncol, ncol * nacf * sizeof(double));
-    const int *hi = (const int *)(hd + nd);
-    memcpy(o->window, hi, ncol * sizeof(int));
-    memcpy(o->status, hi + ncol, ncol * sizeof(int));
+    Carve hb{host.data()};
+    hb.put(o->tau, ncol); hb.put(o->ess, ncol); hb.put(o->rhat, ncol);
+    if (nacf) hb.put(o->acf, ncol * nacf);
+    hb.put(o->window, ncol); hb.put(o->status, ncol);
     return MBB_OK;
 }
 
@@ -2590,31 +2654,16 @@ extern "C" int mbb_chain_diagnostics(mbb_ctx *c, const double *chain, int nsrc, 
     if (rc) return rc;
     if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
     if ((rc = diag_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
-    const size_t cells = (size_t)nsrc * nw * nsteps;
-    double *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, cells * 5 * sizeof(double)));
-    hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(MBB_ERR_HIP, "upload of the chain", e); }
-    rc = diag_run(c, d, nsrc, nw, nsteps, spec, out);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    return rc;
+    return with_uploaded_chain(c, chain, nullptr, (size_t)nsrc * nw * nsteps, [&](const double *d) {
+        return diag_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 extern "C" int mbb_sampler_diagnostics(mbb_ctx *c, void *sp, const mbb_diag_spec *spec, const mbb_diag_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    mbb_sampler_state *s = (mbb_sampler_state *)sp;
-    if (!s || !spec || !out) return fail(MBB_ERR_ARG, "bad sampler arguments");
-    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
-    ShardPlan p;
-    if ((rc = shard_plan(c, s, p))) return rc;
-    if (p.collective)
-        return fail(MBB_ERR_STATE, "a sharded sampler run cannot be diagnosed on the device: a rank holds only its own "
-                                   "walkers' chain");
-    if (s->resident_nsteps <= 0 || !s->d_chain_out)
-        return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, spec && out, "diagnosed", s)) || (rc = resident_chain(s))) return rc;
     return diag_run(c, s->d_chain_out, s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 
@@ -2638,8 +2687,8 @@ static int marg_check(int nsrc, int nw, int nsteps, const mbb_marginals_spec *sp
         (two && !o->counts2) || (sp->nbins2 > 0 && !o->edges2))
         return fail(MBB_ERR_ARG, "null marginals argument");
     const mbb_summary_spec *ss = sp->summary;
-    if (ss->burn < 0 || ss->burn >= nsteps || ss->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
-    if (ss->derived & ~7) return fail(MBB_ERR_ARG, "unknown derived column");
+    int rc;
+    if ((rc = check_window(ss, nsteps))) return rc;
     const auto present = [&](int slot) { return slot >= 0 && slot < kCols && (slot < 5 || ((ss->derived >> (slot - 5)) & 1)); };
     for (int k = 0; k < sp->npairs; ++k) {
         const int a = sp->pairs[k][0], b = sp->pairs[k][1];
@@ -2652,14 +2701,7 @@ static int marg_check(int nsrc, int nw, int nsteps, const mbb_marginals_spec *sp
         if (!(lo - lo == 0.0 && hi - hi == 0.0 && lo < hi && (hi - lo) - (hi - lo) == 0.0))
             return fail(MBB_ERR_ARG, "a range must be finite with lo < hi");
     }
-    int rc;
-    if ((rc = summary_check_cosmology(ss, nsrc))) return rc;
-    if ((ss->derived & MBB_SUM_LIR) && !(ss->lir_wavemin > 0.0 && ss->lir_wavemax > 0.0))
-        return fail(MBB_ERR_ARG, "wavelengths must be positive");
-    if ((ss->derived & MBB_SUM_DUSTMASS) && !(ss->kappa > 0.0 && ss->kappa_wave > 0.0))
-        return fail(MBB_ERR_ARG, "kappa and kappa_wave must be positive");
-    const int nkept = (nsteps - ss->burn + ss->thin - 1) / ss->thin;
-    if ((long long)nw * nkept > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 samples per column");
+    if ((rc = check_derived_settings(ss, nsrc)) || (rc = check_sample_cap(ss, nw, nsteps))) return rc;
     if ((size_t)nsrc * (kCols + kMaxPairs) > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
     return MBB_OK;
 }
@@ -2671,58 +2713,38 @@ static int marg_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     using namespace mbbm;
     int rc;
     if ((rc = marg_check(nsrc, nw, nsteps, sp, o))) return rc;
-    const mbb_summary_spec *ss = sp->summary;
-    const int nkept = (nsteps - ss->burn + ss->thin - 1) / ss->thin;
-    const long long n = (long long)nw * nkept;
-    const size_t cells = (size_t)nsrc * nw * nsteps;
     MargArgs a;
     memset(&a, 0, sizeof a);
-    a.chain = d_chain;
-    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = ss->burn; a.thin = ss->thin; a.nkept = nkept; a.n = n;
-    a.ncol = 5;
-    for (int k = 0; k < 5; ++k) a.col[k] = k;
-    for (int k = 0; k < 3; ++k) if ((ss->derived >> k) & 1) a.col[a.ncol++] = 5 + k;
+    // (summary_run's splits at a finer grain: a table costs no floating-point tree over the splits, and a single
+    // source's five columns are otherwise twenty workgroups)
+    fill_chain_view(a, d_chain, nsrc, nw, nsteps, sp->summary, kSplitSamples);
     a.nbins = sp->nbins;
     a.nbins2 = sp->nbins2;
     a.npairs = sp->nbins2 > 0 ? sp->npairs : 0;
     for (int k = 0; k < a.npairs; ++k) { a.pair[k][0] = sp->pairs[k][0]; a.pair[k][1] = sp->pairs[k][1]; }
     for (int k = 0; k < kCols; ++k) { a.has_range[k] = sp->has_range[k] != 0; a.lo[k] = sp->lo[k]; a.hi[k] = sp->hi[k]; }
-    // One workgroup per (source, column or pair) when those fill the device by themselves; else a column is cut into
-    // splits of at most kSplitSamples samples whose tables are merged (summary_run's scheme at a finer grain: a
-    // table costs no floating-point tree, and a single source's five columns are otherwise twenty workgroups).
     const size_t ncolumns = (size_t)nsrc * a.ncol, npairs = (size_t)nsrc * a.npairs;
-    a.splits = ncolumns >= 1024 ? 1 : (int)std::min<long long>(kMaxSplits, (n + kSplitSamples - 1) / kSplitSamples);
-    a.per_split = (n + a.splits - 1) / a.splits;
     const size_t sc = (size_t)nsrc * kCols, nb = (size_t)a.nbins, nb2 = (size_t)a.nbins2;
     // the result block: doubles, 64-bit counts, 32-bit words
     const size_t n_e1 = sc * (nb + 1), n_e2 = nb2 ? sc * (nb2 + 1) : 0, n_c1 = sc * nb, n_c2 = npairs * nb2 * nb2;
     const size_t out_bytes = (n_e1 + n_e2) * sizeof(double) + 4 * sc * sizeof(long long) +
                              (n_c1 + n_c2) * sizeof(unsigned int) + sc * sizeof(int);
     mbb_ctx::MargWork &w = c->marg;
-    if ((rc = sum_grow(c, &w.extent, &w.c_extent, ncolumns * a.splits * 2 * sizeof(double)))) return rc;
-    if ((rc = sum_grow(c, &w.range, &w.c_range, sc * sizeof(Range)))) return rc;
-    if ((rc = sum_grow(c, &w.part1, &w.c_part1, ncolumns * a.splits * (nb + kTail) * sizeof(unsigned int)))) return rc;
-    if (npairs && (rc = sum_grow(c, &w.part2, &w.c_part2, npairs * a.splits * nb2 * nb2 * sizeof(unsigned int)))) return rc;
-    if ((rc = sum_grow(c, &w.outbuf, &w.c_outbuf, out_bytes))) return rc;
-    if ((rc = sum_grow(c, &c->sum.colstatus, &c->sum.c_colstatus, sc * sizeof(int)))) return rc;
-    a.extent = (double *)w.extent; a.range = (Range *)w.range;
-    a.part1 = (unsigned int *)w.part1; a.part2 = (unsigned int *)w.part2;
-    a.colstatus = (const int *)c->sum.colstatus;
-    a.o_edges1 = (double *)w.outbuf;
-    a.o_edges2 = a.o_edges1 + n_e1;
-    a.o_used = (long long *)(a.o_edges2 + n_e2);
-    a.o_below = a.o_used + sc; a.o_above = a.o_below + sc; a.o_nonfinite = a.o_above + sc;
-    a.o_counts1 = (unsigned int *)(a.o_nonfinite + sc);
-    a.o_counts2 = a.o_counts1 + n_c1;
-    a.o_status = (int *)(a.o_counts2 + n_c2);
-    HIPCHK(hipMemsetAsync(c->sum.colstatus, 0, sc * sizeof(int), c->stream));
-    // the derived columns: the summary's own fill, through a SumArgs that carries what it reads
-    mbbs::SumArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.chain = d_chain;
-    sa.nsrc = nsrc; sa.nw = nw; sa.nsteps = nsteps; sa.burn = ss->burn; sa.thin = ss->thin;
-    if ((rc = summary_fill_derived(c, ss, sa, cells))) return rc;
-    for (int k = 0; k < 3; ++k) a.der[k] = sa.der[k];
+    if ((rc = grow(c, w.extent, ncolumns * a.splits * 2 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.range, sc * sizeof(Range)))) return rc;
+    if ((rc = grow(c, w.part1, ncolumns * a.splits * (nb + kTail) * sizeof(unsigned int)))) return rc;
+    if (npairs && (rc = grow(c, w.part2, npairs * a.splits * nb2 * nb2 * sizeof(unsigned int)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    a.extent = (double *)w.extent.p; a.range = (Range *)w.range.p;
+    a.part1 = (unsigned int *)w.part1.p; a.part2 = (unsigned int *)w.part2.p;
+    Carve ob{(char *)w.outbuf.p};
+    a.o_edges1 = ob.take<double>(n_e1); a.o_edges2 = ob.take<double>(n_e2);
+    a.o_used = ob.take<long long>(sc); a.o_below = ob.take<long long>(sc);
+    a.o_above = ob.take<long long>(sc); a.o_nonfinite = ob.take<long long>(sc);
+    a.o_counts1 = ob.take<unsigned int>(n_c1); a.o_counts2 = ob.take<unsigned int>(n_c2);
+    a.o_status = ob.take<int>(sc);
+    if ((rc = summary_fill_derived(c, sp->summary, a))) return rc;
+    a.colstatus = (const int *)c->der.colstatus.p;
     const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
     hipLaunchKernelGGL(k_marg_extent, gcol, dim3(kThreads), 0, c->stream, a);
     hipLaunchKernelGGL(k_marg_edges, dim3((unsigned)sc), dim3(kThreads), 0, c->stream, a);
@@ -2740,9 +2762,7 @@ static int marg_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     HIPCHK(hipMemcpyAsync(o->counts1, a.o_counts1, n_c1 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     if (n_c2) HIPCHK(hipMemcpyAsync(o->counts2, a.o_counts2, n_c2 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(o->status, a.o_status, sc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->sum.src_in_flight = false;
-    return MBB_OK;
+    return derived_sync(c);
 }
 
 extern "C" int mbb_chain_marginals(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
@@ -2752,31 +2772,16 @@ extern "C" int mbb_chain_marginals(mbb_ctx *c, const double *chain, int nsrc, in
     if (rc) return rc;
     if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
     if ((rc = marg_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
-    const size_t cells = (size_t)nsrc * nw * nsteps;
-    double *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, cells * 5 * sizeof(double)));
-    hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(MBB_ERR_HIP, "upload of the chain", e); }
-    rc = marg_run(c, d, nsrc, nw, nsteps, spec, out);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    return rc;
+    return with_uploaded_chain(c, chain, nullptr, (size_t)nsrc * nw * nsteps, [&](const double *d) {
+        return marg_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 extern "C" int mbb_sampler_marginals(mbb_ctx *c, void *sp, const mbb_marginals_spec *spec, const mbb_marginals_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    mbb_sampler_state *s = (mbb_sampler_state *)sp;
-    if (!s || !spec || !out) return fail(MBB_ERR_ARG, "bad sampler arguments");
-    if (s->nsrc != c->nsrc) return fail(MBB_ERR_STATE, "number of sources changed since the sampler was made");
-    ShardPlan p;
-    if ((rc = shard_plan(c, s, p))) return rc;
-    if (p.collective)
-        return fail(MBB_ERR_STATE, "a sharded sampler run cannot be binned on the device: a rank holds only its own "
-                                   "walkers' chain");
-    if (s->resident_nsteps <= 0 || !s->d_chain_out)
-        return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, spec && out, "binned", s)) || (rc = resident_chain(s))) return rc;
     return marg_run(c, s->d_chain_out, s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 

@@ -34,12 +34,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mbb_chain_view.hip.h"
 
 namespace mbbm {
 
-constexpr int kCols = 8;          // column slots, the summary's
+using mbbc::kCols;
+using mbbc::kMaxSplits;
 constexpr int kThreads = 256;
-constexpr int kMaxSplits = 64;
 constexpr int kSplitSamples = 4096;   // a split has at most this many samples (16 per thread) until kMaxSplits are reached
 constexpr int kMaxBins = 4096;    // 1-D: 16 KB of LDS
 constexpr int kMaxBins2 = 100;    // 2-D, per axis: 40 KB of LDS
@@ -51,14 +52,7 @@ constexpr int kStEmpty = 1, kStNonfinite = 2, kStAbsent = 4, kStRowShift = 8;
 
 struct Range { double lo, hi; };   // NaNs: nothing of the column is binned (absent, or no finite sample)
 
-struct MargArgs {
-    const double *chain;
-    const double *der[3];                   // the derived columns (slots 5, 6, 7) or null
-    int nsrc, nw, nsteps, burn, thin, nkept;
-    long long n;                            // samples per column: nw * nkept
-    int ncol, col[kCols];                   // the active column slots
-    int splits;
-    long long per_split;
+struct MargArgs : mbbc::ChainView {
     int nbins, nbins2, npairs;
     int pair[kMaxPairs][2];                 // slots (a, b), a < b
     int has_range[kCols];
@@ -75,14 +69,6 @@ struct MargArgs {
     long long *o_used, *o_below, *o_above, *o_nonfinite;   // [nsrc][kCols]
     int *o_status;                          // [nsrc][kCols]
 };
-
-// sample j of (source, column slot): its value
-__device__ __forceinline__ double sample(const MargArgs &a, int src, int slot, long long j)
-{
-    const long long w = j / a.nkept, k = j - w * a.nkept;
-    const long long flat = ((long long)src * a.nw + w) * a.nsteps + a.burn + k * a.thin;
-    return slot < 5 ? a.chain[flat * 5 + slot] : a.der[slot - 5][flat];
-}
 
 __device__ __forceinline__ bool finite(double v) { return v - v == 0.0; }   // (v - v: NaN for a NaN and for an infinity)
 

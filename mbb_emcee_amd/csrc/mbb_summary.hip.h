@@ -27,14 +27,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mbb_chain_view.hip.h"
 
 namespace mbbs {
 
-constexpr int kCols = 8;         // column slots: T, beta, lambda0, alpha, fnorm, peak wavelength, L_IR, dust mass
+using mbbc::kCols;
+using mbbc::kMaxSplits;
 constexpr int kMaxPct = 8;       // percentiles per call
 constexpr int kMaxRanks = 2 * kMaxPct;
 constexpr int kThreads = 256;
-constexpr int kMaxSplits = 64;
 constexpr int kStatWords = 8;    // doubles per (column, split) of k_sum_stats
 constexpr int kCovWords = 18;    // doubles per (source, split) of k_sum_cov: 15 products, best lnprob, best index, pad
 
@@ -51,14 +52,8 @@ struct ColState {
     int nan;
 };
 
-struct SumArgs {
-    const double *chain, *lnprob;
-    const double *der[3];                   // the derived columns (slots 5, 6, 7) or null
-    int nsrc, nw, nsteps, burn, thin, nkept;
-    long long n;                            // samples per column: nw * nkept
-    int ncol, col[kCols];                   // the active column slots
-    int splits;
-    long long per_split;
+struct SumArgs : mbbc::ChainView {
+    const double *lnprob;                   // [nsrc][nw][nsteps]
     int npct;
     double pct[kMaxPct];
     int has_lo[kCols], has_hi[kCols];
@@ -88,13 +83,6 @@ __device__ __forceinline__ double from_key(unsigned long long k)
     return __longlong_as_double((long long)b);
 }
 
-// sample j of (source, column slot): its value
-__device__ __forceinline__ double sample(const SumArgs &a, int src, int slot, long long j)
-{
-    const long long w = j / a.nkept, k = j - w * a.nkept;
-    const long long flat = ((long long)src * a.nw + w) * a.nsteps + a.burn + k * a.thin;
-    return slot < 5 ? a.chain[flat * 5 + slot] : a.der[slot - 5][flat];
-}
 __device__ __forceinline__ bool kept(const SumArgs &a, int slot, double v)
 {
     // _parcen_internal's clipping (results.py:351-367): a NaN fails either comparison and is dropped

@@ -171,7 +171,7 @@ class DeviceEnsembleSampler(object):
         ctx, h = self._handle()
         raw = diagnostics._Raw(self.nsources, req.nacf)
         spec, out = req.spec(), raw.out()
-        diagnostics._native_call(ctx.lib.mbb_sampler_diagnostics(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        _native.check_arg(ctx.lib.mbb_sampler_diagnostics(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return diagnostics.ChainDiagnostics(req, raw, self.nsources > 1, self.k, n)
 
     def marginals(self, **kw):
@@ -187,7 +187,7 @@ class DeviceEnsembleSampler(object):
         ctx, h = self._handle()
         raw = marginals._Raw(self.nsources, req.bins, req.bins2d, len(req.pairs))
         spec, out = req.spec(), raw.out()
-        marginals._native_call(ctx.lib.mbb_sampler_marginals(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        _native.check_arg(ctx.lib.mbb_sampler_marginals(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return marginals.ChainMarginals(req, raw, self.nsources > 1, self.k, nkept)
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
@@ -342,9 +342,7 @@ class DeviceEnsembleSampler(object):
                                                  _native._d(chain) if storechain else None,
                                                  _native._d(lnp) if storechain else None,
                                                  _native._d(pos), _native._d(lnprob), _native._d(nacc))
-        if rc == -2:
-            raise ValueError(ctx.lib.mbb_last_error().decode())
-        _native._check(rc)
+        _native.check_arg(rc, ctx)
         if ctx.info("flow_fallbacks") > fallbacks:
             import warnings
             warnings.warn("the one-launch form of the device sampler gave up waiting (a workgroup was not "
@@ -394,9 +392,7 @@ class DeviceEnsembleSampler(object):
         raw = results._Raw(self.nsources, len(req.qs))
         spec, out = req.spec(), raw.out()
         rc = ctx.lib.mbb_sampler_run_summary(ctx.h, h, 0, self.a, C.byref(spec), C.byref(out), None, None, None, None, None)
-        if rc == -2:
-            raise ValueError(ctx.lib.mbb_last_error().decode())
-        _native._check(rc)
+        _native.check_arg(rc, ctx)
         return raw
 
     def sample(self, p0, lnprob0=None, rstate0=None, iterations=1, storechain=True, chunk=64):

@@ -67,12 +67,6 @@ class _Raw(object):
         return o
 
 
-def _native_call(rc, ctx):
-    if rc == -2:
-        raise ValueError(ctx.lib.mbb_last_error().decode())
-    _native._check(rc)
-
-
 class ChainDiagnostics(object):
     """Convergence of a chain, per parameter (a leading source axis for a multi-source chain):
 
@@ -132,18 +126,14 @@ def chain_diagnostics(like, chain, burn=0, c=5.0, tol=50.0, method="mean", nacf=
     c : Sokal's window factor; tol : the chain is flagged UNRELIABLE below tol * tau steps;
     nacf : how many values of the autocorrelation function to return."""
     req = _Request(burn, c, tol, method, nacf)
-    chain = np.ascontiguousarray(chain, dtype=np.float64)
-    if chain.ndim not in (3, 4) or chain.shape[-1] != 5:
-        raise ValueError("chain must be [nwalkers, nsteps, 5] or [nsources, nwalkers, nsteps, 5]")
-    multi = chain.ndim == 4
-    c4 = chain if multi else chain[None]
+    c4, multi = _native.chain4(chain)
     nsrc, nw, nsteps = c4.shape[:3]
     if nsrc < 1 or nw < 1 or nsteps < 1:
         raise ValueError("the chain is empty")
     n = req.check_steps(nsteps)
-    ctx = like._sync_device() if like.data_read else like.context
+    ctx = _native.analysis_context(like, model=False)
     raw = _Raw(nsrc, req.nacf)
     spec, out = req.spec(), raw.out()
-    _native_call(ctx.lib.mbb_chain_diagnostics(ctx.h, _native._d(c4), nsrc, nw, nsteps, C.byref(spec), C.byref(out)),
-                 ctx)
+    _native.check_arg(ctx.lib.mbb_chain_diagnostics(ctx.h, _native._d(c4), nsrc, nw, nsteps, C.byref(spec),
+                                                    C.byref(out)), ctx)
     return ChainDiagnostics(req, raw, multi, nw, n)

@@ -124,12 +124,6 @@ class _Raw(object):
 RAW_FIELDS = ("counts1", "edges1", "counts2", "edges2", "n_used", "n_below", "n_above", "n_nonfinite", "status")
 
 
-def _native_call(rc, ctx):
-    if rc == -2:
-        raise ValueError(ctx.lib.mbb_last_error().decode())
-    _native._check(rc)
-
-
 def levels_of(H, fractions=(0.683, 0.954)):
     """Count thresholds of the highest-density regions of one table: for each fraction f the largest count c such
     that the bins with count >= c hold at least f of the binned samples (0 for an empty table)."""
@@ -265,21 +259,15 @@ def chain_marginals(like, chain, bins=64, bins2d=0, pairs="params", range=None, 
     range : ``{name: (lo, hi)}``, one range for every source; a column without one gets, per source, the min and max of
         its finite samples (``numpy.histogram``'s default), widened by 0.5 on either side when they are equal;
     derived, redshift, lumdist_mpc, kappa, kappa_wave, lir_range, peak_model : ``results.chain_summary``'s."""
-    chain = np.ascontiguousarray(chain, dtype=np.float64)
-    if chain.ndim not in (3, 4) or chain.shape[-1] != 5:
-        raise ValueError("chain must be [nwalkers, nsteps, 5] or [nsources, nwalkers, nsteps, 5]")
-    multi = chain.ndim == 4
-    c4 = chain if multi else chain[None]
+    c4, multi = _native.chain4(chain)
     nsrc, nw, nsteps = c4.shape[:3]
     if nsrc < 1 or nw < 1 or nsteps < 1:
         raise ValueError("the chain is empty")
     req = _Request(bins, bins2d, pairs, range, burn, thin, derived, redshift, lumdist_mpc, kappa, kappa_wave, lir_range,
                    peak_model, nsources=nsrc)
     nkept = req.check_steps(nsteps)
-    ctx = like._sync_device() if like.data_read else like.context
-    if not like.data_read:
-        ctx.set_model(like.opthin, like.noalpha, like.wavenorm)
+    ctx = _native.analysis_context(like)
     raw = _Raw(nsrc, req.bins, req.bins2d, len(req.pairs))
     spec, out = req.spec(), raw.out()
-    _native_call(ctx.lib.mbb_chain_marginals(ctx.h, _native._d(c4), nsrc, nw, nsteps, C.byref(spec), C.byref(out)), ctx)
+    _native.check_arg(ctx.lib.mbb_chain_marginals(ctx.h, _native._d(c4), nsrc, nw, nsteps, C.byref(spec), C.byref(out)), ctx)
     return ChainMarginals(req, raw, multi, nw, nkept)

@@ -169,22 +169,14 @@ class _Raw(object):
         return o
 
 
-def _native_call(rc, ctx):
-    if rc == -2:
-        raise ValueError(ctx.lib.mbb_last_error().decode())
-    _native._check(rc)
-
-
 def _summarise_host(like, chain, lnprob, req):
     """mbb_chain_summary on a host chain [nsrc, nw, nsteps, 5]."""
-    ctx = like._sync_device() if like.data_read else like.context
-    if not like.data_read:
-        ctx.set_model(like.opthin, like.noalpha, like.wavenorm)
+    ctx = _native.analysis_context(like)
     nsrc, nw, nsteps = lnprob.shape
     raw = _Raw(nsrc, len(req.qs))
     spec, out = req.spec(), raw.out()
-    _native_call(ctx.lib.mbb_chain_summary(ctx.h, _native._d(chain), _native._d(lnprob), nsrc, nw, nsteps,
-                                           C.byref(spec), C.byref(out)), ctx)
+    _native.check_arg(ctx.lib.mbb_chain_summary(ctx.h, _native._d(chain), _native._d(lnprob), nsrc, nw, nsteps,
+                                                C.byref(spec), C.byref(out)), ctx)
     return raw
 
 
@@ -205,14 +197,10 @@ def chain_summary(like, chain, lnprob, percentile=68.3, burn=0, thin=1, derived=
     unknown: its L_IR and dust mass are NaN (status ``SUM_HAS_NAN``), everything else is unaffected.
     clip : ``{param or derived name: (lowlim, uplim)}`` applied as ``_parcen_internal`` does (either may be None).
     keep : keep the chain with the result, so that other percentiles and clip bounds can be computed on demand."""
-    chain = np.ascontiguousarray(chain, dtype=np.float64)
     lnprob = np.ascontiguousarray(lnprob, dtype=np.float64)
-    if chain.ndim not in (3, 4) or chain.shape[-1] != 5:
-        raise ValueError("chain must be [nwalkers, nsteps, 5] or [nsources, nwalkers, nsteps, 5]")
-    if lnprob.shape != chain.shape[:-1]:
+    c4, multi = _native.chain4(chain)
+    if lnprob.shape != c4.shape[0 if multi else 1:3]:
         raise ValueError("lnprob must have the chain's shape without its last axis")
-    multi = chain.ndim == 4
-    c4 = chain if multi else chain[None]
     l3 = lnprob if multi else lnprob[None]
     if int(burn) >= c4.shape[2]:
         raise ValueError("burn leaves no step of the chain")

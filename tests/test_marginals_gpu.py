@@ -298,6 +298,52 @@ def test_a_source_of_unknown_redshift(mbb):
     assert "no finite sample" not in str(got)                             # (the first source)
 
 
+SUMMARY_FIELDS = ("n_used", "mean", "min", "max", "pct", "status", "cov", "best", "best_index")
+MARGINALS_FIELDS = ("counts1", "edges1", "counts2", "edges2", "n_used", "n_below", "n_above", "n_nonfinite", "status")
+
+
+def _bits(a):
+    return a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+def test_summary_and_marginals_share_the_derived_column_state(mbb):
+    """The derived columns, their per-source constants and their row-status words are one state of the context, used
+    by the summary and by the marginals.  Four calls in turn on ONE context -- a summary with per-source redshifts
+    (source 1's unknown), marginals with L_IR alone and one redshift, the summary again, marginals with all three
+    columns and the per-source arrays: every array of every result, status words included, has the bits of the same
+    call made on a context of its own."""
+    chain, lnprob = SR.distinct_chain(3, 8, 40, seed=12)
+    zs, dls = np.array([Z, np.nan, 0.9]), np.array([DL, 9000.0, 6000.0])
+    win = dict(burn=4, thin=3)
+
+    def fresh():
+        opthin, noalpha = MODELS["thick_walpha"]
+        lk = mbb.likelihood(response=False, opthin=opthin, noalpha=noalpha)
+        lk.set_phot(WAVE, np.full(4, 10.0), np.full(4, 2.0))
+        return lk
+
+    def summary(lk):
+        return mbb.chain_summary(lk, chain, lnprob, derived=DERIVED, redshift=zs, lumdist_mpc=dls, keep=False, **win)
+
+    calls = [
+        (summary, SUMMARY_FIELDS),
+        (lambda lk: mbb.chain_marginals(lk, chain, bins=16, bins2d=8, pairs="all", derived=("lir",), redshift=Z,
+                                        lumdist_mpc=DL, **win), MARGINALS_FIELDS),
+        (summary, SUMMARY_FIELDS),
+        (lambda lk: mbb.chain_marginals(lk, chain, bins=16, bins2d=8, pairs="all", derived=DERIVED, redshift=zs,
+                                        lumdist_mpc=dls, **win), MARGINALS_FIELDS),
+    ]
+    shared = fresh()
+    for k, (call, fields) in enumerate(calls):
+        got, want = call(shared), call(fresh())
+        for f in fields:
+            a, b = getattr(got._raw, f), getattr(want._raw, f)
+            assert a.dtype == b.dtype and a.shape == b.shape and a.size > 0, (k, f)
+            assert np.array_equal(_bits(a), _bits(b)), (k, f)
+    # (the calls did what they were asked: source 1's L_IR and dust mass are unknown to both analyses)
+    assert np.all(got.status[1, 6:] == (got.EMPTY | got.NONFINITE)) and np.all(got.status[0] == 0)
+
+
 # ---------------------------------------------------------------- through the layers
 NW, NSTEPS = 34, 64
 RAW_FIELDS = ("counts1", "edges1", "counts2", "edges2", "n_used", "n_below", "n_above", "n_nonfinite", "status")
