@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -107,6 +108,7 @@ static void (*const g_kernel[kNumSlots])(const LikeArgs) = {MBB_MODELS(MBB_LNLIK
 #undef MBB_FLOWA_V
 #undef MBB_SERVE_V
 #include "mbb_host_tables.h"
+#include "mbb_owned.h"
 #include "mbb_registry.h"
 
 static_assert(kPolyBDoubles == mbbh::kPolyBCount * mbbh::kPolyStride && mbbh::kPolyStride == mbbm::kPolyStride, "poly table size");
@@ -179,14 +181,49 @@ static int load_rccl()
     return MBB_OK;
 }
 
-// A device buffer that is grown when a call needs more (grow), never shrinks and is freed with the context it is in.
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+// The runtime under the owners of mbb_owned.h: every device and pinned block the library keeps is made and freed here.
+using mbbo::DevBuf;
+using mbbo::Dev;
+using mbbo::Pin;
+int mbbo::dev_alloc(void **p, size_t bytes, DevKind kind)
+{
+    if (kind == kDevFine) HIPCHK(hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained));
+    else HIPCHK(hipMalloc(p, bytes));
+    return MBB_OK;
+}
+int mbbo::dev_free(void *p)
+{
+    HIPCHK(hipFree(p));
+    return MBB_OK;
+}
+int mbbo::pin_alloc(void **p, void **alias, size_t bytes, PinKind kind)
+{
+    // mapped AND coherent (fine-grained): a kernel's stores to the block must become visible to the polling host
+    // while the kernel is still running, whatever HIP_HOST_COHERENT defaults to
+    HIPCHK(hipHostMalloc(p, bytes, kind == kPinMapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault));
+    if (kind == kPinMapped) {
+        const hipError_t e = hipHostGetDevicePointer(alias, *p, 0);
+        if (e != hipSuccess) { (void)pin_free(*p); return fail(MBB_ERR_HIP, "hipHostGetDevicePointer(alias, *p, 0)", e); }
+    }
+    return MBB_OK;
+}
+int mbbo::pin_free(void *p)
+{
+    HIPCHK(hipHostFree(p));
+    return MBB_OK;
+}
+
+// Two events, made when first asked for and destroyed with whatever holds them.
+struct EventPair {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    ~EventPair() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
+    int create()
+    {
+        for (hipEvent_t &ev : e) if (!ev) HIPCHK(hipEventCreate(&ev));
+        return MBB_OK;
+    }
 };
 
 struct mbb_ctx {
@@ -200,14 +237,18 @@ struct mbb_ctx {
     int nb = 0, nseg = 0, nunit = 0, npart = 0, nchunk = 0, nq = 0;
     long t_prep_ns = 0, t_launch_ns = 0, t_wait_ns = 0;   // phases of the last mbb_lnlike_batch
     int simd_chunks[4] = {0, 0, 0, 0};   // chunks dealt to each SIMD position by the unit table
-    double *d_nu = nullptr, *d_lnnu = nullptr, *d_wt = nullptr;
-    double *d_poly_b = nullptr, *d_poly_c = nullptr;     // piecewise polynomials of the sample loop
-    int2 *d_band_rng = nullptr;
-    int32_t *d_tail_slot = nullptr;
-    int4 *d_unit_tab = nullptr;
+    // Every device or pinned block below is an owner (mbb_owned.h), grouped with its capacity: it is remade through grow()
+    // and freed with the context.
+    struct BandTabs {
+        Dev<double> nu, lnnu, wt;
+        Dev<int4> unit_tab;
+        Dev<int2> band_rng;
+        Dev<int32_t> tail_slot;
+    } band;
+    double *d_poly_b = nullptr, *d_poly_c = nullptr;     // piecewise polynomials of the sample loop: the device's, not the context's
     // data
     int data_nb = 0, has_cov = 0, nsrc = 1;
-    double *d_flux = nullptr, *d_ivar = nullptr, *d_invcov = nullptr;
+    struct Data { Dev<double> flux, ivar, invcov; } data;
     // limits and priors (likelihood.py:73, :83-85 defaults)
     double lowlim[5] = {1, 0.1, 1, 0.1, 1e-3};
     double uplim[6] = {INFINITY, 20.0, INFINITY, 20.0, INFINITY, INFINITY};
@@ -216,18 +257,20 @@ struct mbb_ctx {
     double givar[6] = {1, 1, 1, 1, 1, 1};
     uint32_t has_gprior = 0;
     // staging for the host-in / host-out path
-    size_t cap = 0, cap_flux = 0;
-    double *d_pars = nullptr, *d_lnl = nullptr, *d_mflux = nullptr;
-    int32_t *d_status = nullptr;
-    double *h_pars = nullptr, *h_lnl = nullptr, *h_mflux = nullptr;   // pinned
-    double *w_pars = nullptr;    // device memory the host writes through the PCIe BAR (fine-grained), or null
-    double *dv_pars = nullptr, *dv_lnl = nullptr, *dv_mflux = nullptr;   // the pinned blocks as the device addresses them
-    int32_t *dv_status = nullptr;
+    struct Boundary {
+        size_t cap = 0, cap_flux = 0;             // rows; model fluxes
+        Dev<double> d_pars, d_lnl, d_mflux;
+        Dev<int32_t> d_status;
+        Pin<double> h_pars, h_lnl, h_mflux;       // pinned, and (dv()) as the device addresses them
+        Pin<int32_t> h_status;
+        Dev<double> w_pars{mbbo::kDevFine};       // device memory the host writes through the PCIe BAR (fine-grained), or empty
+    } bnd;
     // the served boundary (k_serve, mbb_serve.hip.h): a kernel that stays resident between a host-driven sampler's calls
-    unsigned long long *w_door = nullptr;     // its doorbell: a word of fine-grained device memory the host writes through the BAR
-    double *h_srv = nullptr, *dv_srv = nullptr;   // pinned: a server's result records [row]{lnl, status as a 64-bit integer}
-    size_t srv_cap = 0;
-    unsigned long long *h_gone = nullptr;     // pinned: the number of the last request a server saw before it left (0: still there)
+    struct ServeMem {
+        Dev<unsigned long long> w_door{mbbo::kDevFine};   // its doorbell: a word of fine-grained device memory the host writes through the BAR
+        Pin<double> h_srv;                        // pinned: a server's result records [row]{lnl, status as a 64-bit integer}
+        Pin<unsigned long long> h_gone;           // pinned: the number of the last request a server saw before it left (0: still there)
+    } srv;
     // The serve state below is a context's own -- except that a SIBLING context coming to the device tells this one's
     // server to leave (yield_server), possibly from another thread (ctypes and the _mbbfast extension release the GIL).
     // srv_mu guards it: held by the owner for the whole of mbb_lnlike_call and of use(), taken by a visitor (try_lock
@@ -266,16 +309,19 @@ struct mbb_ctx {
     double *call_in = nullptr;   // mbb_boundary_buffers: where the caller writes its rows (w_pars or h_pars)
     size_t call_cap = 0;         // ... and the capacity that answer was given for
     hipFunction_t mod_fn[kNumSlots] = {};   // the kernels' module handles, by slot (kernel_slot)
-    double *d_gather = nullptr, *h_gather = nullptr;   // sharded boundary: every rank's lnprob, device / pinned landing place
-    size_t gather_cap = 0;
+    struct Gather {                                    // sharded boundary: every rank's lnprob, device / pinned landing place
+        Dev<double> d;
+        Pin<double> h{mbbo::kPinDefault};
+    } gather;
     int large_bar = -1;
-    int32_t *h_status = nullptr;
     // scratch for SED-level calls
-    size_t sed_cap = 0, sed_out_cap = 0;
-    double *d_sed_pars = nullptr, *d_sed_out = nullptr;
-    int32_t *d_sed_status = nullptr;
-    WalkerK *d_sed_wk = nullptr;
-    // Work buffers of the chain analyses: grown as needed (grow), kept for the next call.  The derived columns of a
+    struct SedWork {
+        size_t cap = 0, out_cap = 0;                   // rows; output values
+        Dev<double> pars, out;
+        Dev<int32_t> status;
+        Dev<WalkerK> wk;
+    } sed;
+    // Work buffers of the chain analyses.  The derived columns of a
     // chain (summary_fill_derived), for the summary and the marginals alike:
     struct DerWork {
         DevBuf der, src, colstatus;           // the columns, the per-source constants, [nsrc][kCols] row-status bits
@@ -291,8 +337,7 @@ struct mbb_ctx {
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
-    double *d_pre = nullptr;                   // ... its records
-    size_t pre_cap = 0;                        // (doubles)
+    Dev<double> pre;                           // ... its records
     long opt_zero_copy = 1;   // host path: kernel reads/writes pinned host memory (26 vs 34 us per call)
     long opt_stage = -1;      // -1 auto, 0 never, 1 whenever the tables fit in LDS
     long opt_roof_wgs = 0, opt_roof_threads = 0;   // measurement: geometry of mbb_roof_probe
@@ -307,7 +352,7 @@ struct mbb_ctx {
     long opt_lookahead = 1;   // single-GPU sampler runs prepare the next half-step's proposals ahead of the decisions they depend on
     long opt_serve_overlap = 1;    // the served kernel starts a row's quadrature beside its constructor (0: one after the other)
     long opt_flow_spin_log2 = 0;   // one-launch run: log2 of the polls before a wait gives up (0: the kernel's 22)
-    hipEvent_t ev_timed[2] = {nullptr, nullptr};   // mbb_sampler_advance_timed
+    EventPair ev_timed;            // mbb_sampler_advance_timed
     long flow_fallbacks = 0;       // one-launch runs that timed out and were redone as a launch train
     // A give-up is a property of the moment (a co-tenant holding CUs), not of the context: the next run
     // takes the one-launch form again.  Only kFlowStrikes give-ups in a row rest it, for kFlowRest runs.
@@ -324,31 +369,52 @@ struct mbb_ctx {
                               // (ensembles of 258-512 walkers on 256 CUs); 1, 2 force it (testing)
     size_t lds_granted[kNumSlots] = {};   // dynamic-LDS ceiling already requested, by slot (kernel_slot)
     long last_wpb = 0, last_threads = 0, last_grid = 0, last_smem = 0, last_smode = 0, last_ahead = 0;
-    unsigned long long *d_stamps = nullptr;   // diagnostic build only
+    Dev<unsigned long long> stamps;           // diagnostic build only
     // rccl
     ncclComm_t_ comm = nullptr;
     int nranks = 1, rank = 0;
     // one-hop exchange (mbb_xchg_*): one fine-grained allocation per rank, mapped by all peers:
     // [flags: 16 x u64][arrival counter][state rows: xcap x 6 doubles]
-    struct Xchg {
+    struct XchgState {
         int n = 0, rank = 0, connected = 0;
         int users = 0;                            // samplers whose state rows live in this buffer
         size_t cap_rows = 0;
-        unsigned char *base = nullptr;            // own allocation
         unsigned char *peer[16] = {};             // every rank's allocation as mapped here (own = base)
-        XchgArgs *d_args = nullptr;               // the kernel's view (device memory)
-        FlowX *d_flowx = nullptr;                 // the one-launch sharded run's view of every rank's copy (device memory)
         unsigned long long flow_run = 0;          // one-launch sharded runs so far (the same on every rank)
         unsigned long long seq = 0;               // launches posted so far
         long long spin_max = 4000000;
+    };
+    struct Xchg : XchgState {
+        Dev<unsigned char> base{mbbo::kDevFine};  // own allocation
+        Dev<XchgArgs> d_args;                     // the kernel's view (device memory)
+        Dev<FlowX> d_flowx;                       // the one-launch sharded run's view of every rank's copy (device memory)
         static constexpr size_t kHeader = 256;
+        // unmaps the peers' allocations, frees its own and is as new
+        void close()
+        {
+            for (int r = 0; r < n; ++r)
+                if (r != rank && peer[r]) (void)hipIpcCloseMemHandle(peer[r]);
+            base.release(); d_args.release(); d_flowx.release();
+            static_cast<XchgState &>(*this) = XchgState();
+        }
+        ~Xchg() { close(); }
         double *pos6(int r) const { return reinterpret_cast<double *>(peer[r] + kHeader); }
         // behind the rows: the state of a one-launch run (FlowView, mbb_kernels.hip.h), sized for cap_rows
         double *flow(int r) const { return reinterpret_cast<double *>(peer[r] + kHeader + cap_rows * 6 * sizeof(double)); }
         unsigned long long *flags(int r) const { return reinterpret_cast<unsigned long long *>(peer[r]); }
-        unsigned int *count() const { return reinterpret_cast<unsigned int *>(base + 128); }
+        unsigned int *count() const { return reinterpret_cast<unsigned int *>(base.d() + 128); }
     } x;
 };
+
+// How a block of a context is remade bigger (mbbo::DevBuf::grow, PinBuf::grow): big enough already, or the context's
+// stream is brought to rest, the old block released and the new one made.
+static int sync_stream(mbb_ctx *c)
+{
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MBB_OK;
+}
+static int grow(mbb_ctx *c, DevBuf &b, size_t bytes) { return b.grow(bytes, [c] { return sync_stream(c); }); }
+static int grow(mbb_ctx *c, mbbo::PinBuf &b, size_t bytes) { return b.grow(bytes, [c] { return sync_stream(c); }); }
 
 static int serve_stop(mbb_ctx *c);
 
@@ -498,10 +564,6 @@ extern "C" int mbb_ctx_create(int device, mbb_ctx **out)
     return MBB_OK;
 }
 
-static void free_dev(void *p) { if (p) (void)hipFree(p); }
-static int xchg_free(mbb_ctx *c);
-static void free_host(void *p) { if (p) (void)hipHostFree(p); }
-
 extern "C" void mbb_ctx_destroy(mbb_ctx *c)
 {
     if (!c) return;
@@ -520,31 +582,17 @@ extern "C" void mbb_ctx_destroy(mbb_ctx *c)
     mbbh::registry_leave(c->reg_key);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->x.base) (void)xchg_free(c);
-    free_dev(c->d_nu); free_dev(c->d_lnnu); free_dev(c->d_wt);
-    // (d_poly_b / d_poly_c belong to the device, not to the context: mbb_ctx_create)
-    free_dev(c->d_unit_tab); free_dev(c->d_band_rng); free_dev(c->d_tail_slot);
-    free_dev(c->d_flux); free_dev(c->d_ivar); free_dev(c->d_invcov);
-    free_dev(c->d_pars); free_dev(c->d_lnl); free_dev(c->d_mflux); free_dev(c->d_status);
-    free_host(c->h_pars); free_host(c->h_lnl); free_host(c->h_mflux); free_host(c->h_status);
-    free_dev(c->w_pars);
-    free_dev(c->w_door); free_host(c->h_gone); free_host(c->h_srv);
-    free_dev(c->d_gather); free_host(c->h_gather);
-    free_dev(c->d_pre);
-    free_dev(c->d_sed_pars); free_dev(c->d_sed_out); free_dev(c->d_sed_status);
-    free_dev(c->d_sed_wk);
-    // (the work buffers of the chain analyses are DevBufs: freed with the context, below)
-    for (int i = 0; i < 2; ++i)
-        if (c->ev_timed[i]) (void)hipEventDestroy(c->ev_timed[i]);
-    if (c->stream) {
+    const hipStream_t stream = c->stream;
+    const int device = c->device;
+    delete c;       // the exchange, every buffer and the events: the members free themselves
+    if (stream) {
         // idle (synchronised above): kept for the next context of this device, up to a handful
         std::lock_guard<std::mutex> lock(g_dev_mutex);
-        if (c->device >= 0 && c->device < 64 && g_dev[c->device].idle_streams.size() < 8)
-            g_dev[c->device].idle_streams.push_back(c->stream);
+        if (device >= 0 && device < 64 && g_dev[device].idle_streams.size() < 8)
+            g_dev[device].idle_streams.push_back(stream);
         else
-            (void)hipStreamDestroy(c->stream);
+            (void)hipStreamDestroy(stream);
     }
-    delete c;
 }
 
 extern "C" int mbb_set_model(mbb_ctx *c, int opthin, int noalpha, double wavenorm)
@@ -557,14 +605,13 @@ extern "C" int mbb_set_model(mbb_ctx *c, int opthin, int noalpha, double wavenor
     return MBB_OK;
 }
 
+// (a table is made anew at its exact size, one element at least; the caller has brought the stream to rest)
 template <typename T>
-static int upload(T **dptr, const std::vector<T> &h)
+static int upload(Dev<T> &b, const std::vector<T> &h)
 {
-    free_dev(*dptr);
-    *dptr = nullptr;
-    HIPCHK(hipMalloc((void **)dptr, sizeof(T) * (h.size() ? h.size() : 1)));
+    if (const int rc = b.remake(sizeof(T) * (h.size() ? h.size() : 1))) return rc;
     if (!h.empty())
-        HIPCHK(hipMemcpy(*dptr, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.d(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
     return MBB_OK;
 }
 
@@ -582,12 +629,12 @@ extern "C" int mbb_set_bands(mbb_ctx *c, const double *freq, const double *weigh
     memcpy(unit_tab.data(), L.unit_tab.data(), unit_tab.size() * sizeof(int4));
     memcpy(band_rng.data(), L.band_rng.data(), band_rng.size() * sizeof(int2));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if ((rc = upload(&c->d_nu, L.nu))) return rc;
-    if ((rc = upload(&c->d_lnnu, L.lnnu))) return rc;
-    if ((rc = upload(&c->d_wt, L.wt))) return rc;
-    if ((rc = upload(&c->d_unit_tab, unit_tab))) return rc;
-    if ((rc = upload(&c->d_band_rng, band_rng))) return rc;
-    if ((rc = upload(&c->d_tail_slot, L.tail_slot))) return rc;
+    if ((rc = upload(c->band.nu, L.nu))) return rc;
+    if ((rc = upload(c->band.lnnu, L.lnnu))) return rc;
+    if ((rc = upload(c->band.wt, L.wt))) return rc;
+    if ((rc = upload(c->band.unit_tab, unit_tab))) return rc;
+    if ((rc = upload(c->band.band_rng, band_rng))) return rc;
+    if ((rc = upload(c->band.tail_slot, L.tail_slot))) return rc;
     c->nb = nb;
     c->nchunk = L.nchunk;
     c->nseg = L.nseg;
@@ -605,17 +652,16 @@ extern "C" int mbb_set_data(mbb_ctx *c, const double *flux, const double *w, int
     if (!flux || !w || nb <= 0) return fail(MBB_ERR_ARG, "bad data");
     HIPCHK(hipStreamSynchronize(c->stream));
     std::vector<double> f(flux, flux + nb);
-    if ((rc = upload(&c->d_flux, f))) return rc;
+    if ((rc = upload(c->data.flux, f))) return rc;
     if (is_cov) {
         std::vector<double> m(w, w + (size_t)nb * nb);
-        if ((rc = upload(&c->d_invcov, m))) return rc;
+        if ((rc = upload(c->data.invcov, m))) return rc;
         std::vector<double> iv(nb, 0.0);
-        if ((rc = upload(&c->d_ivar, iv))) return rc;
+        if ((rc = upload(c->data.ivar, iv))) return rc;
     } else {
         std::vector<double> iv(w, w + nb);
-        if ((rc = upload(&c->d_ivar, iv))) return rc;
-        free_dev(c->d_invcov);
-        c->d_invcov = nullptr;
+        if ((rc = upload(c->data.ivar, iv))) return rc;
+        c->data.invcov.release();
     }
     c->has_cov = is_cov ? 1 : 0;
     c->data_nb = nb;
@@ -630,10 +676,9 @@ extern "C" int mbb_set_data_multi(mbb_ctx *c, const double *flux, const double *
     if (!flux || !ivar || nb <= 0 || nsrc <= 0) return fail(MBB_ERR_ARG, "bad data");
     HIPCHK(hipStreamSynchronize(c->stream));
     std::vector<double> f(flux, flux + (size_t)nb * nsrc), iv(ivar, ivar + (size_t)nb * nsrc);
-    if ((rc = upload(&c->d_flux, f))) return rc;
-    if ((rc = upload(&c->d_ivar, iv))) return rc;
-    free_dev(c->d_invcov);
-    c->d_invcov = nullptr;
+    if ((rc = upload(c->data.flux, f))) return rc;
+    if ((rc = upload(c->data.ivar, iv))) return rc;
+    c->data.invcov.release();
     c->has_cov = 0;
     c->data_nb = nb;
     c->nsrc = nsrc;
@@ -688,58 +733,40 @@ static int wait_stream(mbb_ctx *c)
 
 static int ensure_capacity(mbb_ctx *c, size_t n, bool want_flux)
 {
-    if (n > c->cap) {
-        size_t cap = c->cap ? c->cap : 256;
+    mbb_ctx::Boundary &b = c->bnd;
+    int rc;
+    if (n > b.cap) {
+        size_t cap = b.cap ? b.cap : 256;
         while (cap < n) cap *= 2;
-        HIPCHK(hipStreamSynchronize(c->stream));
+        // (grow() taken apart: the generation goes between the stream coming to rest and the first release)
+        if ((rc = sync_stream(c))) return rc;
         // whoever holds addresses from mbb_boundary_buffers must see this BEFORE it writes through them again
         __atomic_store_n(&c->buf_gen, c->buf_gen + 1, __ATOMIC_RELEASE);
-        free_dev(c->d_pars); free_dev(c->d_lnl); free_dev(c->d_status);
-        free_host(c->h_pars); free_host(c->h_lnl); free_host(c->h_status);
-        c->d_pars = c->d_lnl = nullptr; c->d_status = nullptr;
-        c->h_pars = c->h_lnl = nullptr; c->h_status = nullptr;
-        c->cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_pars, cap * 5 * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&c->d_lnl, cap * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&c->d_status, cap * sizeof(int32_t)));
-        // mapped AND coherent (fine-grained): the kernel's stores to the result slots must
-        // become visible to the polling host while the kernel is still running, whatever
-        // HIP_HOST_COHERENT defaults to
-        const unsigned hflags = hipHostMallocMapped | hipHostMallocCoherent;
-        HIPCHK(hipHostMalloc((void **)&c->h_pars, cap * 5 * sizeof(double), hflags));
-        HIPCHK(hipHostMalloc((void **)&c->h_lnl, cap * sizeof(double), hflags));
-        HIPCHK(hipHostMalloc((void **)&c->h_status, cap * sizeof(int32_t), hflags));
-        HIPCHK(hipHostGetDevicePointer((void **)&c->dv_pars, c->h_pars, 0));
-        HIPCHK(hipHostGetDevicePointer((void **)&c->dv_lnl, c->h_lnl, 0));
-        HIPCHK(hipHostGetDevicePointer((void **)&c->dv_status, c->h_status, 0));
+        b.cap = 0;
         c->call_in = nullptr; c->call_cap = 0;
+        b.w_pars.release();
+        if ((rc = b.d_pars.remake(cap * 5 * sizeof(double))) || (rc = b.d_lnl.remake(cap * sizeof(double))) ||
+            (rc = b.d_status.remake(cap * sizeof(int32_t))) || (rc = b.h_pars.remake(cap * 5 * sizeof(double))) ||
+            (rc = b.h_lnl.remake(cap * sizeof(double))) || (rc = b.h_status.remake(cap * sizeof(int32_t))))
+            return rc;
         // With a large BAR the host can store into (fine-grained) device memory directly:
         // posted writes, and the kernel then reads its parameter rows from local memory
         // instead of pulling them across PCIe.
-        free_dev(c->w_pars);
-        c->w_pars = nullptr;
         if (c->large_bar < 0) {
             int lb = 0;
             if (hipDeviceGetAttribute(&lb, hipDeviceAttributeIsLargeBar, c->device) != hipSuccess) lb = 0;
             c->large_bar = lb;
         }
-        if (c->large_bar > 0 &&
-            hipExtMallocWithFlags((void **)&c->w_pars, cap * 5 * sizeof(double), hipDeviceMallocFinegrained) != hipSuccess) {
-            (void)hipGetLastError();
-            c->w_pars = nullptr;
-        }
-        c->cap = cap;
+        // (refused: the rows go through the pinned block)
+        if (c->large_bar > 0 && b.w_pars.remake(cap * 5 * sizeof(double))) (void)hipGetLastError();
+        b.cap = cap;
     }
-    if (want_flux && n * (size_t)c->nb > c->cap_flux) {
-        size_t cap = c->cap * (size_t)c->nb;
+    if (want_flux && n * (size_t)c->nb > b.cap_flux) {
+        size_t cap = b.cap * (size_t)c->nb;
         if (cap < n * (size_t)c->nb) cap = n * (size_t)c->nb;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        free_dev(c->d_mflux); free_host(c->h_mflux);
-        c->d_mflux = nullptr; c->h_mflux = nullptr; c->cap_flux = 0;
-        HIPCHK(hipMalloc((void **)&c->d_mflux, cap * sizeof(double)));
-        HIPCHK(hipHostMalloc((void **)&c->h_mflux, cap * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&c->dv_mflux, c->h_mflux, 0));
-        c->cap_flux = cap;
+        b.cap_flux = 0;
+        if ((rc = grow(c, b.d_mflux, cap * sizeof(double))) || (rc = grow(c, b.h_mflux, cap * sizeof(double)))) return rc;
+        b.cap_flux = cap;
     }
     return MBB_OK;
 }
@@ -863,10 +890,10 @@ static int launch_packed(mbb_ctx *c, int slot, int grid, int threads, size_t sme
 // The part of the argument block every kernel of the family reads alike: model, bands, data, limits and priors.
 static void fill_model_args(const mbb_ctx *c, LikeArgs &a)
 {
-    a.nu = c->d_nu; a.lnnu = c->d_lnnu; a.wt = c->d_wt;
+    a.nu = c->band.nu.d(); a.lnnu = c->band.lnnu.d(); a.wt = c->band.wt.d();
     a.poly_b = c->d_poly_b; a.poly_c = c->d_poly_c;
-    a.unit_tab = c->d_unit_tab; a.band_rng = c->d_band_rng; a.tail_slot = c->d_tail_slot;
-    a.flux = c->d_flux; a.ivar = c->d_ivar; a.invcov = c->has_cov ? c->d_invcov : nullptr;
+    a.unit_tab = c->band.unit_tab.d(); a.band_rng = c->band.band_rng.d(); a.tail_slot = c->band.tail_slot.d();
+    a.flux = c->data.flux.d(); a.ivar = c->data.ivar.d(); a.invcov = c->has_cov ? c->data.invcov.d() : nullptr;
     a.nb = c->nb; a.nunit = c->nunit; a.npart = c->npart; a.nchunk = c->nchunk;
     a.nunorm = kUmToGHz / c->wavenorm;
     a.lnunorm = log(a.nunorm);
@@ -875,7 +902,7 @@ static void fill_model_args(const mbb_ctx *c, LikeArgs &a)
     a.has_uplim = c->has_uplim; a.has_gprior = c->has_gprior;
     a.debug = (int)c->opt_debug;
 #ifdef MBB_STAMPS
-    a.stamps = c->d_stamps;
+    a.stamps = c->stamps.d();
 #endif
 }
 
@@ -930,16 +957,11 @@ static int launch_rows(mbb_ctx *c, const double *d_pars, int n, double *d_lnl, i
     // them on the constructors (cfg5's 250 000 rows: 1.31 -> 1.0x ms).  Option "prepass": -1 auto (from 64 walkers per CU),
     // 0 never, 1 always.
     if (c->opt_prepass > 0 || (c->opt_prepass < 0 && (long)n >= 64L * c->cu_count)) {
-        const size_t need = (size_t)n * kPreWords;
-        if (need > c->pre_cap) {
-            size_t cap = c->pre_cap ? c->pre_cap : 16384 * (size_t)kPreWords;
-            while (cap < need) cap *= 2;
-            HIPCHK(hipStreamSynchronize(c->stream));
-            free_dev(c->d_pre); c->d_pre = nullptr; c->pre_cap = 0;
-            HIPCHK(hipMalloc((void **)&c->d_pre, cap * sizeof(double)));
-            c->pre_cap = cap;
-        }
-        a.spec = c->d_pre;
+        const size_t need = (size_t)n * kPreWords * sizeof(double);
+        size_t cap = c->pre.cap ? c->pre.cap : 16384 * (size_t)kPreWords * sizeof(double);
+        while (cap < need) cap *= 2;
+        if ((rc = grow(c, c->pre, cap))) return rc;
+        a.spec = c->pre.d();
         static void (*const ptable[4])(const LikeArgs) = {k_walker_pre<false, false>, k_walker_pre<false, true>,
                                                           k_walker_pre<true, false>, k_walker_pre<true, true>};
         hipLaunchKernelGGL(ptable[model_of(c)], dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
@@ -972,15 +994,15 @@ extern "C" int mbb_lnlike_repeat_device(mbb_ctx *c, const double *d_pars, int n,
 
 // The zero-copy host path once the parameter rows are where the kernel reads them (device memory the host
 // wrote through the BAR when `push`, the pinned block otherwise): launch, watch the result slots in pinned
-// memory (or wait for the stream), leave lnl / status / model flux in c->h_lnl, c->h_status, c->h_mflux.
+// memory (or wait for the stream), leave lnl / status / model flux in the boundary's pinned blocks (c->bnd.h_lnl, h_status, h_mflux).
 static int lnlike_zero_copy(mbb_ctx *c, int n, bool push, bool model_flux, long t_a)
 {
     int rc;
     auto now_ns = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1000000000L + ts.tv_nsec; };
     // the kernel reads the pinned parameter block and writes lnL straight
     // into pinned host memory: no copy commands on the stream at all
-    double *const dp = push ? c->w_pars : c->dv_pars, *const dl = c->dv_lnl, *const df = model_flux ? c->dv_mflux : nullptr;
-    int32_t *const ds = c->dv_status;
+    double *const dp = push ? c->bnd.w_pars.d() : c->bnd.h_pars.dv(), *const dl = c->bnd.h_lnl.dv(), *const df = model_flux ? c->bnd.h_mflux.dv() : nullptr;
+    int32_t *const ds = c->bnd.h_status.dv();
     // spin_wait = 2: do not wait for the kernel's completion signal at all.  The
     // result slots in pinned memory are pre-filled with patterns the kernel never
     // writes (a NaN with a payload; it produces the canonical NaN), and the host
@@ -989,8 +1011,8 @@ static int lnlike_zero_copy(mbb_ctx *c, int n, bool push, bool model_flux, long 
     const bool watch = c->opt_spin == 2 && !model_flux && n <= 8192;
     c->last_watch_seen = -1;
     if (watch) {
-        uint64_t *hl = reinterpret_cast<uint64_t *>(c->h_lnl);
-        for (int i = 0; i < n; ++i) { hl[i] = kLnlSentinel; c->h_status[i] = kStatusSentinel; }
+        uint64_t *hl = reinterpret_cast<uint64_t *>(c->bnd.h_lnl.h());
+        for (int i = 0; i < n; ++i) { hl[i] = kLnlSentinel; c->bnd.h_status.h()[i] = kStatusSentinel; }
     }
     const long t_b = now_ns();
     if ((rc = launch_rows(c, dp, n, dl, ds, df))) return rc;
@@ -999,8 +1021,8 @@ static int lnlike_zero_copy(mbb_ctx *c, int n, bool push, bool model_flux, long 
     if (watch) {
         // acquire loads: the copies out of h_lnl / h_status below must not be satisfied
         // from before the slot was seen to change
-        const uint64_t *hl = reinterpret_cast<const uint64_t *>(c->h_lnl);
-        const int32_t *hs = c->h_status;
+        const uint64_t *hl = reinterpret_cast<const uint64_t *>(c->bnd.h_lnl.h());
+        const int32_t *hs = c->bnd.h_status.h();
         int i = 0;
         for (long spins = 0; spins < c->opt_spin_budget; ++spins) {   // default ~ tens of ms, then give up
             while (i < n && __atomic_load_n(&hl[i], __ATOMIC_ACQUIRE) != kLnlSentinel &&
@@ -1027,31 +1049,31 @@ extern "C" int mbb_lnlike_batch(mbb_ctx *c, const double *pars, int n, double *l
     const size_t nbytes = (size_t)n * 5 * sizeof(double);
     auto now_ns = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1000000000L + ts.tv_nsec; };
     const long t_a = now_ns();
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->w_pars;
+    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
     if (push) {
-        memcpy(c->w_pars, pars, nbytes);           // CPU stores through the BAR ...
+        memcpy(c->bnd.w_pars.d(), pars, nbytes);           // CPU stores through the BAR ...
         __builtin_ia32_sfence();                   // ... drained before the doorbell is rung
     } else {
-        memcpy(c->h_pars, pars, nbytes);
+        memcpy(c->bnd.h_pars.h(), pars, nbytes);
     }
     if (c->opt_zero_copy) {
         if ((rc = lnlike_zero_copy(c, n, push, model_flux != nullptr, t_a))) return rc;
     } else {
-        HIPCHK(hipMemcpyAsync(c->d_pars, c->h_pars, nbytes, hipMemcpyHostToDevice, c->stream));
-        if ((rc = launch_rows(c, c->d_pars, n, c->d_lnl, c->d_status,
-                                model_flux ? c->d_mflux : nullptr))) return rc;
-        HIPCHK(hipMemcpyAsync(c->h_lnl, c->d_lnl, (size_t)n * sizeof(double),
+        HIPCHK(hipMemcpyAsync(c->bnd.d_pars.d(), c->bnd.h_pars.h(), nbytes, hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_rows(c, c->bnd.d_pars.d(), n, c->bnd.d_lnl.d(), c->bnd.d_status.d(),
+                                model_flux ? c->bnd.d_mflux.d() : nullptr))) return rc;
+        HIPCHK(hipMemcpyAsync(c->bnd.h_lnl.h(), c->bnd.d_lnl.d(), (size_t)n * sizeof(double),
                               hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(c->h_status, c->d_status, (size_t)n * sizeof(int32_t),
+        HIPCHK(hipMemcpyAsync(c->bnd.h_status.h(), c->bnd.d_status.d(), (size_t)n * sizeof(int32_t),
                               hipMemcpyDeviceToHost, c->stream));
         if (model_flux)
-            HIPCHK(hipMemcpyAsync(c->h_mflux, c->d_mflux, (size_t)n * c->nb * sizeof(double),
+            HIPCHK(hipMemcpyAsync(c->bnd.h_mflux.h(), c->bnd.d_mflux.d(), (size_t)n * c->nb * sizeof(double),
                                   hipMemcpyDeviceToHost, c->stream));
         if ((rc = wait_stream(c))) return rc;
     }
-    memcpy(lnl, c->h_lnl, (size_t)n * sizeof(double));
-    if (status) memcpy(status, c->h_status, (size_t)n * sizeof(int32_t));
-    if (model_flux) memcpy(model_flux, c->h_mflux, (size_t)n * c->nb * sizeof(double));
+    memcpy(lnl, c->bnd.h_lnl.h(), (size_t)n * sizeof(double));
+    if (status) memcpy(status, c->bnd.h_status.h(), (size_t)n * sizeof(int32_t));
+    if (model_flux) memcpy(model_flux, c->bnd.h_mflux.h(), (size_t)n * c->nb * sizeof(double));
     return MBB_OK;
 }
 
@@ -1073,11 +1095,11 @@ extern "C" int mbb_boundary_buffers(mbb_ctx *c, int nmax, double **in, double **
     if (rc) return rc;
     if (nmax <= 0 || !in || !out) return fail(MBB_ERR_ARG, "bad arguments");
     if ((rc = ensure_capacity(c, (size_t)nmax, false))) return rc;
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->w_pars;
-    c->call_in = push ? c->w_pars : c->h_pars;
-    c->call_cap = c->cap;
-    *in = c->call_in; *out = c->h_lnl;
-    if (status) *status = c->h_status;
+    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
+    c->call_in = push ? c->bnd.w_pars.d() : c->bnd.h_pars.h();
+    c->call_cap = c->bnd.cap;
+    *in = c->call_in; *out = c->bnd.h_lnl.h();
+    if (status) *status = c->bnd.h_status.h();
     return MBB_OK;
 }
 
@@ -1093,7 +1115,7 @@ static int serve_stop(mbb_ctx *c)
         if (g_dev[c->device].server == c) g_dev[c->device].server = nullptr;
     }
     // a request number the server has not seen, with the row count that means "leave"
-    __atomic_store_n(c->w_door, (++c->srv_seq << 16) | kServeQuit, __ATOMIC_RELAXED);
+    __atomic_store_n(c->srv.w_door.d(), (++c->srv_seq << 16) | kServeQuit, __ATOMIC_RELAXED);
     __builtin_ia32_sfence();
     HIPCHK(hipStreamSynchronize(c->stream));
     return MBB_OK;
@@ -1114,19 +1136,17 @@ static int serve_grid(const mbb_ctx *c, int n, int share)
 // (the launch itself; serve_start below claims the device around it)
 static int serve_launch(mbb_ctx *c, int n, unsigned long long word, int grid)
 {
-    if (!c->w_door) {
-        if (hipExtMallocWithFlags((void **)&c->w_door, 64, hipDeviceMallocFinegrained) != hipSuccess) {
-            (void)hipGetLastError();
-            c->w_door = nullptr;
-            return 1;
-        }
-        HIPCHK(hipHostMalloc((void **)&c->h_gone, 64, hipHostMallocMapped | hipHostMallocCoherent));
+    if (!c->srv.w_door.p && c->srv.w_door.remake(64)) {
+        (void)hipGetLastError();                   // (no fine-grained memory to be had: every call is a launch)
+        return 1;
     }
+    if (!c->srv.h_gone.p)
+        if (const int rc = c->srv.h_gone.remake(64)) return rc;
 
     LikeArgs a;
     memset(&a, 0, sizeof a);
     fill_model_args(c, a);
-    a.pars = c->w_pars; a.n = n; a.lnl = c->dv_srv; a.status = nullptr; a.model_flux = nullptr;
+    a.pars = c->bnd.w_pars.d(); a.n = n; a.lnl = c->srv.h_srv.dv(); a.status = nullptr; a.model_flux = nullptr;
     a.wpb = 1; a.nsrc = 1;
     int wpb, threads;
     pick_geometry(c, 1, wpb, threads);
@@ -1146,12 +1166,12 @@ static int serve_launch(mbb_ctx *c, int n, unsigned long long word, int grid)
     a.spec_cfg = ovl ? 1 : 0;
     const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
     if (sm_total > dyn_limit) return 1;
-    HIPCHK(hipHostGetDevicePointer((void **)&a.chain6, c->h_gone, 0));
-    a.pos6 = reinterpret_cast<double *>(c->w_door);
+    a.chain6 = reinterpret_cast<double *>(c->srv.h_gone.dv());
+    a.pos6 = reinterpret_cast<double *>(c->srv.w_door.d());
     a.seed = word;
     a.persist = (int)std::min<long>(std::max<long>(c->opt_serve_idle_us, 20), 1000000);
-    *c->h_gone = 0;
-    __atomic_store_n(c->w_door, word, __ATOMIC_RELAXED);
+    *c->srv.h_gone.h() = 0;
+    __atomic_store_n(c->srv.w_door.d(), word, __ATOMIC_RELAXED);
     __builtin_ia32_sfence();
     {
         int rc = launch_packed(c, kernel_slot(kServe, model_of(c), (ovl ? 2 : 0) + (stg ? 1 : 0)), grid, threads, sm_total, a,
@@ -1190,19 +1210,16 @@ static int serve_start(mbb_ctx *c, int n, unsigned long long word, int grid)
 }
 
 // One request: MBB_OK when the results are in the pinned slots, 1 when the rows have to go by a launch after all,
-// negative on error.  The parameter rows are in c->w_pars already.
+// negative on error.  The parameter rows are in c->bnd.w_pars already.
 static int serve_request(mbb_ctx *c, int n, int grid)
 {
     const int kPfAhead = c->opt_serve_prefetch;
     auto now_ns = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1000000000L + ts.tv_nsec; };
     const long t_a = now_ns();
     // (the records exist once a server has been started; before that serve_start makes them)
-    if (!c->h_srv) {
-        HIPCHK(hipHostMalloc((void **)&c->h_srv, (size_t)kServePasses * c->cu_count * 8 * kSrvStride, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&c->dv_srv, c->h_srv, 0));
-        c->srv_cap = (size_t)kServePasses * c->cu_count;
-    }
-    uint64_t *hr = reinterpret_cast<uint64_t *>(c->h_srv);
+    if (!c->srv.h_srv.p)
+        if (const int rc = c->srv.h_srv.remake((size_t)kServePasses * c->cu_count * 8 * kSrvStride)) return rc;
+    uint64_t *hr = reinterpret_cast<uint64_t *>(c->srv.h_srv.h());
     for (int i = 0; i < n; ++i) hr[kSrvStride * i + 1] = (uint64_t)kStatusSentinel;
     const unsigned long long word = (++c->srv_seq << 16) | (unsigned long long)n;
     __builtin_ia32_sfence();                       // the caller's rows, through the BAR, before the request
@@ -1213,7 +1230,7 @@ static int serve_request(mbb_ctx *c, int n, int grid)
         if (rc) return rc;
         budget_ns += 200000L;                      // (a launch, and the tables into LDS on every CU)
     } else {
-        __atomic_store_n(c->w_door, word, __ATOMIC_RELAXED);
+        __atomic_store_n(c->srv.w_door.d(), word, __ATOMIC_RELAXED);
         __builtin_ia32_sfence();
     }
     const long t_c = now_ns();
@@ -1229,12 +1246,12 @@ static int serve_request(mbb_ctx *c, int n, int grid)
             // turned: a line that sits in the core's cache when the GPU wants to write it costs the GPU a snoop)
             if (i == 0) for (int k = 1; k < kPfAhead && k < n; ++k) __builtin_prefetch(&hr[kSrvStride * k], 0, 3);
             if (kPfAhead && i + kPfAhead < n) __builtin_prefetch(&hr[kSrvStride * (i + kPfAhead)], 0, 3);
-            c->h_lnl[i] = c->h_srv[kSrvStride * i];
-            c->h_status[i] = (int32_t)hr[kSrvStride * i + 1];
+            c->bnd.h_lnl.h()[i] = c->srv.h_srv.h()[kSrvStride * i];
+            c->bnd.h_status.h()[i] = (int32_t)hr[kSrvStride * i + 1];
             ++i;
         }
         if (i == n) { seen = true; break; }
-        if ((spins & 63) == 63 && (now_ns() - t_c > budget_ns || __atomic_load_n(c->h_gone, __ATOMIC_ACQUIRE) != 0)) break;
+        if ((spins & 63) == 63 && (now_ns() - t_c > budget_ns || __atomic_load_n(c->srv.h_gone.h(), __ATOMIC_ACQUIRE) != 0)) break;
         __builtin_ia32_pause();
     }
     c->last_watch_seen = seen ? 1 : 0;
@@ -1251,7 +1268,7 @@ static int serve_request(mbb_ctx *c, int n, int grid)
     // stretch on a shared box, and a sampler's every later call was a launch; the sampler forms rest the same way).
     ++c->srv_fallbacks;
     c->srv_hot = 0;
-    if (__atomic_load_n(c->h_gone, __ATOMIC_ACQUIRE) == 0 && ++c->srv_strikes >= 3) {
+    if (__atomic_load_n(c->srv.h_gone.h(), __ATOMIC_ACQUIRE) == 0 && ++c->srv_strikes >= 3) {
         c->srv_strikes = 0;
         c->srv_rest = kServeRest;
         ++c->srv_rests;
@@ -1270,9 +1287,9 @@ extern "C" int mbb_lnlike_call(mbb_ctx *c, int n)
     int rc;
     if (n <= 0) return n == 0 ? MBB_OK : fail(MBB_ERR_ARG, "bad row count");
     if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->w_pars;
-    if (!c->opt_zero_copy || !c->call_in || c->call_cap != c->cap || (size_t)n > c->cap ||
-        c->call_in != (push ? c->w_pars : c->h_pars)) {
+    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
+    if (!c->opt_zero_copy || !c->call_in || c->call_cap != c->bnd.cap || (size_t)n > c->bnd.cap ||
+        c->call_in != (push ? c->bnd.w_pars.d() : c->bnd.h_pars.h())) {
         if (c->serving && (rc = serve_stop(c))) return rc;
         return fail(MBB_ERR_STATE, "mbb_boundary_buffers first (or again: the buffers or the host-path options changed)");
     }
@@ -1344,7 +1361,7 @@ extern "C" int mbb_lnlike_call(mbb_ctx *c, int n)
         if (push) __builtin_ia32_sfence();         // the caller's stores through the BAR, drained before the doorbell
         if ((rc = lnlike_zero_copy(c, n, push, false, ts.tv_sec * 1000000000L + ts.tv_nsec))) return rc;
     }
-    const int32_t *hs = c->h_status;
+    const int32_t *hs = c->bnd.h_status.h();
     for (int i = 0; i < n; ++i)
         if (hs[i] >= 2 && hs[i] != 7) return hs[i];
     return MBB_OK;
@@ -1352,25 +1369,15 @@ extern "C" int mbb_lnlike_call(mbb_ctx *c, int n)
 
 // ---- device-resident ensemble sampler ----------------------------------------
 constexpr size_t kChainDirectBytes = (size_t)8 << 20;   // stored chains up to this size go straight into the caller's arrays
-struct mbb_sampler_state {
+struct mbb_sampler_state : mbbo::SamplerMem {      // (its device and pinned memory: mbb_owned.h)
     int nw = 0;            // walkers per source
     int nsrc = 1;          // independent ensembles advanced together
-    double *d_pos6 = nullptr;
-    bool pos6_owned = true;              // false: the rows live in the context's exchange buffer
-    unsigned int *d_nacc = nullptr;      // [shards][2][nsrc*per], launch-local order
-    int *d_err = nullptr;
-    double *d_bak = nullptr;             // one-launch run: the rows and counts it started from (R x 6 doubles, R counts)
     bool backup_kept = false;            // the last run kept d_bak, a copy of what it started from to redo it from
     bool unchecked = false;              // an asynchronous advance was enqueued and its error flag not looked at yet
     bool lost = false;                   // such an advance gave up: the rows are no state of the chain until set again
-    double *d_spec = nullptr;            // one-launch run: its device state (FlowView or FlowMView, spec_words(rows))
     int spec_form = 0;                   // the sampler form whose state d_spec holds (0: none / not to be trusted)
     int flowm_parity = 0;                // form 7: the set of completion counters the next launch uses
-    double *d_chain6 = nullptr;          // [shards][nsteps][2][nsrc*per][6]
-    double *d_chain_out = nullptr;       // the same chain in the caller's layout: [rows][nsteps][5] then [rows][nsteps]
-    double *h_chain = nullptr;           // ... and its pinned landing place on the host (a D2H into the caller's pageable,
-                                         // often untouched, arrays ran at ~1 GB/s: 18.8 us per step for 2000 stored steps)
-    size_t chain_cap = 0;
+    size_t chain_cap = 0;                // doubles of d_chain6, and of d_chain_out
     bool h_chain_tried = false;          // the landing buffer was asked for since d_chain_out was last made
     int resident_nsteps = 0;             // steps of the chain d_chain_out holds in the caller's layout (0: none)
     unsigned long long seed = 0, steps_done = 0;
@@ -1383,25 +1390,24 @@ extern "C" int mbb_sampler_create(mbb_ctx *c, int nwalkers, unsigned long long s
     int rc = use(c);
     if (rc) return rc;
     if (!out || nwalkers < 2 || (nwalkers & 1)) return fail(MBB_ERR_ARG, "nwalkers must be even");
-    mbb_sampler_state *s = new mbb_sampler_state();
+    std::unique_ptr<mbb_sampler_state> s(new mbb_sampler_state());
     s->nw = nwalkers;
     s->nsrc = c->nsrc > 0 ? c->nsrc : 1;
     s->seed = seed;
     const size_t R = (size_t)s->rows();
     if (c->x.connected) {
         // sharded with the one-hop exchange: the ensemble lives where the peers can write it
-        if (R > c->x.cap_rows) { delete s; return fail(MBB_ERR_ARG, "more walkers than the exchange buffer holds"); }
+        if (R > c->x.cap_rows) return fail(MBB_ERR_ARG, "more walkers than the exchange buffer holds");
         s->d_pos6 = c->x.pos6(c->x.rank);
-        s->pos6_owned = false;
-        ++c->x.users;
     } else {
-        HIPCHK(hipMalloc((void **)&s->d_pos6, R * 6 * sizeof(double)));
+        if ((rc = s->pos6_own.remake(R * 6 * sizeof(double)))) return rc;
+        s->d_pos6 = s->pos6_own.d();
     }
-    HIPCHK(hipMalloc((void **)&s->d_nacc, R * sizeof(unsigned int)));
-    HIPCHK(hipMalloc((void **)&s->d_err, sizeof(int)));
-    HIPCHK(hipMemset(s->d_nacc, 0, R * sizeof(unsigned int)));
-    HIPCHK(hipMemset(s->d_err, 0, sizeof(int)));
-    *out = s;
+    if ((rc = s->d_nacc.remake(R * sizeof(unsigned int))) || (rc = s->d_err.remake(sizeof(int)))) return rc;
+    HIPCHK(hipMemset(s->d_nacc.d(), 0, R * sizeof(unsigned int)));
+    HIPCHK(hipMemset(s->d_err.d(), 0, sizeof(int)));
+    if (!s->pos6_own.p) ++c->x.users;       // (only a sampler that exists is counted: mbb_xchg_close waits for the count)
+    *out = s.release();
     return MBB_OK;
 }
 
@@ -1412,11 +1418,7 @@ extern "C" int mbb_sampler_destroy(mbb_ctx *c, void *sp)
     mbb_sampler_state *s = (mbb_sampler_state *)sp;
     if (!s) return MBB_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (s->pos6_owned) free_dev(s->d_pos6);
-    else if (c->x.users > 0) --c->x.users;
-    free_dev(s->d_nacc); free_dev(s->d_err); free_dev(s->d_chain6); free_dev(s->d_chain_out); free_dev(s->d_spec);
-    if (s->h_chain) (void)hipHostFree(s->h_chain);
-    free_dev(s->d_bak);
+    if (!s->pos6_own.p && c->x.users > 0) --c->x.users;
     delete s;
     return MBB_OK;
 }
@@ -1434,10 +1436,10 @@ extern "C" int mbb_sampler_flow_counters(mbb_ctx *c, void *sp, unsigned long lon
     mbb_sampler_state *s = (mbb_sampler_state *)sp;
     const int n = 2 * kFmRing * kFmShards;
     if (!s || !counters || !ring || !shards || !next_set || cap < n) return fail(MBB_ERR_ARG, "bad arguments");
-    if (!s->d_spec || (s->spec_form != 7 && s->spec_form != 9))
+    if (!s->d_spec.p || (s->spec_form != 7 && s->spec_form != 9))
         return fail(MBB_ERR_STATE, "the sampler holds no state of a one-launch run (forms 7, 9)");
     HIPCHK(hipStreamSynchronize(c->stream));
-    const FlowMView fv = flowm_view(s->d_spec, s->rows());
+    const FlowMView fv = flowm_view(s->d_spec.d(), s->rows());
     std::vector<unsigned long long> w(kFmDoneWords);
     HIPCHK(hipMemcpy(w.data(), fv.done, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int set = 0; set < 2; ++set)
@@ -1460,8 +1462,8 @@ extern "C" int mbb_sampler_reset(mbb_ctx *c, void *sp)
     if (!s) return fail(MBB_ERR_ARG, "null sampler");
     (void)sampler_check_pending(c, s);       // (a give-up of an asynchronous advance is remembered, not wiped with the flag)
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemset(s->d_nacc, 0, (size_t)s->rows() * sizeof(unsigned int)));
-    HIPCHK(hipMemset(s->d_err, 0, sizeof(int)));
+    HIPCHK(hipMemset(s->d_nacc.d(), 0, (size_t)s->rows() * sizeof(unsigned int)));
+    HIPCHK(hipMemset(s->d_err.d(), 0, sizeof(int)));
     return MBB_OK;
 }
 
@@ -1510,7 +1512,7 @@ extern "C" int mbb_sampler_set_state(mbb_ctx *c, void *sp, const double *pos, co
     HIPCHK(hipStreamSynchronize(c->stream));
     if (s->lost || s->unchecked) {
         // whatever an asynchronous advance left in the flag belongs to the state just replaced
-        HIPCHK(hipMemset(s->d_err, 0, sizeof(int)));
+        HIPCHK(hipMemset(s->d_err.d(), 0, sizeof(int)));
         s->lost = s->unchecked = false;
         s->spec_form = 0;
     }
@@ -1526,11 +1528,11 @@ static int sampler_check_pending(mbb_ctx *c, mbb_sampler_state *s)
 {
     if (s->unchecked) {
         int err = 0;
-        HIPCHK(hipMemcpyAsync(&err, s->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&err, s->d_err.d(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         s->unchecked = false;
         if (err == 9) {
-            HIPCHK(hipMemset(s->d_err, 0, sizeof(int)));
+            HIPCHK(hipMemset(s->d_err.d(), 0, sizeof(int)));
             s->lost = true;
             s->spec_form = 0;
         }
@@ -1553,7 +1555,7 @@ struct ShardPlan { int shards, first, last, per; bool collective, xchg; };
 static int shard_plan(const mbb_ctx *c, const mbb_sampler_state *s, ShardPlan &p)
 {
     const int half = s->nw / 2;
-    const bool xchg = c->x.connected && !s->pos6_owned && c->x.n > 1;
+    const bool xchg = c->x.connected && !s->pos6_own.p && c->x.n > 1;
     p.collective = xchg || (c->comm != nullptr && c->nranks > 1);
     const int granks = xchg ? c->x.n : c->nranks, grank = xchg ? c->x.rank : c->rank;
     p.shards = p.collective ? granks : (int)(c->opt_vranks > 1 ? c->opt_vranks : 1);
@@ -1685,7 +1687,7 @@ static int launch_sampler(mbb_ctx *c, const RunPlan &rp, const SamplerLaunch &sl
     // ensemble size).  Form 6 dispatches first the n_ahead workgroups that prepare the next half-step -- one row of 16 lanes
     // per (walker, candidate), `rows` of them per wave, `aw` such waves per workgroup (lookahead_plan) -- then the movers.
     int grid = g.grid;
-    if (form == 2) a.xargs = c->x.d_args;
+    if (form == 2) a.xargs = c->x.d_args.d();
     if (form == 6) {
         a.spec_cfg = (rp.rows << 8) | (rp.aw << 16) | spin;
         a.n_ahead = rp.n_ahead;
@@ -1710,7 +1712,7 @@ static int run_one_launch(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, S
     const bool sharded = rp.form == 6;
     const int rank = sharded ? c->x.rank : 0;
     double *const mine = sharded ? c->x.flow(rank) : nullptr;   // form 6: this rank's copy of the run's state
-    sl.spec = sharded ? reinterpret_cast<double *>(c->x.d_flowx) : s->d_spec;
+    sl.spec = sharded ? reinterpret_cast<double *>(c->x.d_flowx.d()) : s->d_spec.d();
     for (int t0 = 0; t0 < nsteps; t0 += 4096) {
         const int nt = std::min(4096, nsteps - t0);
         FlowX fxh;
@@ -1718,10 +1720,10 @@ static int run_one_launch(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, S
             memset(&fxh, 0, sizeof fxh);
             for (int r = 0; r < c->x.n; ++r) fxh.base[r] = c->x.flow(r);
             fxh.n = c->x.n; fxh.rank = rank; fxh.run = ++c->x.flow_run;
-            HIPCHK(hipMemcpyAsync(c->x.d_flowx, &fxh, sizeof fxh, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->x.d_flowx.d(), &fxh, sizeof fxh, hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(k_flow_init, dim3((unsigned)((R * 8 + 255) / 256)), dim3(256), 0, c->stream,
                                s->d_pos6, mine, (int)R);
-            hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx, (int)R, 0, fxh.run,
+            hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx.d(), (int)R, 0, fxh.run,
                                (const int *)nullptr);
             HIPCHK(hipGetLastError());
         } else {
@@ -1731,16 +1733,16 @@ static int run_one_launch(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, S
         sl.serial = ++g_flow_serial;
         sl.s_begin = rank * rp.p.per; sl.c_begin = s->nw / 2; sl.step = t0; sl.half = 0;
         sl.persist = 2 * nt;
-        sl.chain6 = store ? s->d_chain6 + (((size_t)rank * nsteps + t0) * 2 * nl) * 6 : nullptr;
-        sl.nacc = s->d_nacc + (size_t)rank * 2 * nl;
+        sl.chain6 = store ? s->d_chain6.d() + (((size_t)rank * nsteps + t0) * 2 * nl) * 6 : nullptr;
+        sl.nacc = s->d_nacc.d() + (size_t)rank * 2 * nl;
         sl.seed = step_key(s, t0);
         int rc = launch_sampler(c, rp, sl, ev);
         if (rc) return rc;
         if (sharded) {
-            hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx, (int)R, 1, fxh.run,
-                               (const int *)s->d_err);
+            hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx.d(), (int)R, 1, fxh.run,
+                               (const int *)s->d_err.d());
             hipLaunchKernelGGL(k_flow_wait_end, dim3(1), dim3(64), 0, c->stream, flow_view(mine, (int)R).endf, c->x.n, rank,
-                               fxh.run, c->x.spin_max, s->d_err);
+                               fxh.run, c->x.spin_max, s->d_err.d());
             hipLaunchKernelGGL(k_flow_finish, dim3((unsigned)((R * 6 + 255) / 256)), dim3(256), 0, c->stream,
                                s->d_pos6, mine, (int)R, 2 * nt);
             HIPCHK(hipGetLastError());
@@ -1762,8 +1764,8 @@ static int run_train(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, Sample
             for (int r = p.first; r <= p.last; ++r) {
                 sl.s_begin = hb + r * p.per; sl.c_begin = h ? 0 : half;
                 sl.step = t; sl.half = h;
-                sl.chain6 = store ? s->d_chain6 + ((((size_t)r * nsteps + t) * 2 + h) * nl) * 6 : nullptr;
-                sl.nacc = s->d_nacc + ((size_t)r * 2 + h) * nl;
+                sl.chain6 = store ? s->d_chain6.d() + ((((size_t)r * nsteps + t) * 2 + h) * nl) * 6 : nullptr;
+                sl.nacc = s->d_nacc.d() + ((size_t)r * 2 + h) * nl;
                 sl.seed = step_key(s, t);
                 if (p.xchg) ++c->x.seq;
                 if ((rc = launch_sampler(c, rp, sl, nullptr))) return rc;
@@ -1777,11 +1779,11 @@ static int run_train(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, Sample
         // and acceptance counts stay per rank (the caller gathers them if it wants them)
         if (c->x.seq)
             hipLaunchKernelGGL(k_xchg_wait, dim3(1), dim3(64), 0, c->stream, c->x.flags(c->x.rank), c->x.n,
-                               c->x.rank, c->x.seq, c->x.spin_max, s->d_err);
+                               c->x.rank, c->x.seq, c->x.spin_max, s->d_err.d());
         HIPCHK(hipGetLastError());
     } else if (p.collective) {   // every rank ends up with the whole chain and all counts
-        if (store && (rc = allgather_bytes(c, s->d_chain6, (size_t)nsteps * 2 * nl * 6 * sizeof(double)))) return rc;
-        if ((rc = allgather_bytes(c, s->d_nacc, 2 * nl * sizeof(unsigned int)))) return rc;
+        if (store && (rc = allgather_bytes(c, s->d_chain6.d(), (size_t)nsteps * 2 * nl * 6 * sizeof(double)))) return rc;
+        if ((rc = allgather_bytes(c, s->d_nacc.d(), 2 * nl * sizeof(unsigned int)))) return rc;
     }
     return MBB_OK;
 }
@@ -1797,22 +1799,23 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, 
     if (rp.resting) --c->flow_rest;
     if (rp.form >= 7) {
         const size_t R = (size_t)s->rows();
-        if (!s->d_spec) {
+        if (!s->d_spec.p) {
             // zeroed: the records of a one-launch run are taken by their check words, and freshly
             // allocated memory may hold those of another sampler's run
-            HIPCHK(hipMalloc((void **)&s->d_spec, spec_words(R) * sizeof(double)));
-            HIPCHK(hipMemsetAsync(s->d_spec, 0, spec_words(R) * sizeof(double), c->stream));
+            if (const int rc = s->d_spec.remake(spec_words(R) * sizeof(double))) return rc;
+            HIPCHK(hipMemsetAsync(s->d_spec.d(), 0, spec_words(R) * sizeof(double), c->stream));
         }
         if (backup) {
-            if (!s->d_bak) HIPCHK(hipMalloc((void **)&s->d_bak, R * 6 * sizeof(double) + R * sizeof(unsigned int)));
-            HIPCHK(hipMemcpyAsync(s->d_bak, s->d_pos6, R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(s->d_bak + R * 6, s->d_nacc, R * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+            if (!s->d_bak.p)
+                if (const int rc = s->d_bak.remake(R * 6 * sizeof(double) + R * sizeof(unsigned int))) return rc;
+            HIPCHK(hipMemcpyAsync(s->d_bak.d(), s->d_pos6, R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(s->d_bak.d() + R * 6, s->d_nacc.d(), R * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
         }
         s->backup_kept = backup;
         if (s->spec_form != 7 && s->spec_form != 9) {
             // forms 7 and 9 find their completion counters cleared by the launch before it (either's); after
             // another form (or a run that gave up) has used the memory, once from here
-            const FlowMView fvh = flowm_view(s->d_spec, (int)R);
+            const FlowMView fvh = flowm_view(s->d_spec.d(), (int)R);
             HIPCHK(hipMemsetAsync(fvh.done, 0, kFmDoneWords * sizeof(unsigned long long), c->stream));
             s->flowm_parity = 0;
         }
@@ -1828,10 +1831,10 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, 
         for (int r = 0; r < c->x.n; ++r) { xa.xpos[r] = c->x.pos6(r); xa.xflag[r] = c->x.flags(r); }
         xa.xcount = c->x.count(); xa.xn = c->x.n; xa.xrank = c->x.rank;
         xa.xseq0 = c->x.seq; xa.xspin_max = c->x.spin_max;
-        HIPCHK(hipMemcpyAsync(c->x.d_args, &xa, sizeof xa, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->x.d_args.d(), &xa, sizeof xa, hipMemcpyHostToDevice, c->stream));
     }
     SamplerLaunch sl;
-    sl.pos6 = s->d_pos6; sl.errflag = s->d_err; sl.nw = s->rows(); sl.nw_src = s->nw;
+    sl.pos6 = s->d_pos6; sl.errflag = s->d_err.d(); sl.nw = s->rows(); sl.nw_src = s->nw;
     sl.stretch_a = stretch_a; sl.zpow = s->zpow; sl.c_count = s->nw / 2; sl.m_count = rp.p.per;
     const int rc = rp.form >= 6 ? run_one_launch(c, s, rp, sl, nsteps, store, carried ? tev : nullptr)
                                 : run_train(c, s, rp, sl, nsteps, store);
@@ -1862,33 +1865,29 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
     if ((rc = sampler_check_pending(c, s))) return rc;
     if (store) s->resident_nsteps = 0;
     if (store && (size_t)nsteps * R * 6 > s->chain_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        free_dev(s->d_chain6); s->d_chain6 = nullptr; s->chain_cap = 0;
-        free_dev(s->d_chain_out); s->d_chain_out = nullptr;
-        if (s->h_chain) { (void)hipHostFree(s->h_chain); s->h_chain = nullptr; }
-        HIPCHK(hipMalloc((void **)&s->d_chain6, (size_t)nsteps * R * 6 * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&s->d_chain_out, (size_t)nsteps * R * 6 * sizeof(double)));
+        // (the exact size: a chain is as long as its run)
+        const size_t bytes = (size_t)nsteps * R * 6 * sizeof(double);
+        s->chain_cap = 0;
+        if ((rc = grow(c, s->d_chain6, bytes)) || (rc = grow(c, s->d_chain_out, bytes))) return rc;
         // (a landing buffer the host refuses to pin -- a limit on locked memory -- is done without: the chain
         // then goes straight into the caller's arrays, slower for big chains, never wrong)
         // (only chains big enough to go through it get one: pinning costs a few hundred microseconds)
+        s->h_chain.release();
         s->chain_cap = (size_t)nsteps * R * 6;
         s->h_chain_tried = false;
     }
-    if (to_host && !s->h_chain && !s->h_chain_tried && s->chain_cap * sizeof(double) > kChainDirectBytes) {
+    if (to_host && !s->h_chain.p && !s->h_chain_tried && s->chain_cap * sizeof(double) > kChainDirectBytes) {
         // (a run that only summarises its chain brings none back and pins nothing)
         s->h_chain_tried = true;
-        if (hipHostMalloc((void **)&s->h_chain, s->chain_cap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            s->h_chain = nullptr;
-        }
+        if (s->h_chain.remake(s->chain_cap * sizeof(double))) (void)hipGetLastError();
     }
     if ((rc = sampler_enqueue(c, s, rp, nsteps, stretch_a, store, true, nullptr))) return rc;
     std::vector<double> rows((size_t)R * 6);
     std::vector<unsigned int> nacc(R);
     int err = 0;
     HIPCHK(hipMemcpyAsync(rows.data(), s->d_pos6, rows.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(nacc.data(), s->d_nacc, nacc.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&err, s->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(nacc.data(), s->d_nacc.d(), nacc.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&err, s->d_err.d(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     // The chain comes back in the caller's layout: re-ordered on the device, copied straight into the
     // caller's arrays.  (A rank of a run sharded with the one-hop exchange holds its own walkers' part
     // only: there the old way, through a staging vector, fills just those rows.)
@@ -1898,33 +1897,33 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
     if (direct) {
         const long long cells = (long long)R * nsteps;
         hipLaunchKernelGGL(k_chain_reorder, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream,
-                           (const double *)s->d_chain6, s->d_chain_out, nsteps, nw, half, p.per, s->nsrc, p.shards);
+                           (const double *)s->d_chain6.d(), s->d_chain_out.d(), nsteps, nw, half, p.per, s->nsrc, p.shards);
         HIPCHK(hipGetLastError());
         // small chains go straight into the caller's arrays (the runtime stages them through its own pinned
         // buffers); big ones land in ours first -- a D2H into megabytes of pageable, untouched memory runs at
         // ~1 GB/s (measured: 3 MB direct 0.43 ms against 1.35 ms staged; 24 MB direct 25 ms against 6 ms staged)
-        via_pinned = to_host && s->h_chain != nullptr && (size_t)cells * 6 * sizeof(double) > kChainDirectBytes;
+        via_pinned = to_host && s->h_chain.p != nullptr && (size_t)cells * 6 * sizeof(double) > kChainDirectBytes;
         if (via_pinned) {
-            HIPCHK(hipMemcpyAsync(s->h_chain, s->d_chain_out, (size_t)cells * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(s->h_chain.h(), s->d_chain_out.d(), (size_t)cells * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         } else {
-            if (chain) HIPCHK(hipMemcpyAsync(chain, s->d_chain_out, (size_t)cells * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            if (lnprob) HIPCHK(hipMemcpyAsync(lnprob, s->d_chain_out + (size_t)cells * 5, (size_t)cells * sizeof(double),
+            if (chain) HIPCHK(hipMemcpyAsync(chain, s->d_chain_out.d(), (size_t)cells * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            if (lnprob) HIPCHK(hipMemcpyAsync(lnprob, s->d_chain_out.d() + (size_t)cells * 5, (size_t)cells * sizeof(double),
                                               hipMemcpyDeviceToHost, c->stream));
         }
     } else if (store) {
         ch.resize((size_t)nsteps * R * 6);
-        HIPCHK(hipMemcpyAsync(ch.data(), s->d_chain6, ch.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(ch.data(), s->d_chain6.d(), ch.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     if (err) {
-        HIPCHK(hipMemset(s->d_err, 0, sizeof(int)));
+        HIPCHK(hipMemset(s->d_err.d(), 0, sizeof(int)));
         if (err == 8) return fail(MBB_ERR_RCCL, "the exchange timed out: a peer did not post its launch");
         if (err == 9 && s->backup_kept) {
             // The one-launch run gave up waiting (not every workgroup was resident): back to the state it
             // started from and the same steps as a train of launches -- the same chain.  The next run takes
             // the one-launch form again; kFlowStrikes give-ups in a row rest it for kFlowRest runs.
-            HIPCHK(hipMemcpyAsync(s->d_pos6, s->d_bak, (size_t)R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(s->d_nacc, s->d_bak + (size_t)R * 6, (size_t)R * sizeof(unsigned int), hipMemcpyDeviceToDevice,
+            HIPCHK(hipMemcpyAsync(s->d_pos6, s->d_bak.d(), (size_t)R * 6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(s->d_nacc.d(), s->d_bak.d() + (size_t)R * 6, (size_t)R * sizeof(unsigned int), hipMemcpyDeviceToDevice,
                                   c->stream));
             s->steps_done -= (unsigned long long)nsteps;
             s->spec_form = 0;
@@ -1946,8 +1945,8 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
     if (s->backup_kept) c->flow_strikes = 0;                // a one-launch run that went through
     if (direct && via_pinned) {
         const size_t cells = (size_t)R * nsteps;
-        if (chain) memcpy(chain, s->h_chain, cells * 5 * sizeof(double));
-        if (lnprob) memcpy(lnprob, s->h_chain + cells * 5, cells * sizeof(double));
+        if (chain) memcpy(chain, s->h_chain.h(), cells * 5 * sizeof(double));
+        if (lnprob) memcpy(lnprob, s->h_chain.h() + cells * 5, cells * sizeof(double));
     }
     for (int i = 0; i < R; ++i) {
         if (pos_out) for (int k = 0; k < 5; ++k) pos_out[(size_t)i * 5 + k] = rows[(size_t)i * 6 + k];
@@ -1971,7 +1970,7 @@ static int sampler_run(mbb_ctx *c, mbb_sampler_state *s, int nsteps, double stre
     if (direct) s->resident_nsteps = nsteps;
     if (sspec) {
         const size_t cells = (size_t)R * nsteps;
-        return summary_run(c, s->d_chain_out, s->d_chain_out + cells * 5, s->nsrc, nw, nsteps, sspec, sout);
+        return summary_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, nw, nsteps, sspec, sout);
     }
     return MBB_OK;
 }
@@ -2020,42 +2019,38 @@ extern "C" int mbb_sampler_advance_timed(mbb_ctx *c, void *sp, int nsteps, doubl
     if (!s || nsteps < 0 || !wall_s || !stream_ms) return fail(MBB_ERR_ARG, "bad sampler arguments");
     if (s->lost) return sampler_check_pending(c, s);
     s->unchecked = true;
-    if (!c->ev_timed[0]) {
-        HIPCHK(hipEventCreate(&c->ev_timed[0]));
-        HIPCHK(hipEventCreate(&c->ev_timed[1]));
-    }
+    if ((rc = c->ev_timed.create())) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     RunPlan rp;
     if ((rc = plan_sampler_run(c, s, nsteps, true, rp))) return rc;
-    if ((rc = sampler_enqueue(c, s, rp, nsteps, stretch_a, false, false, c->ev_timed))) return rc;
+    if ((rc = sampler_enqueue(c, s, rp, nsteps, stretch_a, false, false, c->ev_timed.e))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     const auto t1 = std::chrono::steady_clock::now();
     *wall_s = std::chrono::duration<double>(t1 - t0).count();
-    HIPCHK(hipEventElapsedTime(stream_ms, c->ev_timed[0], c->ev_timed[1]));
+    HIPCHK(hipEventElapsedTime(stream_ms, c->ev_timed.e[0], c->ev_timed.e[1]));
     return MBB_OK;
 }
 
 // ---- SED-level entry points -------------------------------------------------
 static int ensure_sed(mbb_ctx *c, size_t n, size_t nout)
 {
-    if (n > c->sed_cap) {
-        size_t cap = c->sed_cap ? c->sed_cap : 64;
+    mbb_ctx::SedWork &w = c->sed;
+    int rc;
+    if (n > w.cap) {
+        size_t cap = w.cap ? w.cap : 64;
         while (cap < n) cap *= 2;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        free_dev(c->d_sed_pars); free_dev(c->d_sed_status); free_dev(c->d_sed_wk);
-        c->d_sed_pars = nullptr; c->d_sed_status = nullptr; c->d_sed_wk = nullptr; c->sed_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_sed_pars, cap * 5 * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&c->d_sed_status, cap * sizeof(int32_t)));
-        HIPCHK(hipMalloc((void **)&c->d_sed_wk, cap * sizeof(WalkerK)));
-        c->sed_cap = cap;
+        w.cap = 0;
+        if ((rc = grow(c, w.pars, cap * 5 * sizeof(double))) || (rc = grow(c, w.status, cap * sizeof(int32_t))) ||
+            (rc = grow(c, w.wk, cap * sizeof(WalkerK))))
+            return rc;
+        w.cap = cap;
     }
-    if (nout > c->sed_out_cap) {
-        size_t cap = c->sed_out_cap ? c->sed_out_cap : 1024;
+    if (nout > w.out_cap) {
+        size_t cap = w.out_cap ? w.out_cap : 1024;
         while (cap < nout) cap *= 2;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        free_dev(c->d_sed_out); c->d_sed_out = nullptr; c->sed_out_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_sed_out, cap * sizeof(double)));
-        c->sed_out_cap = cap;
+        w.out_cap = 0;
+        if ((rc = grow(c, w.out, cap * sizeof(double)))) return rc;
+        w.out_cap = cap;
     }
     return MBB_OK;
 }
@@ -2075,8 +2070,8 @@ static int launch_prologue(mbb_ctx *c, const double *d_pars, int n, int opthin, 
     dispatch_variant(opthin, noalpha, [&](auto OT, auto NA) {
         hipLaunchKernelGGL((k_prologue<decltype(OT)::value, decltype(NA)::value>), dim3(grid),
                            dim3(threads), 0, c->stream, d_pars, n, kUmToGHz / wavenorm,
-                           log(kUmToGHz / wavenorm), want_peak, d_out6, c->d_sed_status,
-                           c->d_sed_wk);
+                           log(kUmToGHz / wavenorm), want_peak, d_out6, c->sed.status.d(),
+                           c->sed.wk.d());
     });
     HIPCHK(hipGetLastError());
     return MBB_OK;
@@ -2085,9 +2080,9 @@ static int launch_prologue(mbb_ctx *c, const double *d_pars, int n, int opthin, 
 static int run_prologue(mbb_ctx *c, const double *pars, int n, int opthin, int noalpha,
                         double wavenorm, int want_peak, double *d_out6)
 {
-    HIPCHK(hipMemcpyAsync(c->d_sed_pars, pars, (size_t)n * 5 * sizeof(double),
+    HIPCHK(hipMemcpyAsync(c->sed.pars.d(), pars, (size_t)n * 5 * sizeof(double),
                           hipMemcpyHostToDevice, c->stream));
-    return launch_prologue(c, c->d_sed_pars, n, opthin, noalpha, wavenorm, want_peak, d_out6);
+    return launch_prologue(c, c->sed.pars.d(), n, opthin, noalpha, wavenorm, want_peak, d_out6);
 }
 
 extern "C" int mbb_sed_prologue_batch(mbb_ctx *c, const double *pars, int n, int opthin,
@@ -2098,11 +2093,11 @@ extern "C" int mbb_sed_prologue_batch(mbb_ctx *c, const double *pars, int n, int
     if (rc) return rc;
     if (n <= 0 || !pars || !out) return fail(MBB_ERR_ARG, "bad arguments");
     if ((rc = ensure_sed(c, (size_t)n, (size_t)n * 6))) return rc;
-    if ((rc = run_prologue(c, pars, n, opthin, noalpha, wavenorm, want_peak, c->d_sed_out))) return rc;
-    HIPCHK(hipMemcpyAsync(out, c->d_sed_out, (size_t)n * 6 * sizeof(double),
+    if ((rc = run_prologue(c, pars, n, opthin, noalpha, wavenorm, want_peak, c->sed.out.d()))) return rc;
+    HIPCHK(hipMemcpyAsync(out, c->sed.out.d(), (size_t)n * 6 * sizeof(double),
                           hipMemcpyDeviceToHost, c->stream));
     if (status)
-        HIPCHK(hipMemcpyAsync(status, c->d_sed_status, (size_t)n * sizeof(int32_t),
+        HIPCHK(hipMemcpyAsync(status, c->sed.status.d(), (size_t)n * sizeof(int32_t),
                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return MBB_OK;
@@ -2118,19 +2113,19 @@ extern "C" int mbb_sed_eval_batch(mbb_ctx *c, const double *pars, int n, int opt
     if (n > 65535) return fail(MBB_ERR_ARG, "at most 65535 rows per call");
     const size_t nout = (size_t)n * m;
     if ((rc = ensure_sed(c, (size_t)n, nout + (size_t)m))) return rc;
-    double *d_freq = c->d_sed_out + nout;
+    double *d_freq = c->sed.out.d() + nout;
     if ((rc = run_prologue(c, pars, n, opthin, noalpha, wavenorm, 0, nullptr))) return rc;
     HIPCHK(hipMemcpyAsync(d_freq, freq, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const int threads = 256;
     dim3 grid((m + threads - 1) / threads, n);
     dispatch_variant(opthin, noalpha, [&](auto OT, auto NA) {
         hipLaunchKernelGGL((k_sed_eval<decltype(OT)::value, decltype(NA)::value>), grid,
-                           dim3(threads), 0, c->stream, c->d_sed_wk, d_freq, m, c->d_sed_out);
+                           dim3(threads), 0, c->stream, c->sed.wk.d(), d_freq, m, c->sed.out.d());
     });
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, c->d_sed_out, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->sed.out.d(), nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (status)
-        HIPCHK(hipMemcpyAsync(status, c->d_sed_status, (size_t)n * sizeof(int32_t),
+        HIPCHK(hipMemcpyAsync(status, c->sed.status.d(), (size_t)n * sizeof(int32_t),
                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return MBB_OK;
@@ -2167,35 +2162,25 @@ extern "C" int mbb_sed_integrate_batch(mbb_ctx *c, const double *pars, int n, in
     if ((rc = ensure_sed(c, (size_t)n, (size_t)n + 2 * ngl))) return rc;
     double gx[64], gw[64];
     gauss_legendre64(gx, gw);
-    double *d_gx = c->d_sed_out + n, *d_gw = d_gx + ngl;
+    double *d_gx = c->sed.out.d() + n, *d_gw = d_gx + ngl;
     if ((rc = run_prologue(c, pars, n, opthin, noalpha, wavenorm, 0, nullptr))) return rc;
     HIPCHK(hipMemcpyAsync(d_gx, gx, sizeof gx, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_gw, gw, sizeof gw, hipMemcpyHostToDevice, c->stream));
     dispatch_variant(opthin, noalpha, [&](auto OT, auto NA) {
         hipLaunchKernelGGL((k_sed_integrate<decltype(OT)::value, decltype(NA)::value>), dim3(n),
-                           dim3(64), 0, c->stream, c->d_sed_wk, numin, numax, d_gx, d_gw, ngl,
-                           8, c->d_sed_out);
+                           dim3(64), 0, c->stream, c->sed.wk.d(), numin, numax, d_gx, d_gw, ngl,
+                           8, c->sed.out.d());
     });
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, c->d_sed_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->sed.out.d(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (status)
-        HIPCHK(hipMemcpyAsync(status, c->d_sed_status, (size_t)n * sizeof(int32_t),
+        HIPCHK(hipMemcpyAsync(status, c->sed.status.d(), (size_t)n * sizeof(int32_t),
                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return MBB_OK;
 }
 
 // ---- analyses of a resident chain: what the summary, the diagnostics and the marginals share ------------------------
-static int grow(mbb_ctx *c, DevBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return MBB_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    b.release();
-    HIPCHK(hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return MBB_OK;
-}
-
 // A result block handed out array by array: take<T>(n) is its next n values of T, put(dst, n) copies them out of a
 // host image of the block.  (The callers list their arrays by falling alignment, the same list on either side.)
 struct Carve {
@@ -2208,14 +2193,14 @@ struct Carve {
 template <typename F>
 static int with_uploaded_chain(mbb_ctx *c, const double *chain, const double *lnprob, size_t cells, F &&run)
 {
-    double *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, cells * (lnprob ? 6 : 5) * sizeof(double)));
+    Dev<double> buf;
+    if (const int rc = buf.remake(cells * (lnprob ? 6 : 5) * sizeof(double))) return rc;
+    double *const d = buf.d();
     hipError_t e = hipMemcpyAsync(d, chain, cells * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && lnprob)
         e = hipMemcpyAsync(d + cells * 5, lnprob, cells * sizeof(double), hipMemcpyHostToDevice, c->stream);
     const int rc = e != hipSuccess ? fail(MBB_ERR_HIP, "upload of the chain", e) : run((const double *)d);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
+    (void)hipStreamSynchronize(c->stream);       // (before buf goes)
     return rc;
 }
 
@@ -2240,7 +2225,7 @@ static int analysed_sampler(mbb_ctx *c, void *sp, bool args_ok, const char *verb
 // sampler_run alone, after k_chain_reorder has written d_chain_out: the chain is never null when it is.)
 static int resident_chain(const mbb_sampler_state *s)
 {
-    if (s->resident_nsteps > 0 && s->d_chain_out) return MBB_OK;
+    if (s->resident_nsteps > 0 && s->d_chain_out.p) return MBB_OK;
     return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
 }
 
@@ -2328,7 +2313,7 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbc::Ch
     const int ngl = 64;
     const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
     if ((rc = ensure_sed(c, chunk, chunk * 6 + 2 * ngl))) return rc;
-    double *d_gx = c->d_sed_out + chunk * 6, *d_gw = d_gx + ngl;
+    double *d_gx = c->sed.out.d() + chunk * 6, *d_gw = d_gx + ngl;
     // what depends on redshift and distance: one entry for the call, or a table with one per source
     mbbs::SrcConst one = {};
     mbbs::SrcConst *d_src = nullptr;
@@ -2368,9 +2353,9 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbc::Ch
         if (der[0]) {
             // peak wavelength: the prologue with want_peak, the fit's model or the reference's (results.py:574-581)
             const int ot = sp->peak_model ? 0 : c->opthin, na = sp->peak_model ? 0 : c->noalpha;
-            if ((rc = launch_prologue(c, rows, n, ot, na, c->wavenorm, 1, c->d_sed_out))) return rc;
-            hipLaunchKernelGGL(mbbs::k_sum_take, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
-                               (const int32_t *)c->d_sed_status, n, (long long)off, der[0], colstatus,
+            if ((rc = launch_prologue(c, rows, n, ot, na, c->wavenorm, 1, c->sed.out.d()))) return rc;
+            hipLaunchKernelGGL(mbbs::k_sum_take, dim3(grid), dim3(256), 0, c->stream, (const double *)c->sed.out.d(),
+                               (const int32_t *)c->sed.status.d(), n, (long long)off, der[0], colstatus,
                                a.nw, a.nsteps, a.burn, a.thin);
             HIPCHK(hipGetLastError());
         }
@@ -2380,23 +2365,23 @@ static int summary_fill_derived(mbb_ctx *c, const mbb_summary_spec *sp, mbbc::Ch
             dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
                 if (per_src)
                     hipLaunchKernelGGL((k_sed_integrate_src<decltype(OT)::value, decltype(NA)::value>), dim3(n),
-                                       dim3(64), 0, c->stream, c->d_sed_wk, (const double *)d_src,
+                                       dim3(64), 0, c->stream, c->sed.wk.d(), (const double *)d_src,
                                        (int)(sizeof(mbbs::SrcConst) / sizeof(double)), (long long)off, per, d_gx, d_gw,
-                                       ngl, 8, c->d_sed_out);
+                                       ngl, 8, c->sed.out.d());
                 else
                     hipLaunchKernelGGL((k_sed_integrate<decltype(OT)::value, decltype(NA)::value>), dim3(n), dim3(64),
-                                       0, c->stream, c->d_sed_wk, one.numin, one.numax, d_gx, d_gw,
-                                       ngl, 8, c->d_sed_out);
+                                       0, c->stream, c->sed.wk.d(), one.numin, one.numax, d_gx, d_gw,
+                                       ngl, 8, c->sed.out.d());
             });
             HIPCHK(hipGetLastError());
             if (per_src)
                 hipLaunchKernelGGL(mbbs::k_sum_lir_src, dim3(grid), dim3(256), 0, c->stream,
-                                   (const double *)c->d_sed_out, (const int32_t *)c->d_sed_status, n, (long long)off,
+                                   (const double *)c->sed.out.d(), (const int32_t *)c->sed.status.d(), n, (long long)off,
                                    (const mbbs::SrcConst *)d_src, der[1], colstatus, a.nw, a.nsteps,
                                    a.burn, a.thin);
             else
-                hipLaunchKernelGGL(mbbs::k_sum_lir, dim3(grid), dim3(256), 0, c->stream, (const double *)c->d_sed_out,
-                                   (const int32_t *)c->d_sed_status, n, (long long)off, one.prefac, der[1],
+                hipLaunchKernelGGL(mbbs::k_sum_lir, dim3(grid), dim3(256), 0, c->stream, (const double *)c->sed.out.d(),
+                                   (const int32_t *)c->sed.status.d(), n, (long long)off, one.prefac, der[1],
                                    colstatus, a.nw, a.nsteps, a.burn, a.thin);
             HIPCHK(hipGetLastError());
         }
@@ -2567,7 +2552,7 @@ extern "C" int mbb_sampler_run_summary(mbb_ctx *c, void *sp, int nsteps, double 
     if (nsteps == 0) {
         if ((rc = resident_chain(s))) return rc;
         const size_t cells = (size_t)s->rows() * s->resident_nsteps;
-        return summary_run(c, s->d_chain_out, s->d_chain_out + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+        return summary_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
     }
     return sampler_run(c, s, nsteps, stretch_a, chain, lnprob, pos_out, lnprob_out, naccepted, true, spec, out);
 }
@@ -2664,7 +2649,7 @@ extern "C" int mbb_sampler_diagnostics(mbb_ctx *c, void *sp, const mbb_diag_spec
     mbb_sampler_state *s;
     int rc;
     if ((rc = analysed_sampler(c, sp, spec && out, "diagnosed", s)) || (rc = resident_chain(s))) return rc;
-    return diag_run(c, s->d_chain_out, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return diag_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 
 // ---- binned marginals of a chain (mbb_marginals.hip.h) ------------------------
@@ -2782,7 +2767,7 @@ extern "C" int mbb_sampler_marginals(mbb_ctx *c, void *sp, const mbb_marginals_s
     mbb_sampler_state *s;
     int rc;
     if ((rc = analysed_sampler(c, sp, spec && out, "binned", s)) || (rc = resident_chain(s))) return rc;
-    return marg_run(c, s->d_chain_out, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return marg_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).
@@ -2797,20 +2782,20 @@ extern "C" int mbb_roof_probe(mbb_ctx *c, const double pars[5], int reps, double
     const int grid = (int)(c->opt_roof_wgs > 0 ? c->opt_roof_wgs : 2) * c->cu_count;
     if ((rc = ensure_sed(c, 1, (size_t)grid * threads + 2))) return rc;
     if ((rc = run_prologue(c, pars, 1, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
-    unsigned long long *d_clk = reinterpret_cast<unsigned long long *>(c->d_sed_out + (size_t)grid * threads);
+    unsigned long long *d_clk = reinterpret_cast<unsigned long long *>(c->sed.out.d() + (size_t)grid * threads);
     LikeArgs a;
     memset(&a, 0, sizeof a);
-    a.nu = c->d_nu; a.lnnu = c->d_lnnu; a.wt = c->d_wt;
+    a.nu = c->band.nu.d(); a.lnnu = c->band.lnnu.d(); a.wt = c->band.wt.d();
     a.poly_b = c->d_poly_b; a.poly_c = c->d_poly_c;
     a.nchunk = c->nchunk;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    EventPair ev;
+    if ((rc = ev.create())) return rc;
+    const hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
     for (int pass = 0; pass < 2; ++pass) {            // the first pass warms clocks and caches
         HIPCHK(hipEventRecord(e0, c->stream));
         dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
             hipLaunchKernelGGL((k_roof<decltype(OT)::value, decltype(NA)::value>), dim3(grid), dim3(threads),
-                               0, c->stream, a, c->d_sed_wk, reps, c->d_sed_out, d_clk);
+                               0, c->stream, a, c->sed.wk.d(), reps, c->sed.out.d(), d_clk);
         });
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e1, c->stream));
@@ -2818,8 +2803,6 @@ extern "C" int mbb_roof_probe(mbb_ctx *c, const double pars[5], int reps, double
     }
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    HIPCHK(hipEventDestroy(e0));
-    HIPCHK(hipEventDestroy(e1));
     *seconds = ms * 1e-3;
     *lane_slots = (double)grid * (threads / 64) * (double)reps * c->nchunk * 64.0;
     if (clock_mhz) {
@@ -2838,16 +2821,16 @@ extern "C" int mbb_fnu_eval(mbb_ctx *c, int opthin, int noalpha, const double *f
     if (rc) return rc;
     if (n <= 0 || !freq || !out) return fail(MBB_ERR_ARG, "bad arguments");
     if ((rc = ensure_sed(c, 1, (size_t)2 * n))) return rc;
-    double *d_freq = c->d_sed_out + n;
+    double *d_freq = c->sed.out.d() + n;
     HIPCHK(hipMemcpyAsync(d_freq, freq, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const int threads = 256, grid = (n + threads - 1) / threads;
     dispatch_variant(opthin, noalpha, [&](auto OT, auto NA) {
         hipLaunchKernelGGL((k_fnu_explicit<decltype(OT)::value, decltype(NA)::value>), dim3(grid),
                            dim3(threads), 0, c->stream, d_freq, n, T, beta, x0, alpha, normfac,
-                           xmerge, kappa, c->d_sed_out);
+                           xmerge, kappa, c->sed.out.d());
     });
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, c->d_sed_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->sed.out.d(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return MBB_OK;
 }
@@ -2931,14 +2914,14 @@ extern "C" int mbb_stamps(mbb_ctx *c, unsigned long long *host, int nblocks)
 {
     int rc = use(c);
     if (rc) return rc;
-    if (!c->d_stamps) {
-        HIPCHK(hipMalloc((void **)&c->d_stamps, 32 * sizeof(unsigned long long) * 65536));
-        HIPCHK(hipMemset(c->d_stamps, 0, 32 * sizeof(unsigned long long) * 65536));
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(mbbd::g_pstamps), &c->d_stamps, sizeof(c->d_stamps)));
+    if (!c->stamps.p) {
+        if ((rc = c->stamps.remake(32 * sizeof(unsigned long long) * 65536))) return rc;
+        HIPCHK(hipMemset(c->stamps.d(), 0, 32 * sizeof(unsigned long long) * 65536));
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(mbbd::g_pstamps), &c->stamps.p, sizeof(c->stamps.p)));
     }
     if (host) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(host, c->d_stamps, 32 * sizeof(unsigned long long) * nblocks, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(host, c->stamps.d(), 32 * sizeof(unsigned long long) * nblocks, hipMemcpyDeviceToHost));
     }
     return MBB_OK;
 }
@@ -3037,38 +3020,29 @@ extern "C" int mbb_get_info(mbb_ctx *c, const char *name, long *value)
 // ---- one-hop exchange between the ranks of a sharded sampler run ----------------
 // (the direct exchange on the xGMI mesh instead of a ring
 // collective for a 6 KB message.)  Replaces emcee's pool, mbb_fit.py:80-81.
-static int xchg_free(mbb_ctx *c)
-{
-    for (int r = 0; r < c->x.n; ++r)
-        if (r != c->x.rank && c->x.peer[r]) (void)hipIpcCloseMemHandle(c->x.peer[r]);
-    free_dev(c->x.base);
-    free_dev(c->x.d_args);
-    free_dev(c->x.d_flowx);
-    c->x = mbb_ctx::Xchg();
-    return MBB_OK;
-}
-
 extern "C" int mbb_xchg_open(mbb_ctx *c, int nranks, int rank, int max_rows, unsigned char handle[64])
 {
     int rc = use(c);
     if (rc) return rc;
     if (nranks < 1 || nranks > 16 || rank < 0 || rank >= nranks || max_rows <= 0 || !handle)
         return fail(MBB_ERR_ARG, "bad exchange layout (at most 16 ranks)");
-    if (c->x.base) return fail(MBB_ERR_STATE, "this context already has an exchange (mbb_xchg_close first)");
+    if (c->x.base.p) return fail(MBB_ERR_STATE, "this context already has an exchange (mbb_xchg_close first)");
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "handle size");
     const size_t bytes = mbb_ctx::Xchg::kHeader + (size_t)max_rows * 6 * sizeof(double) +
                          spec_words((size_t)max_rows) * sizeof(double);
     // fine-grained: peers' system-scope stores must be visible to this device's loads while
     // kernels run on both sides
-    HIPCHK(hipExtMallocWithFlags((void **)&c->x.base, bytes, hipDeviceMallocFinegrained));
-    HIPCHK(hipMemset(c->x.base, 0, bytes));
-    HIPCHK(hipDeviceSynchronize());
+    // (an exchange that does not get as far as its handle is closed again: nothing half-made stays with the context)
+    if ((rc = c->x.base.remake(bytes))) return rc;
     hipIpcMemHandle_t h;
-    hipError_t e = hipIpcGetMemHandle(&h, c->x.base);
-    if (e != hipSuccess) { free_dev(c->x.base); c->x.base = nullptr; return fail(MBB_ERR_HIP, "hipIpcGetMemHandle", e); }
+    hipError_t e = hipMemset(c->x.base.d(), 0, bytes);
+    const char *what = "hipMemset(c->x.base, 0, bytes)";
+    if (e == hipSuccess) { e = hipDeviceSynchronize(); what = "hipDeviceSynchronize()"; }
+    if (e == hipSuccess) { e = hipIpcGetMemHandle(&h, c->x.base.d()); what = "hipIpcGetMemHandle"; }
+    if (e != hipSuccess) { c->x.close(); return fail(MBB_ERR_HIP, what, e); }
     memcpy(handle, &h, 64);
     c->x.n = nranks; c->x.rank = rank; c->x.cap_rows = (size_t)max_rows; c->x.connected = 0; c->x.seq = 0;
-    c->x.peer[rank] = c->x.base;
+    c->x.peer[rank] = c->x.base.d();
     return MBB_OK;
 }
 
@@ -3078,7 +3052,7 @@ extern "C" int mbb_xchg_connect(mbb_ctx *c, const unsigned char *handles)
 {
     int rc = use(c);
     if (rc) return rc;
-    if (!c->x.base || !handles) return fail(MBB_ERR_STATE, "mbb_xchg_open first");
+    if (!c->x.base.p || !handles) return fail(MBB_ERR_STATE, "mbb_xchg_open first");
     if (c->x.connected) return fail(MBB_ERR_STATE, "exchange already connected");
     for (int r = 0; r < c->x.n; ++r) {
         if (r == c->x.rank) continue;
@@ -3089,8 +3063,7 @@ extern "C" int mbb_xchg_connect(mbb_ctx *c, const unsigned char *handles)
         if (e != hipSuccess) return fail(MBB_ERR_HIP, "hipIpcOpenMemHandle", e);
         c->x.peer[r] = (unsigned char *)p;
     }
-    HIPCHK(hipMalloc((void **)&c->x.d_args, sizeof(XchgArgs)));
-    HIPCHK(hipMalloc((void **)&c->x.d_flowx, sizeof(FlowX)));
+    if ((rc = c->x.d_args.remake(sizeof(XchgArgs))) || (rc = c->x.d_flowx.remake(sizeof(FlowX)))) return rc;
     c->x.connected = 1;
     return MBB_OK;
 }
@@ -3101,7 +3074,8 @@ extern "C" int mbb_xchg_close(mbb_ctx *c)
     if (rc) return rc;
     if (c->x.users > 0) return fail(MBB_ERR_STATE, "a sampler still lives in the exchange buffer (mbb_sampler_destroy first)");
     HIPCHK(hipStreamSynchronize(c->stream));
-    return xchg_free(c);
+    c->x.close();
+    return MBB_OK;
 }
 
 // ---- RCCL -------------------------------------------------------------------
@@ -3179,43 +3153,37 @@ extern "C" int mbb_lnlike_allgather(mbb_ctx *c, const double *pars, int n, doubl
     if (!c->comm && c->nranks != 1) return fail(MBB_ERR_STATE, "communicator not initialised");
     if ((rc = ensure_capacity(c, (size_t)n, false))) return rc;
     const size_t total = (size_t)nranks * n;
-    if (total > c->gather_cap) {
-        size_t cap = c->gather_cap ? c->gather_cap : 1024;
-        while (cap < total) cap *= 2;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        free_dev(c->d_gather); free_host(c->h_gather);
-        c->d_gather = c->h_gather = nullptr; c->gather_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_gather, cap * sizeof(double)));
-        HIPCHK(hipHostMalloc((void **)&c->h_gather, cap * sizeof(double), hipHostMallocDefault));
-        c->gather_cap = cap;
+    {
+        size_t cap = c->gather.d.cap ? c->gather.d.cap : 1024 * sizeof(double);
+        while (cap < total * sizeof(double)) cap *= 2;
+        if ((rc = grow(c, c->gather.d, cap)) || (rc = grow(c, c->gather.h, cap))) return rc;
     }
     const size_t nbytes = (size_t)n * 5 * sizeof(double);
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->w_pars;
+    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
     double *dp;
     int32_t *ds;
     if (push) {
-        memcpy(c->w_pars, pars, nbytes);
+        memcpy(c->bnd.w_pars.d(), pars, nbytes);
         __builtin_ia32_sfence();
-        dp = c->w_pars;
+        dp = c->bnd.w_pars.d();
     } else {
-        memcpy(c->h_pars, pars, nbytes);
-        if (c->opt_zero_copy) HIPCHK(hipHostGetDevicePointer((void **)&dp, c->h_pars, 0));
+        memcpy(c->bnd.h_pars.h(), pars, nbytes);
+        if (c->opt_zero_copy) dp = c->bnd.h_pars.dv();
         else {
-            HIPCHK(hipMemcpyAsync(c->d_pars, c->h_pars, nbytes, hipMemcpyHostToDevice, c->stream));
-            dp = c->d_pars;
+            HIPCHK(hipMemcpyAsync(c->bnd.d_pars.d(), c->bnd.h_pars.h(), nbytes, hipMemcpyHostToDevice, c->stream));
+            dp = c->bnd.d_pars.d();
         }
     }
-    if (c->opt_zero_copy) HIPCHK(hipHostGetDevicePointer((void **)&ds, c->h_status, 0));
-    else ds = c->d_status;
-    double *mine = c->d_gather + (size_t)rank * n;
+    ds = c->opt_zero_copy ? c->bnd.h_status.dv() : c->bnd.d_status.d();
+    double *mine = c->gather.d.d() + (size_t)rank * n;
     if ((rc = launch_rows(c, dp, n, mine, ds, nullptr))) return rc;
-    if ((rc = mbb_allgather_f64(c, mine, c->d_gather, n))) return rc;
-    HIPCHK(hipMemcpyAsync(c->h_gather, c->d_gather, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = mbb_allgather_f64(c, mine, c->gather.d.d(), n))) return rc;
+    HIPCHK(hipMemcpyAsync(c->gather.h.h(), c->gather.d.d(), total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (!c->opt_zero_copy)
-        HIPCHK(hipMemcpyAsync(c->h_status, c->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bnd.h_status.h(), c->bnd.d_status.d(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if ((rc = wait_stream(c))) return rc;
-    memcpy(all, c->h_gather, total * sizeof(double));
-    if (status) memcpy(status, c->h_status, (size_t)n * sizeof(int32_t));
+    memcpy(all, c->gather.h.h(), total * sizeof(double));
+    if (status) memcpy(status, c->bnd.h_status.h(), (size_t)n * sizeof(int32_t));
     return MBB_OK;
 }
 

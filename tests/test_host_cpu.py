@@ -777,6 +777,26 @@ def test_sanitizers():
         and "runtime error" not in text, text[-3000:]
 
 
+def test_owners_under_sanitizers(tmp_path):
+    """The owners of every device and pinned allocation of the host library (mbb_emcee_amd/csrc/mbb_owned.h) over
+    malloc / free: tests/owned_main.cpp, a program of its own built with AddressSanitizer (leaks included) and UBSan
+    and run directly -- grow within and beyond capacity, a failed allocation, destruction, a struct of owners whose
+    allocations stop midway, a sampler's state held by a unique_ptr whose second allocation fails."""
+    import shutil
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    libs = [subprocess.check_output([gxx, "-print-file-name=" + n]).decode().strip() for n in ("libasan.so", "libubsan.so")]
+    if not all(os.path.isabs(p) and os.path.exists(p) for p in libs):
+        pytest.skip("g++'s sanitizer runtimes are not installed")
+    exe = str(tmp_path / "owned_main")
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "owned_main.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    text = out.stdout.decode(errors="replace")
+    assert out.returncode == 0 and "OWNED_OK" in text, text[-3000:]
+
+
 # ------------------------------------------------- dust mass (results.py:726-801), parity unpinned
 def test_dustmass_identities():
     """postprocess.dustmass restates results.py:746-801, which cannot be imported here
