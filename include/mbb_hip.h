@@ -347,6 +347,48 @@ int mbb_chain_marginals(mbb_ctx *ctx, const double *chain, int nsrc, int nw, int
  * none, and for a sharded run, as mbb_sampler_diagnostics. */
 int mbb_sampler_marginals(mbb_ctx *ctx, void *sampler, const mbb_marginals_spec *spec, const mbb_marginals_out *out);
 
+/* ---- predicted fluxes of a chain, computed where the chain is ---- */
+/* Replaces: mbb_results.predflux_cen (results.py:895-985): the model flux of every chain entry at a wavelength or
+ * through a passband, then _parcen_internal's mean and percentiles of that column.  A prediction target ("spec") is a
+ * list of quadrature samples (frequency in GHz, weight): a passband's samples with weight sedmult * normfac
+ * (response.py:575-576), or the single sample (um_to_GHz / lambda, 1) of a wavelength or a delta-function band.  Spec
+ * s has samples sample_off[s] <= i < sample_off[s + 1] of freq[] and weight[].
+ *   value   of (chain row, spec): a single sample of weight 1 gives f_nu at that frequency itself, the bits
+ *           mbb_sed_eval_batch gives; any other list gives sum_i f_nu(freq_i) weight_i, summed in a fixed order
+ *   model   the context's (mbb_set_model); wavenorm the spec's, or the context's when that is 0
+ *   window, statistics, percentiles, clip, status bits: a summary column's (mbb_summary_spec), per (source, spec); a
+ *           chain row the SED constructor fails on gives NaN and its row-status bit when it is inside the window
+ * A spec's results do not depend on the other specs of the call, nor on whether the chain was uploaded or resident:
+ * the same chain gives the same bits.  Columns are made three at a time, whatever nspec is: a call needs the memory of
+ * three columns.  A column may have 2^32 - 1 samples. */
+#define MBB_PRED_MAX_SPECS 128        /* specs per call                                                       */
+#define MBB_PRED_MAX_SAMPLES 32768    /* quadrature samples per call, all specs together                      */
+typedef struct mbb_predict_spec {
+    int32_t nspec;                         /* 1 .. MBB_PRED_MAX_SPECS                                         */
+    int32_t npct;                          /* 1 .. MBB_SUMMARY_MAX_PCT                                        */
+    int32_t burn, thin;                    /* window: steps burn, burn + thin, ...                            */
+    const int32_t *sample_off;             /* [nspec + 1], sample_off[0] = 0, strictly increasing             */
+    const double *freq, *weight;           /* [sample_off[nspec]]: finite and > 0; finite                     */
+    double pct[MBB_SUMMARY_MAX_PCT];       /* numpy's q, 0 .. 100                                             */
+    double wavenorm;                       /* normalisation wavelength [um] of the SED; 0: the context's      */
+    const int32_t *has_lo, *has_hi;        /* [nspec] each, or all four NULL: no clip                         */
+    const double *lo, *hi;                 /* [nspec]: samples with lo <= x <= hi are used                    */
+} mbb_predict_spec;
+/* Where predictions go; every pointer is the caller's, host memory, required. */
+typedef struct mbb_predict_out {
+    int64_t *n_used;                       /* [nsrc][nspec]                                                   */
+    double *mean, *min, *max;              /* [nsrc][nspec]                                                   */
+    double *pct;                           /* [nsrc][nspec][npct]                                             */
+    int32_t *status;                       /* [nsrc][nspec] mbb_summary_status bits (never MBB_SUM_ABSENT)    */
+} mbb_predict_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5]: upload, predict on the device, download the results.
+ * Arguments are checked before anything is allocated, uploaded or launched (MBB_ERR_ARG with a message). */
+int mbb_chain_predict(mbb_ctx *ctx, const double *chain, int nsrc, int nw, int nsteps,
+                      const mbb_predict_spec *spec, const mbb_predict_out *out);
+/* The same of the chain the sampler's last stored or summarised run left on the device.  MBB_ERR_STATE when there is
+ * none, and for a sharded run, as mbb_sampler_diagnostics. */
+int mbb_sampler_predict(mbb_ctx *ctx, void *sampler, const mbb_predict_spec *spec, const mbb_predict_out *out);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

@@ -78,6 +78,22 @@ class MarginalsOut(C.Structure):
                 ("n_used", _lp), ("n_below", _lp), ("n_above", _lp), ("n_nonfinite", _lp), ("status", _ip)]
 
 
+PRED_MAX_SPECS, PRED_MAX_SAMPLES = 128, 32768
+
+
+class PredictSpec(C.Structure):
+    """mbb_predict_spec (include/mbb_hip.h)"""
+    _fields_ = [("nspec", C.c_int32), ("npct", C.c_int32), ("burn", C.c_int32), ("thin", C.c_int32),
+                ("sample_off", _ip), ("freq", _dp), ("weight", _dp),
+                ("pct", C.c_double * SUMMARY_MAX_PCT), ("wavenorm", C.c_double),
+                ("has_lo", _ip), ("has_hi", _ip), ("lo", _dp), ("hi", _dp)]
+
+
+class PredictOut(C.Structure):
+    """mbb_predict_out (include/mbb_hip.h)"""
+    _fields_ = [("n_used", _lp), ("mean", _dp), ("min", _dp), ("max", _dp), ("pct", _dp), ("status", _ip)]
+
+
 # name -> (restype, argtypes); mirrors include/mbb_hip.h one to one
 SIGNATURES = {
     "mbb_last_error": (C.c_char_p, []),
@@ -111,6 +127,8 @@ SIGNATURES = {
     "mbb_chain_marginals": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(MarginalsSpec),
                                       C.POINTER(MarginalsOut)]),
     "mbb_sampler_marginals": (C.c_int, [_vp, _vp, C.POINTER(MarginalsSpec), C.POINTER(MarginalsOut)]),
+    "mbb_chain_predict": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(PredictSpec), C.POINTER(PredictOut)]),
+    "mbb_sampler_predict": (C.c_int, [_vp, _vp, C.POINTER(PredictSpec), C.POINTER(PredictOut)]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

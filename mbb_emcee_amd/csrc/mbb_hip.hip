@@ -33,6 +33,7 @@
 #include "mbb_summary.hip.h"
 #include "mbb_diag.hip.h"
 #include "mbb_marginals.hip.h"
+#include "mbb_predict.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
 #define MBB_FLOW_EXT(OT, NA)                                                    \
@@ -333,7 +334,8 @@ struct mbb_ctx {
         DevBuf mean, seq, outbuf;
         size_t lds_granted = 0;               // dynamic-LDS ceiling already requested for k_diag_acf
     } diag;
-    struct MargWork { DevBuf extent, range, part1, part2, outbuf; } marg;       // ... and the chain marginals (marg_run)
+    struct MargWork { DevBuf extent, range, part1, part2, outbuf; } marg;       // ... the chain marginals (marg_run)
+    struct PredWork { DevBuf samples, part, state, hist, status, outbuf; } pred;   // ... and the predicted fluxes (pred_run)
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -2768,6 +2770,180 @@ extern "C" int mbb_sampler_marginals(mbb_ctx *c, void *sp, const mbb_marginals_s
     int rc;
     if ((rc = analysed_sampler(c, sp, spec && out, "binned", s)) || (rc = resident_chain(s))) return rc;
     return marg_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
+}
+
+// ---- predicted fluxes of a chain (mbb_predict.hip.h) ------------------------
+// Kept steps per walker of a prediction's window, in 64 bits: burn + thin may be beyond an int.
+static long long pred_kept_steps(const mbb_predict_spec *sp, int nsteps)
+{
+    return ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
+}
+
+// The argument checks of a prediction call: before anything is allocated, uploaded or launched.
+static int pred_check(int nsrc, int nw, int nsteps, const mbb_predict_spec *sp, const mbb_predict_out *o)
+{
+    using namespace mbbp;
+    static_assert(kMaxSpecs == MBB_PRED_MAX_SPECS && kMaxSamples == MBB_PRED_MAX_SAMPLES, "prediction sizes");
+    if (!sp || !o || !sp->sample_off || !sp->freq || !sp->weight || !o->n_used || !o->mean || !o->min || !o->max ||
+        !o->pct || !o->status)
+        return fail(MBB_ERR_ARG, "null prediction argument");
+    const bool clip = sp->has_lo || sp->has_hi || sp->lo || sp->hi;
+    if (clip && !(sp->has_lo && sp->has_hi && sp->lo && sp->hi))
+        return fail(MBB_ERR_ARG, "has_lo, has_hi, lo and hi go together: all or none");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    if (sp->nspec < 1 || sp->nspec > kMaxSpecs) return fail(MBB_ERR_ARG, "1 to 128 specs per prediction call");
+    if (sp->sample_off[0] != 0) return fail(MBB_ERR_ARG, "sample_off must start at 0");
+    for (int s = 0; s < sp->nspec; ++s) {
+        if (sp->sample_off[s + 1] <= sp->sample_off[s]) return fail(MBB_ERR_ARG, "a spec has no samples");
+        if (sp->sample_off[s + 1] > kMaxSamples) return fail(MBB_ERR_ARG, "more than 32768 samples in a prediction call");
+    }
+    const int ns = sp->sample_off[sp->nspec];
+    for (int i = 0; i < ns; ++i) {
+        if (!(sp->freq[i] > 0.0 && sp->freq[i] < INFINITY)) return fail(MBB_ERR_ARG, "a frequency must be finite and positive");
+        if (!(sp->weight[i] - sp->weight[i] == 0.0)) return fail(MBB_ERR_ARG, "a weight must be finite");
+    }
+    if (sp->npct < 1 || sp->npct > mbbs::kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per prediction call");
+    for (int k = 0; k < sp->npct; ++k)
+        if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
+    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    if (!(sp->wavenorm >= 0.0 && sp->wavenorm < INFINITY)) return fail(MBB_ERR_ARG, "wavenorm must be positive (0: the context's)");
+    if ((long long)nw * pred_kept_steps(sp, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
+    if ((size_t)nsrc * mbbp::kGroup > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    return MBB_OK;
+}
+
+// Predict from a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
+static int pred_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nsteps, const mbb_predict_spec *sp,
+                    const mbb_predict_out *o)
+{
+    using namespace mbbp;
+    int rc;
+    if ((rc = pred_check(nsrc, nw, nsteps, sp, o))) return rc;
+    const int nspec = sp->nspec, ns = sp->sample_off[nspec];
+    const size_t cells = (size_t)nsrc * nw * nsteps, sn = (size_t)nsrc * nspec, np = (size_t)sp->npct;
+    const double wavenorm = sp->wavenorm > 0.0 ? sp->wavenorm : c->wavenorm;
+    // the window of the chain and a column's splits.  (Not fill_chain_view's rule, which looks at the number of active
+    // columns: a spec's sums must not depend on how many specs share its group.)
+    mbbs::SumArgs a;
+    memset(&a, 0, sizeof a);
+    a.chain = d_chain;
+    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
+    a.nkept = (int)pred_kept_steps(sp, nsteps);          // (at most nsteps)
+    a.n = (long long)nw * a.nkept;
+    a.splits = nsrc >= 256 ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (a.n + 16383) / 16384);
+    a.per_split = (a.n + a.splits - 1) / a.splits;
+    a.npct = sp->npct;
+    for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
+    const int ngmax = std::min(nspec, kGroup);
+    const size_t ncolmax = (size_t)nsrc * ngmax;
+    mbb_ctx::PredWork &w = c->pred;
+    // the result block: 64-bit counts, doubles, 32-bit words
+    const size_t out_bytes = sn * sizeof(long long) + sn * (3 + np) * sizeof(double) + sn * sizeof(int);
+    if ((rc = grow(c, w.samples, (size_t)ns * 3 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.part, ncolmax * a.splits * mbbs::kStatWords * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.state, ncolmax * sizeof(mbbs::ColState)))) return rc;
+    if ((rc = grow(c, w.hist, ncolmax * a.splits * mbbs::kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    if ((rc = grow(c, w.status, sn * sizeof(int)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = grow(c, c->der.der, (size_t)ngmax * cells * sizeof(double)))) return rc;
+    const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
+    if ((rc = ensure_sed(c, chunk, 0))) return rc;
+    a.part = (double *)w.part.p; a.state = (mbbs::ColState *)w.state.p; a.hist = (unsigned int *)w.hist.p;
+    FinishArgs f;
+    f.nspec = nspec;
+    f.pstatus = (const int *)w.status.p;
+    Carve ob{(char *)w.outbuf.p};
+    f.o_nused = ob.take<long long>(sn);
+    f.o_mean = ob.take<double>(sn); f.o_min = ob.take<double>(sn); f.o_max = ob.take<double>(sn);
+    f.o_pct = ob.take<double>(sn * np);
+    f.o_status = ob.take<int>(sn);
+    double *const d_nu = (double *)w.samples.p, *const d_ln = d_nu + ns, *const d_wt = d_ln + ns;
+    // (the caller's arrays are pageable: the copies below have read them when they return)
+    HIPCHK(hipMemcpyAsync(d_nu, sp->freq, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_wt, sp->weight, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_pred_lnnu, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream, (const double *)d_nu, ns, d_ln);
+    HIPCHK(hipMemsetAsync(w.status.p, 0, sn * sizeof(int), c->stream));
+    for (int spec0 = 0; spec0 < nspec; spec0 += kGroup) {
+        const int ng = std::min(kGroup, nspec - spec0);
+        FillArgs fa;
+        memset(&fa, 0, sizeof fa);
+        fa.wk = c->sed.wk.d(); fa.status = c->sed.status.d();
+        fa.nu = d_nu; fa.lnnu = d_ln; fa.wt = d_wt;
+        fa.ng = ng; fa.pstatus = (int *)w.status.p; fa.nspec = nspec; fa.spec0 = spec0;
+        fa.nw = nw; fa.nsteps = nsteps; fa.burn = sp->burn; fa.thin = sp->thin;
+        int staged = 0;
+        a.ncol = ng;
+        for (int g = 0; g < ng; ++g) {
+            const int s = spec0 + g;
+            fa.s0[g] = sp->sample_off[s]; fa.s1[g] = sp->sample_off[s + 1];
+            fa.single[g] = fa.s1[g] - fa.s0[g] == 1 && sp->weight[fa.s0[g]] == 1.0;
+            fa.l0[g] = staged;
+            if (!fa.single[g]) staged += fa.s1[g] - fa.s0[g];
+            fa.col[g] = (double *)c->der.der.p + (size_t)g * cells;
+            a.der[g] = fa.col[g];
+            a.col[g] = 5 + g;
+            a.has_lo[5 + g] = sp->has_lo ? sp->has_lo[s] != 0 : 0; a.has_hi[5 + g] = sp->has_hi ? sp->has_hi[s] != 0 : 0;
+            a.lo[5 + g] = sp->lo ? sp->lo[s] : 0.0; a.hi[5 + g] = sp->hi ? sp->hi[s] : 0.0;
+        }
+        const bool stage = staged > 0 && staged <= kLdsSamples;
+        fa.nstaged = stage ? staged : 0;
+        const size_t lds = (size_t)fa.nstaged * 3 * sizeof(double);
+        for (size_t off = 0; off < cells; off += chunk) {
+            const int n = (int)std::min(chunk, cells - off);
+            if ((rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, wavenorm, 0, nullptr))) return rc;
+            fa.n = n; fa.off = (long long)off;
+            const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
+            dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
+                if (stage)
+                    hipLaunchKernelGGL((k_pred_fill<decltype(OT)::value, decltype(NA)::value, true>), grid, dim3(kThreads), lds,
+                                       c->stream, fa);
+                else
+                    hipLaunchKernelGGL((k_pred_fill<decltype(OT)::value, decltype(NA)::value, false>), grid, dim3(kThreads), 0,
+                                       c->stream, fa);
+            });
+            HIPCHK(hipGetLastError());
+        }
+        const size_t ncolumns = (size_t)nsrc * ng;
+        const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
+        hipLaunchKernelGGL(mbbs::k_sum_stats, gcol, dim3(mbbs::kThreads), 0, c->stream, a);
+        hipLaunchKernelGGL(mbbs::k_sum_begin, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a);
+        for (int pass = 0; pass < 8; ++pass) {
+            hipLaunchKernelGGL(mbbs::k_sum_hist, gcol, dim3(mbbs::kThreads), 0, c->stream, a, pass);
+            hipLaunchKernelGGL(mbbs::k_sum_pick, dim3((unsigned)ncolumns), dim3(mbbs::kThreads), 0, c->stream, a);
+        }
+        f.spec0 = spec0;
+        hipLaunchKernelGGL(k_pred_finish, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a, f);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<char> host(out_bytes);
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Carve hb{host.data()};
+    hb.put(o->n_used, sn);
+    hb.put(o->mean, sn); hb.put(o->min, sn); hb.put(o->max, sn);
+    hb.put(o->pct, sn * np);
+    hb.put(o->status, sn);
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_predict(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
+                                 const mbb_predict_spec *spec, const mbb_predict_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = pred_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
+    return with_uploaded_chain(c, chain, nullptr, (size_t)nsrc * nw * nsteps, [&](const double *d) {
+        return pred_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
+}
+
+extern "C" int mbb_sampler_predict(mbb_ctx *c, void *sp, const mbb_predict_spec *spec, const mbb_predict_out *out)
+{
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, spec && out, "predicted from", s)) || (rc = resident_chain(s))) return rc;
+    return pred_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

@@ -98,7 +98,7 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary``, ``convergence_`` or ``marginals_``, nothing resident for ``convergence()`` or
+        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_`` or ``predictions_``, nothing resident for ``convergence()`` or
         ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
@@ -118,6 +118,7 @@ class DeviceEnsembleSampler(object):
         self.summary = None
         self.convergence_ = None
         self.marginals_ = None
+        self._drop_predictions()
         self._resident = 0                    # steps of the last run's chain that are resident on the device
         if self._h is not None:
             _native._check(self._ctx.lib.mbb_sampler_reset(self._ctx.h, self._h))
@@ -190,8 +191,49 @@ class DeviceEnsembleSampler(object):
         _native.check_arg(ctx.lib.mbb_sampler_marginals(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return marginals.ChainMarginals(req, raw, self.nsources > 1, self.k, nkept)
 
+    def predictions(self, specs, percentile=68.3, percentiles=(), burn=0, thin=1, clip=None, wavenorm=None, keep=True):
+        """``predict.ChainPredictions`` (predicted fluxes at wavelengths and through passbands, ``predflux_cen``) of the
+        chain the last run left on the device -- a run with storechain=True or with summary= --; the arguments are
+        ``predict.chain_predictions``'s.  No chain crosses the bus."""
+        from . import predict
+        cens, qs = predict._quantiles(percentile, percentiles)
+        req = predict._Request(self.lnprobfn, specs, qs, burn, thin, clip, wavenorm)
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: predictions() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset")
+        nkept = req.check_steps(self._resident)
+        res = predict.ChainPredictions(req, self._predict_again(req), self.nsources > 1,
+                                       self._predict_again if keep else None, cens[0], self.k, nkept)
+        if keep:
+            # every result that can go back to the resident chain is known to the sampler, which tells it when that
+            # chain goes (_drop_predictions); a result nobody holds any more is forgotten by itself
+            import weakref
+            if getattr(self, "_handed_predictions", None) is None:
+                self._handed_predictions = weakref.WeakSet()
+            self._handed_predictions.add(res)
+        return res
+
+    def _drop_predictions(self):
+        """The resident chain is about to go (the start of a run, reset()): ``predictions_`` is None again, and every
+        result ``predictions()`` handed out -- that one included -- forgets how to compute more from the chain, so
+        that what it was not made with is a RuntimeError afterwards and never a number from another chain."""
+        for res in list(getattr(self, "_handed_predictions", None) or ()) + [getattr(self, "predictions_", None)]:
+            if res is not None:
+                res.drop_chain()
+        self._handed_predictions = None
+        self.predictions_ = None
+
+    def _predict_again(self, req):
+        """A prediction from the chain the last run left on the device (mbb_sampler_predict)."""
+        from . import predict
+        ctx, h = self._handle()
+        raw = predict._Raw(self.nsources, len(req.keys), len(req.qs))
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(ctx.lib.mbb_sampler_predict(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return raw
+
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
-                 marginals=None, **unused):
+                 marginals=None, predict=None, **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -224,9 +266,15 @@ class DeviceEnsembleSampler(object):
         marginals=True, or a dict of ``marginals()``'s keywords: the chain of this run is binned on the device and
         ``sampler.marginals_`` is the ``marginals.ChainMarginals`` of it (None again after reset() and at the start of
         the next run).  With storechain=False it needs summary= too; burn, thin, derived and the derived columns'
-        settings default to those given with summary=."""
+        settings default to those given with summary=.
+
+        predict=specs, or a dict of ``predictions()``'s arguments (``specs`` among them): the fluxes the chain of this
+        run predicts at those wavelengths and through those passbands are summarised on the device and
+        ``sampler.predictions_`` is the ``predict.ChainPredictions`` of them (None again after reset() and at the
+        start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
+        with summary=."""
         self._retire()
-        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals)
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
@@ -245,10 +293,30 @@ class DeviceEnsembleSampler(object):
         if not st.single:
             self._resident = 0                # (what is resident is the last chunk: a part)
 
-    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None):
-        creq = mkw = None
+    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None, predict=None):
+        creq = mkw = pkw = None
         self.convergence_ = None
         self.marginals_ = None
+        self._drop_predictions()                    # (the chain they could go back to is about to be overwritten)
+        if predict is not None and predict is not False:
+            from . import predict as _predict
+            pkw = dict(predict) if isinstance(predict, dict) else dict(specs=predict)
+            if "specs" not in pkw:
+                raise ValueError("predict= needs specs: wavelengths in um and / or passband names")
+            if summary is not None and summary is not False and summary is not True:
+                for key in ("burn", "thin"):
+                    if key in summary:
+                        pkw.setdefault(key, summary[key])
+            unknown = set(pkw) - {"specs", "percentile", "percentiles", "burn", "thin", "clip", "wavenorm", "keep"}
+            if unknown:
+                raise TypeError("predict= got unexpected keyword(s) {}".format(sorted(unknown)))
+            preq = _predict._Request(self.lnprobfn, pkw["specs"],
+                                     _predict._quantiles(pkw.get("percentile", 68.3), pkw.get("percentiles", ()))[1],
+                                     pkw.get("burn", 0), pkw.get("thin", 1), pkw.get("clip"), pkw.get("wavenorm"))
+            if not storechain and (summary is None or summary is False):
+                raise ValueError("predict= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device")
+            preq.check_steps(int(N))
         if marginals is not None and marginals is not False:
             from . import marginals as _marginals
             mkw = {} if marginals is True else dict(marginals)
@@ -275,6 +343,9 @@ class DeviceEnsembleSampler(object):
                              "walkers' chain")
         if mkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be binned on the device: a rank holds only its own "
+                             "walkers' chain")
+        if pkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be predicted from on the device: a rank holds only its own "
                              "walkers' chain")
         req = None
         if summary is not None and summary is not False:
@@ -370,6 +441,8 @@ class DeviceEnsembleSampler(object):
             self.convergence_ = self.convergence(creq.burn, creq.c, creq.tol, creq.method, creq.nacf)
         if mkw is not None:
             self.marginals_ = self.marginals(**mkw)
+        if pkw is not None:
+            self.predictions_ = self.predictions(**pkw)
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):
@@ -423,7 +496,7 @@ class DeviceEnsembleSampler(object):
         run_mcmc refuses -- a wrong shape, NaN or inf in ``p0``, ``p0`` None without a state -- sample() refuses at
         the first ``next()``; ``iterations=0`` sets the state as ``run_mcmc(p0, 0)`` does and yields nothing.
 
-        Afterwards ``summary``, ``convergence_`` and ``marginals_`` are None.  ``convergence()`` describes all the steps this call
+        Afterwards ``summary``, ``convergence_``, ``marginals_`` and ``predictions_`` are None.  ``convergence()`` describes all the steps this call
         made where the whole run was one chunk (``iterations`` <= ``chunk``), which is then resident on the device;
         otherwise it raises its "no chain of this sampler is resident" ValueError: it never describes a part."""
         self._retire()

@@ -137,7 +137,7 @@ class mbb_fitter(object):
                                                                 lo[worst], hi[worst]))
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
-    def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None):
+    def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
@@ -145,7 +145,12 @@ class mbb_fitter(object):
         convergence (device sampler only): True or a dict of ``diagnostics.chain_diagnostics``'s keywords -- the main
         chain's autocorrelation times, effective sample sizes and split R-hat, ``mbb_fitter.convergence``.
         marginals (device sampler only): True or a dict of ``marginals.chain_marginals``'s keywords -- the main chain's
-        1-d and 2-d histograms, ``mbb_fitter.marginals``."""
+        1-d and 2-d histograms, ``mbb_fitter.marginals``.
+        predict (device sampler only): wavelengths in um and / or passband names, or a dict of
+        ``predict.chain_predictions``'s keywords (``specs`` among them) -- the fluxes the main chain predicts there,
+        ``mbb_fitter.predictions``."""
+        if predict is not None and predict is not False and not hasattr(self.sampler, "predictions"):
+            raise ValueError("predict= needs sampler=\"device\"")
         if marginals is not None and marginals is not False and not hasattr(self.sampler, "marginals"):
             raise ValueError("marginals= needs sampler=\"device\"")
         if convergence is not None and convergence is not False and not hasattr(self.sampler, "convergence"):
@@ -190,6 +195,8 @@ class mbb_fitter(object):
             extra["convergence"] = convergence
         if marginals is not None and marginals is not False:
             extra["marginals"] = marginals
+        if predict is not None and predict is not False:
+            extra["predict"] = predict
         self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, **extra)
         self._sampled = True
 
@@ -231,6 +238,8 @@ mbb_fitter.convergence = property(lambda self: getattr(self.sampler, "convergenc
                                       "else None")
 mbb_fitter.marginals = property(lambda self: getattr(self.sampler, "marginals_", None),
                                 doc="marginals.ChainMarginals of the main chain when run() was given marginals=, else None")
+mbb_fitter.predictions = property(lambda self: getattr(self.sampler, "predictions_", None),
+                                  doc="predict.ChainPredictions of the main chain when run() was given predict=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,
                                          doc="Is passband integration in use?")
 

@@ -50,6 +50,10 @@ def build_parser():
                         "the peak wavelength too; needs --sampler device): printed, and added to the .npz as marginals_*")
     p.add_argument("--marginals2d", type=int, default=0, metavar="NBINS2",
                    help="with --marginals: also the 2-d histograms of all pairs of columns, NBINS2 bins per axis")
+    p.add_argument("--predict", default=None, metavar="SPEC[,SPEC...]",
+                   help="predict fluxes from the chain on the device: each SPEC a wavelength in um or, with --response, "
+                        "the name of a passband of the wheel (needs --sampler device): mean and 68.3%% interval printed, "
+                        "and added to the .npz as predict_*")
     p.add_argument("-v", "--verbose", action="store_true")
     for nm, dflt in zip(NAMES, (10.0, 2.0, 2500.0, 4.0, 40.0)):
         p.add_argument("--init" + nm, type=float, default=dflt)
@@ -60,6 +64,19 @@ def build_parser():
     p.add_argument("--upLambdaPeak", type=float, default=None)
     p.add_argument("--priorLambdaPeak", type=float, nargs=2, default=None)
     return p
+
+
+def parse_predict(text):
+    """--predict's list: what reads as a number is a wavelength in um, anything else a passband name."""
+    specs = []
+    for tok in (t.strip() for t in text.split(",")):
+        if not tok:
+            raise ValueError("--predict: empty spec in {!r}".format(text))
+        try:
+            specs.append(float(tok))
+        except ValueError:
+            specs.append(tok)
+    return specs
 
 
 def main(argv=None):
@@ -99,6 +116,8 @@ def main(argv=None):
     if a.marginals:
         extra["marginals"] = dict(bins=a.marginals, bins2d=a.marginals2d, pairs="all",
                                   derived=("peaklambda",) if a.get_peaklambda else ())
+    if a.predict:
+        extra["predict"] = parse_predict(a.predict)
     fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary, **extra)
     chain, lnp = fit.sampler.chain, fit.sampler.lnprobability
     out = dict(chain=chain, lnprobability=lnp, acceptance_fraction=fit.sampler.acceptance_fraction,
@@ -116,6 +135,9 @@ def main(argv=None):
     if a.marginals:
         out.update(fit.marginals.arrays())
         print(fit.marginals)
+    if a.predict:
+        out.update(fit.predictions.arrays())
+        print(fit.predictions)
     np.savez_compressed(a.outfile, **out)
     if a.verbose:
         flat = chain.reshape(-1, 5)
