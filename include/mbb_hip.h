@@ -389,6 +389,51 @@ int mbb_chain_predict(mbb_ctx *ctx, const double *chain, int nsrc, int nw, int n
  * none, and for a sharded run, as mbb_sampler_diagnostics. */
 int mbb_sampler_predict(mbb_ctx *ctx, void *sampler, const mbb_predict_spec *spec, const mbb_predict_out *out);
 
+/* ---- posterior draws of a chain, taken where the chain is ---- */
+/* Replaces: mbb_results.choice() (results.py:803-893): nsamples cells of the chain, uniform over walkers x steps with
+ * replacement, with their peak wavelength, L_IR and dust mass.  Per source n cells of the window (steps burn, burn +
+ * thin, ... of every walker: N = nw * nkept cells, cell j = walker j / nkept, step burn + (j % nkept) thin) are picked
+ * and their rows, lnprob and (walker, step) gathered on the device; the derived columns are computed for the drawn
+ * rows alone, by the kernels and with the settings of a summary, so a drawn row's derived values and status bits are
+ * those a summary of that one cell reports.  Draw i of source s picks
+ *   MBB_DRAWS_RANDOM  j = (u N) >> 64, u = out[0] | out[1] << 32 of Philox4x32-10 with counter (i, s, 0x44524157, 1)
+ *                     and key (seed low, seed high): the reference's semantics; apart from every stretch-move draw of
+ *                     the same seed (counters (row, half, 0, 0))
+ *   MBB_DRAWS_EVEN    j = floor(i N / n): deterministic, spread over the window, no repeats while n <= N
+ * Rows and lnprob are copies of the chain's, bit for bit.  The same chain, spec and seed give the same draws, resident
+ * or uploaded. */
+#define MBB_DRAWS_MAX (1 << 24)       /* draws per source and call; nsrc * n may be 2^31 - 1 at most              */
+enum mbb_draws_how { MBB_DRAWS_RANDOM = 0, MBB_DRAWS_EVEN = 1 };
+typedef struct mbb_draws_spec {
+    int32_t n;                             /* draws per source, 1 .. MBB_DRAWS_MAX                            */
+    int32_t how;                           /* mbb_draws_how                                                   */
+    uint64_t seed;
+    /* burn, thin, derived, peak_model, redshift / lumdist_mpc (scalar or per source), kappa, kappa_wave and the L_IR
+     * range are taken from here; its percentiles and clips are ignored.  Required. */
+    const mbb_summary_spec *summary;
+} mbb_draws_spec;
+/* Where draws go; every pointer is the caller's, host memory, required (derived[k] only where bit k of the summary
+ * spec's derived is set; others are not written and may be NULL). */
+typedef struct mbb_draws_out {
+    double *rows;                          /* [nsrc][n][5]                                                    */
+    double *lnprob;                        /* [nsrc][n]; NaN when no lnprob was given                         */
+    int32_t *index;                        /* [nsrc][n][2]: walker, step                                      */
+    double *derived[3];                    /* [nsrc][n] each: peak wavelength, L_IR, dust mass                */
+    int32_t *status;                       /* [nsrc][8]: from MBB_SUM_ROW_SHIFT on the row status of drawn rows the
+                                              SED kernels failed on, per derived column, as a summary reports them;
+                                              MBB_SUM_ABSENT for a derived column not asked for                */
+} mbb_draws_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5], lnprob [nsrc][nw][nsteps] or NULL: upload, draw on the
+ * device, download the draws.  Arguments are checked before anything is allocated, uploaded or launched. */
+int mbb_chain_draws(mbb_ctx *ctx, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                    const mbb_draws_spec *spec, const mbb_draws_out *out);
+/* The same of the chain (and its lnprob) the sampler's last stored or summarised run left on the device.
+ * MBB_ERR_STATE when there is none, and for a sharded run, as mbb_sampler_diagnostics. */
+int mbb_sampler_draws(mbb_ctx *ctx, void *sampler, const mbb_draws_spec *spec, const mbb_draws_out *out);
+/* The picks alone, index [nsrc][n][2] (walker, step), with no chain: for a chain the caller holds on the host. */
+int mbb_draw_indices(mbb_ctx *ctx, int nsrc, int nw, int nsteps, int burn, int thin, int n, int how,
+                     unsigned long long seed, int32_t *index);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

@@ -94,6 +94,20 @@ class PredictOut(C.Structure):
     _fields_ = [("n_used", _lp), ("mean", _dp), ("min", _dp), ("max", _dp), ("pct", _dp), ("status", _ip)]
 
 
+DRAWS_MAX = 1 << 24
+DRAWS_RANDOM, DRAWS_EVEN = 0, 1
+
+
+class DrawsSpec(C.Structure):
+    """mbb_draws_spec (include/mbb_hip.h)"""
+    _fields_ = [("n", C.c_int32), ("how", C.c_int32), ("seed", C.c_uint64), ("summary", C.POINTER(SummarySpec))]
+
+
+class DrawsOut(C.Structure):
+    """mbb_draws_out (include/mbb_hip.h)"""
+    _fields_ = [("rows", _dp), ("lnprob", _dp), ("index", _ip), ("derived", _dp * 3), ("status", _ip)]
+
+
 # name -> (restype, argtypes); mirrors include/mbb_hip.h one to one
 SIGNATURES = {
     "mbb_last_error": (C.c_char_p, []),
@@ -129,6 +143,10 @@ SIGNATURES = {
     "mbb_sampler_marginals": (C.c_int, [_vp, _vp, C.POINTER(MarginalsSpec), C.POINTER(MarginalsOut)]),
     "mbb_chain_predict": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(PredictSpec), C.POINTER(PredictOut)]),
     "mbb_sampler_predict": (C.c_int, [_vp, _vp, C.POINTER(PredictSpec), C.POINTER(PredictOut)]),
+    "mbb_chain_draws": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(DrawsSpec), C.POINTER(DrawsOut)]),
+    "mbb_sampler_draws": (C.c_int, [_vp, _vp, C.POINTER(DrawsSpec), C.POINTER(DrawsOut)]),
+    "mbb_draw_indices": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
+                                   _ip]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

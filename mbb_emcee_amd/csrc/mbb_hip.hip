@@ -34,6 +34,7 @@
 #include "mbb_diag.hip.h"
 #include "mbb_marginals.hip.h"
 #include "mbb_predict.hip.h"
+#include "mbb_draws.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
 #define MBB_FLOW_EXT(OT, NA)                                                    \
@@ -335,7 +336,8 @@ struct mbb_ctx {
         size_t lds_granted = 0;               // dynamic-LDS ceiling already requested for k_diag_acf
     } diag;
     struct MargWork { DevBuf extent, range, part1, part2, outbuf; } marg;       // ... the chain marginals (marg_run)
-    struct PredWork { DevBuf samples, part, state, hist, status, outbuf; } pred;   // ... and the predicted fluxes (pred_run)
+    struct PredWork { DevBuf samples, part, state, hist, status, outbuf; } pred;   // ... the predicted fluxes (pred_run)
+    struct DrawWork { DevBuf rows, aux; } draw;     // ... and the posterior draws (draws_run): the compact block, its lnprob and index
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -2239,7 +2241,11 @@ static int check_window(const mbb_summary_spec *sp, int nsteps)
     return MBB_OK;
 }
 
-static int kept_steps(const mbb_summary_spec *sp, int nsteps) { return (nsteps - sp->burn + sp->thin - 1) / sp->thin; }
+// (in 64 bits: nsteps + thin may be beyond an int)
+static int kept_steps(const mbb_summary_spec *sp, int nsteps)
+{
+    return (int)(((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin);
+}
 
 static int check_sample_cap(const mbb_summary_spec *sp, int nw, int nsteps)
 {
@@ -2944,6 +2950,131 @@ extern "C" int mbb_sampler_predict(mbb_ctx *c, void *sp, const mbb_predict_spec 
     int rc;
     if ((rc = analysed_sampler(c, sp, spec && out, "predicted from", s)) || (rc = resident_chain(s))) return rc;
     return pred_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
+}
+
+// ---- posterior draws of a chain (mbb_draws.hip.h) ------------------------
+// The checks of the picks themselves: sizes, how, and the window (ss: burn and thin are looked at).
+static int draws_check_picks(int nsrc, int nw, int nsteps, const mbb_summary_spec *ss, int n, int how)
+{
+    static_assert(mbbw::kMaxDraws == MBB_DRAWS_MAX && mbbw::kRandom == MBB_DRAWS_RANDOM && mbbw::kEven == MBB_DRAWS_EVEN,
+                  "draws constants");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    if (n < 1) return fail(MBB_ERR_ARG, "at least one draw per source");
+    if (n > mbbw::kMaxDraws) return fail(MBB_ERR_ARG, "more than 2^24 draws per source");
+    if ((long long)nsrc * n > 0x7fffffffll) return fail(MBB_ERR_ARG, "more than 2^31 - 1 draws per call");
+    if (how != mbbw::kRandom && how != mbbw::kEven) return fail(MBB_ERR_ARG, "unknown how (0 random, 1 even)");
+    int rc;
+    if ((rc = check_window(ss, nsteps)) || (rc = check_sample_cap(ss, nw, nsteps))) return rc;
+    return MBB_OK;
+}
+
+// The argument checks of a draws call: before anything is allocated, uploaded or launched.
+static int draws_check(int nsrc, int nw, int nsteps, const mbb_draws_spec *sp, const mbb_draws_out *o)
+{
+    if (!sp || !o || !sp->summary || !o->rows || !o->lnprob || !o->index || !o->status)
+        return fail(MBB_ERR_ARG, "null draws argument");
+    int rc;
+    if ((rc = draws_check_picks(nsrc, nw, nsteps, sp->summary, sp->n, sp->how))) return rc;
+    for (int k = 0; k < 3; ++k)
+        if (((sp->summary->derived >> k) & 1) && !o->derived[k]) return fail(MBB_ERR_ARG, "null draws argument");
+    return check_derived_settings(sp->summary, nsrc);
+}
+
+// The picks of a checked call as kernel arguments (the chain may be null: k_draw_index reads none).
+static void fill_draw_args(mbbw::DrawArgs &a, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
+                           const mbb_summary_spec *ss, int n, int how, unsigned long long seed)
+{
+    memset(&a, 0, sizeof a);
+    fill_chain_view(a, d_chain, nsrc, nw, nsteps, ss, 16384);       // (the splits are not used)
+    a.lnprob = d_lnprob;
+    a.ndraw = n; a.how = how; a.seed = seed;
+}
+
+// Draw from a chain that is on the device in emcee's layout (d_lnprob may be null).  Synchronous; the results land in
+// the caller's arrays.
+static int draws_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
+                     const mbb_draws_spec *sp, const mbb_draws_out *o)
+{
+    using namespace mbbw;
+    using mbbc::kCols;
+    int rc;
+    if ((rc = draws_check(nsrc, nw, nsteps, sp, o))) return rc;
+    DrawArgs a;
+    fill_draw_args(a, d_chain, d_lnprob, nsrc, nw, nsteps, sp->summary, sp->n, sp->how, sp->seed);
+    const size_t nd = (size_t)nsrc * sp->n;
+    mbb_ctx::DrawWork &w = c->draw;
+    if ((rc = grow(c, w.rows, nd * 5 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.aux, nd * (sizeof(double) + 2 * sizeof(int))))) return rc;
+    a.o_rows = (double *)w.rows.p;
+    a.o_lnprob = (double *)w.aux.p;
+    a.o_index = (int *)(a.o_lnprob + nd);
+    hipLaunchKernelGGL(k_draw_gather, dim3((unsigned)((nd + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    // the derived columns of the drawn rows alone: the compact block is a chain of nsrc x 1 x n, all of it the window
+    mbb_summary_spec block = *sp->summary;
+    block.burn = 0;
+    block.thin = 1;
+    mbbc::ChainView b;
+    memset(&b, 0, sizeof b);
+    fill_chain_view(b, a.o_rows, nsrc, 1, sp->n, &block, 16384);
+    if ((rc = summary_fill_derived(c, &block, b))) return rc;
+    HIPCHK(hipMemcpyAsync(o->rows, a.o_rows, nd * 5 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->lnprob, a.o_lnprob, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->index, a.o_index, nd * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < 3; ++k)
+        if (b.der[k]) HIPCHK(hipMemcpyAsync(o->derived[k], b.der[k], nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->status, c->der.colstatus.p, (size_t)nsrc * kCols * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = derived_sync(c))) return rc;
+    for (int s = 0; s < nsrc; ++s)
+        for (int k = 0; k < 3; ++k)
+            if (!b.der[k]) o->status[(size_t)s * kCols + 5 + k] |= mbbs::kStAbsent;
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_draws(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                               const mbb_draws_spec *spec, const mbb_draws_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = draws_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
+        return draws_run(c, d, lnprob ? d + cells * 5 : nullptr, nsrc, nw, nsteps, spec, out);
+    });
+}
+
+extern "C" int mbb_sampler_draws(mbb_ctx *c, void *sp, const mbb_draws_spec *spec, const mbb_draws_out *out)
+{
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, spec && out, "drawn from", s)) || (rc = resident_chain(s))) return rc;
+    const size_t cells = (size_t)s->rows() * s->resident_nsteps;
+    return draws_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+}
+
+extern "C" int mbb_draw_indices(mbb_ctx *c, int nsrc, int nw, int nsteps, int burn, int thin, int n, int how,
+                                unsigned long long seed, int32_t *index)
+{
+    using namespace mbbw;
+    int rc = use(c);
+    if (rc) return rc;
+    if (!index) return fail(MBB_ERR_ARG, "null draws argument");
+    mbb_summary_spec ss;
+    memset(&ss, 0, sizeof ss);
+    ss.burn = burn;
+    ss.thin = thin;
+    if ((rc = draws_check_picks(nsrc, nw, nsteps, &ss, n, how))) return rc;
+    DrawArgs a;
+    fill_draw_args(a, nullptr, nullptr, nsrc, nw, nsteps, &ss, n, how, seed);
+    const size_t nd = (size_t)nsrc * n;
+    if ((rc = grow(c, c->draw.aux, nd * 2 * sizeof(int)))) return rc;
+    a.o_index = (int *)c->draw.aux.p;
+    hipLaunchKernelGGL(k_draw_index, dim3((unsigned)((nd + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(index, a.o_index, nd * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MBB_OK;
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

@@ -98,7 +98,7 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_`` or ``predictions_``, nothing resident for ``convergence()`` or
+        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_`` or ``predictions_``, nothing resident for ``convergence()`` or
         ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
@@ -118,6 +118,7 @@ class DeviceEnsembleSampler(object):
         self.summary = None
         self.convergence_ = None
         self.marginals_ = None
+        self.draws_ = None
         self._drop_predictions()
         self._resident = 0                    # steps of the last run's chain that are resident on the device
         if self._h is not None:
@@ -191,6 +192,24 @@ class DeviceEnsembleSampler(object):
         _native.check_arg(ctx.lib.mbb_sampler_marginals(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return marginals.ChainMarginals(req, raw, self.nsources > 1, self.k, nkept)
 
+    def draws(self, n=1, **kw):
+        """``draws.ChainDraws`` (``n`` cells per source with their parameters, lnprob, (walker, step) and the derived
+        values asked for) from the chain the last run left on the device -- a run with storechain=True or with
+        summary= --; the keywords are ``draws.chain_draws``'s, ``seed`` defaulting to the sampler's.  A few rows
+        cross the bus, no chain."""
+        from . import draws
+        kw.setdefault("seed", self.seed)
+        req = draws._Request(n, nsources=self.nsources, **kw)
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: draws() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset")
+        nkept = req.check_steps(self._resident)
+        ctx, h = self._handle()
+        raw = draws._Raw(self.nsources, req.n, req.derived)
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(ctx.lib.mbb_sampler_draws(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return draws.ChainDraws(self.lnprobfn, req, raw, self.nsources > 1, self.k, nkept)
+
     def predictions(self, specs, percentile=68.3, percentiles=(), burn=0, thin=1, clip=None, wavenorm=None, keep=True):
         """``predict.ChainPredictions`` (predicted fluxes at wavelengths and through passbands, ``predflux_cen``) of the
         chain the last run left on the device -- a run with storechain=True or with summary= --; the arguments are
@@ -233,7 +252,7 @@ class DeviceEnsembleSampler(object):
         return raw
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
-                 marginals=None, predict=None, **unused):
+                 marginals=None, predict=None, draws=None, **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -272,9 +291,14 @@ class DeviceEnsembleSampler(object):
         run predicts at those wavelengths and through those passbands are summarised on the device and
         ``sampler.predictions_`` is the ``predict.ChainPredictions`` of them (None again after reset() and at the
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
-        with summary=."""
+        with summary=.
+
+        draws=n, or a dict of ``draws()``'s keywords (``n`` among them): that many cells per source are drawn from the
+        chain of this run on the device and ``sampler.draws_`` is the ``draws.ChainDraws`` of them (None again after
+        reset() and at the start of the next run).  With storechain=False it needs summary= too; burn, thin, derived
+        and the derived columns' settings default to those given with summary=."""
         self._retire()
-        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict)
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
@@ -293,10 +317,12 @@ class DeviceEnsembleSampler(object):
         if not st.single:
             self._resident = 0                # (what is resident is the last chunk: a part)
 
-    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None, predict=None):
-        creq = mkw = pkw = None
+    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None, predict=None,
+             draws=None):
+        creq = mkw = pkw = dkw = None
         self.convergence_ = None
         self.marginals_ = None
+        self.draws_ = None
         self._drop_predictions()                    # (the chain they could go back to is about to be overwritten)
         if predict is not None and predict is not False:
             from . import predict as _predict
@@ -329,6 +355,19 @@ class DeviceEnsembleSampler(object):
                 raise ValueError("marginals= with storechain=False needs summary= too: a run that neither stores "
                                  "nor summarises its chain keeps none on the device")
             mreq.check_steps(int(N))
+        if draws is not None and draws is not False:
+            from . import draws as _draws
+            dkw = dict(draws) if isinstance(draws, dict) else dict(n=draws)
+            if summary is not None and summary is not False and summary is not True:
+                for key in _draws._SUMMARY_KEYS:
+                    if key in summary:
+                        dkw.setdefault(key, summary[key])
+            dkw.setdefault("seed", self.seed)
+            dreq = _draws._Request(nsources=self.nsources, **dkw)
+            if not storechain and (summary is None or summary is False):
+                raise ValueError("draws= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device")
+            dreq.check_steps(int(N))
         if convergence is not None and convergence is not False:
             from . import diagnostics
             ckw = {} if convergence is True else dict(convergence)
@@ -346,6 +385,9 @@ class DeviceEnsembleSampler(object):
                              "walkers' chain")
         if pkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be predicted from on the device: a rank holds only its own "
+                             "walkers' chain")
+        if dkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be drawn from on the device: a rank holds only its own "
                              "walkers' chain")
         req = None
         if summary is not None and summary is not False:
@@ -443,6 +485,8 @@ class DeviceEnsembleSampler(object):
             self.marginals_ = self.marginals(**mkw)
         if pkw is not None:
             self.predictions_ = self.predictions(**pkw)
+        if dkw is not None:
+            self.draws_ = self.draws(**dkw)
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):

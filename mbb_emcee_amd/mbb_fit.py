@@ -137,7 +137,8 @@ class mbb_fitter(object):
                                                                 lo[worst], hi[worst]))
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
-    def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None):
+    def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None,
+            draws=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
@@ -148,7 +149,11 @@ class mbb_fitter(object):
         1-d and 2-d histograms, ``mbb_fitter.marginals``.
         predict (device sampler only): wavelengths in um and / or passband names, or a dict of
         ``predict.chain_predictions``'s keywords (``specs`` among them) -- the fluxes the main chain predicts there,
-        ``mbb_fitter.predictions``."""
+        ``mbb_fitter.predictions``.
+        draws (device sampler only): a number of draws per source, or a dict of ``draws.chain_draws``'s keywords (``n``
+        among them) -- cells drawn from the main chain with their derived values, ``mbb_fitter.draws``."""
+        if draws is not None and draws is not False and not hasattr(self.sampler, "draws"):
+            raise ValueError("draws= needs sampler=\"device\"")
         if predict is not None and predict is not False and not hasattr(self.sampler, "predictions"):
             raise ValueError("predict= needs sampler=\"device\"")
         if marginals is not None and marginals is not False and not hasattr(self.sampler, "marginals"):
@@ -197,6 +202,8 @@ class mbb_fitter(object):
             extra["marginals"] = marginals
         if predict is not None and predict is not False:
             extra["predict"] = predict
+        if draws is not None and draws is not False:
+            extra["draws"] = draws
         self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, **extra)
         self._sampled = True
 
@@ -240,6 +247,8 @@ mbb_fitter.marginals = property(lambda self: getattr(self.sampler, "marginals_",
                                 doc="marginals.ChainMarginals of the main chain when run() was given marginals=, else None")
 mbb_fitter.predictions = property(lambda self: getattr(self.sampler, "predictions_", None),
                                   doc="predict.ChainPredictions of the main chain when run() was given predict=, else None")
+mbb_fitter.draws = property(lambda self: getattr(self.sampler, "draws_", None),
+                            doc="draws.ChainDraws from the main chain when run() was given draws=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,
                                          doc="Is passband integration in use?")
 

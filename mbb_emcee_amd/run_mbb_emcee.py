@@ -54,6 +54,10 @@ def build_parser():
                    help="predict fluxes from the chain on the device: each SPEC a wavelength in um or, with --response, "
                         "the name of a passband of the wheel (needs --sampler device): mean and 68.3%% interval printed, "
                         "and added to the .npz as predict_*")
+    p.add_argument("--draws", type=int, default=0, metavar="N",
+                   help="draw N cells of the chain on the device (parameters, lnprob, walker and step; with "
+                        "--get_peaklambda the peak wavelength too; needs --sampler device): printed, and added to the "
+                        ".npz as draws_*")
     p.add_argument("-v", "--verbose", action="store_true")
     for nm, dflt in zip(NAMES, (10.0, 2.0, 2500.0, 4.0, 40.0)):
         p.add_argument("--init" + nm, type=float, default=dflt)
@@ -118,6 +122,8 @@ def main(argv=None):
                                   derived=("peaklambda",) if a.get_peaklambda else ())
     if a.predict:
         extra["predict"] = parse_predict(a.predict)
+    if a.draws:
+        extra["draws"] = dict(n=a.draws, derived=("peaklambda",) if a.get_peaklambda else ())
     fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary, **extra)
     chain, lnp = fit.sampler.chain, fit.sampler.lnprobability
     out = dict(chain=chain, lnprobability=lnp, acceptance_fraction=fit.sampler.acceptance_fraction,
@@ -138,6 +144,9 @@ def main(argv=None):
     if a.predict:
         out.update(fit.predictions.arrays())
         print(fit.predictions)
+    if a.draws:
+        out.update(fit.draws.arrays())
+        print(fit.draws)
     np.savez_compressed(a.outfile, **out)
     if a.verbose:
         flat = chain.reshape(-1, 5)
