@@ -434,6 +434,61 @@ int mbb_sampler_draws(mbb_ctx *ctx, void *sampler, const mbb_draws_spec *spec, c
 int mbb_draw_indices(mbb_ctx *ctx, int nsrc, int nw, int nsteps, int burn, int thin, int n, int how,
                      unsigned long long seed, int32_t *index);
 
+/* ---- goodness of fit of a chain, computed where the chain is ---- */
+/* New: the reference has nothing comparable (its "ChiSquare of best fit point" is -2 lnprob, which carries the soft
+ * upper walls and the Gaussian priors: results.py:261-272, likelihood.py:672-752).  Everything is per source, over a
+ * summary's window: steps burn, burn + thin, ... of every walker.
+ *   chisq   of a chain row theta: sum_b (f_b - m_b(theta))^2 ivar_b, or r^T C^-1 r with r = f - m when the data has a
+ *           covariance matrix; m_b the model flux through band b of the context (mbb_set_bands' samples, mbb_set_model),
+ *           f, ivar, C^-1 the context's data (mbb_set_data, mbb_set_data_multi).  Defined for every row the SED
+ *           constructor succeeds on, whatever the limits and priors are: a row below a lower limit has one.  A row the
+ *           constructor fails on gives NaN and its row-status bit when it is inside the window.
+ *   q       = Q(nb/2, chisq/2), Q the regularised upper incomplete gamma function, nb the number of bands: the
+ *           probability that data replicated from the model at theta with the stated errors has a larger chisq.  Its
+ *           posterior mean is the posterior predictive p-value of the chisq discrepancy.  chisq <= 0 gives 1, +inf 0,
+ *           NaN NaN.
+ *   columns slot 0 is chisq, slot 1 is q: n_used, mean, min, max, numpy-linear percentiles of exact order statistics
+ *           and mbb_summary_status bits, as a summary column without clipping.
+ *   at_mean theta-bar, the window's mean of each parameter column (the bits a summary of the same window with neither
+ *           clipping nor derived columns reports as mean[0:5]; a summary with derived columns may split its sums
+ *           otherwise and differ in the last bits), then chisq(theta-bar) and q(theta-bar).
+ *   ml      the window's entry of smallest chisq, ties to the smallest index in [walker][step] order; a NaN never
+ *           wins: its parameters (the chain's bits), chisq, q; ml_index (walker, step); ml_model its nb band fluxes.
+ *           All NaN and index -1 when every entry is NaN.
+ *   best    chisq and q of the window's entry of largest lnprob, best_index the summary's; NaN and -1 without lnprob.
+ * A row's chisq and q are the same bits whatever the call's shape and wherever the chain came from.  The chain's nsrc
+ * is the context's, or the context holds one source, which then serves every source of the chain; at most 256 bands. */
+typedef struct mbb_goodness_spec {
+    int32_t npct;                          /* 1 .. MBB_SUMMARY_MAX_PCT                                        */
+    int32_t burn, thin;                    /* window: steps burn, burn + thin, ...                            */
+    double pct[MBB_SUMMARY_MAX_PCT];       /* numpy's q, 0 .. 100                                             */
+} mbb_goodness_spec;
+/* Where the results go; every pointer is the caller's, host memory, required. */
+typedef struct mbb_goodness_out {
+    int64_t *n_used;                       /* [nsrc][2]                                                       */
+    double *mean, *min, *max;              /* [nsrc][2]                                                       */
+    int32_t *status;                       /* [nsrc][2] mbb_summary_status bits (never MBB_SUM_ABSENT)        */
+    double *pct;                           /* [nsrc][2][npct]                                                 */
+    double *at_mean;                       /* [nsrc][7] theta-bar, chisq, q                                   */
+    double *ml;                            /* [nsrc][7] parameters, chisq, q                                  */
+    int32_t *ml_index;                     /* [nsrc][2] walker, step                                          */
+    double *ml_model;                      /* [nsrc][nb]                                                      */
+    double *best;                          /* [nsrc][2] chisq, q                                              */
+    int32_t *best_index;                   /* [nsrc][2] walker, step                                          */
+} mbb_goodness_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5], its lnprob [nsrc][nw][nsteps] or NULL: upload, work on the
+ * device, download the results.  Arguments are checked before anything is allocated, uploaded or launched:
+ * MBB_ERR_STATE with no bands or data set, MBB_ERR_ARG otherwise, with a message. */
+int mbb_chain_goodness(mbb_ctx *ctx, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                       const mbb_goodness_spec *spec, const mbb_goodness_out *out);
+/* The same of the chain the sampler's last stored or summarised run left on the device.  MBB_ERR_STATE when there is
+ * none, and for a sharded run, as mbb_sampler_predict. */
+int mbb_sampler_goodness(mbb_ctx *ctx, void *sampler, const mbb_goodness_spec *spec, const mbb_goodness_out *out);
+/* chisq, q and the row status of n parameter rows, and their band fluxes model_flux [n*nb] unless NULL: the device
+ * function the chain's entries go through.  Rows are grouped by source as for mbb_lnlike_batch. */
+int mbb_goodness_rows(mbb_ctx *ctx, const double *pars, int n, double *chisq, double *q, int32_t *status,
+                      double *model_flux);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

@@ -94,6 +94,17 @@ class PredictOut(C.Structure):
     _fields_ = [("n_used", _lp), ("mean", _dp), ("min", _dp), ("max", _dp), ("pct", _dp), ("status", _ip)]
 
 
+class GoodnessSpec(C.Structure):
+    """mbb_goodness_spec (include/mbb_hip.h)"""
+    _fields_ = [("npct", C.c_int32), ("burn", C.c_int32), ("thin", C.c_int32), ("pct", C.c_double * SUMMARY_MAX_PCT)]
+
+
+class GoodnessOut(C.Structure):
+    """mbb_goodness_out (include/mbb_hip.h)"""
+    _fields_ = [("n_used", _lp), ("mean", _dp), ("min", _dp), ("max", _dp), ("status", _ip), ("pct", _dp),
+                ("at_mean", _dp), ("ml", _dp), ("ml_index", _ip), ("ml_model", _dp), ("best", _dp), ("best_index", _ip)]
+
+
 DRAWS_MAX = 1 << 24
 DRAWS_RANDOM, DRAWS_EVEN = 0, 1
 
@@ -147,6 +158,10 @@ SIGNATURES = {
     "mbb_sampler_draws": (C.c_int, [_vp, _vp, C.POINTER(DrawsSpec), C.POINTER(DrawsOut)]),
     "mbb_draw_indices": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
                                    _ip]),
+    "mbb_chain_goodness": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(GoodnessSpec),
+                                     C.POINTER(GoodnessOut)]),
+    "mbb_sampler_goodness": (C.c_int, [_vp, _vp, C.POINTER(GoodnessSpec), C.POINTER(GoodnessOut)]),
+    "mbb_goodness_rows": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _ip, _dp]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

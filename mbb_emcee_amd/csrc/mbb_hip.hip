@@ -34,6 +34,7 @@
 #include "mbb_diag.hip.h"
 #include "mbb_marginals.hip.h"
 #include "mbb_predict.hip.h"
+#include "mbb_goodness.hip.h"
 #include "mbb_draws.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
@@ -238,6 +239,8 @@ struct mbb_ctx {
     // bands
     int nb = 0, nseg = 0, nunit = 0, npart = 0, nchunk = 0, nq = 0;
     long t_prep_ns = 0, t_launch_ns = 0, t_wait_ns = 0;   // phases of the last mbb_lnlike_batch
+    std::vector<double> band_freq, band_wt;   // the bands as mbb_set_bands was given them: sample frequencies [GHz], weights,
+    std::vector<int32_t> band_off;            // ... and offsets [nb + 1] (the goodness of fit sums them in this order)
     int simd_chunks[4] = {0, 0, 0, 0};   // chunks dealt to each SIMD position by the unit table
     // Every device or pinned block below is an owner (mbb_owned.h), grouped with its capacity: it is remade through grow()
     // and freed with the context.
@@ -337,7 +340,8 @@ struct mbb_ctx {
     } diag;
     struct MargWork { DevBuf extent, range, part1, part2, outbuf; } marg;       // ... the chain marginals (marg_run)
     struct PredWork { DevBuf samples, part, state, hist, status, outbuf; } pred;   // ... the predicted fluxes (pred_run)
-    struct DrawWork { DevBuf rows, aux; } draw;     // ... and the posterior draws (draws_run): the compact block, its lnprob and index
+    struct DrawWork { DevBuf rows, aux; } draw;     // ... the posterior draws (draws_run): the compact block, its lnprob and index
+    struct GoodWork { DevBuf samples, band, mf, rows, part, state, hist, best, status, outbuf; } good;   // ... and the goodness of fit (good_run)
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -640,6 +644,9 @@ extern "C" int mbb_set_bands(mbb_ctx *c, const double *freq, const double *weigh
     if ((rc = upload(c->band.band_rng, band_rng))) return rc;
     if ((rc = upload(c->band.tail_slot, L.tail_slot))) return rc;
     c->nb = nb;
+    c->band_off.assign(offsets, offsets + nb + 1);
+    c->band_freq.assign(freq, freq + offsets[nb]);
+    c->band_wt.assign(weight, weight + offsets[nb]);
     c->nchunk = L.nchunk;
     c->nseg = L.nseg;
     c->nunit = L.nunit;
@@ -3074,6 +3081,288 @@ extern "C" int mbb_draw_indices(mbb_ctx *c, int nsrc, int nw, int nsteps, int bu
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(index, a.o_index, nd * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return MBB_OK;
+}
+
+// ---- goodness of fit of a chain (mbb_goodness.hip.h) ------------------------
+// What every goodness call needs of the context, and of the sources its rows belong to: before anything else is done.
+static int good_check_ctx(const mbb_ctx *c, int nsrc)
+{
+    if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
+    if (c->data_nb <= 0) return fail(MBB_ERR_STATE, "data not set (mbb_set_data)");
+    if (c->data_nb != c->nb) return fail(MBB_ERR_STATE, "the data and the bands differ in number");
+    if (c->nb > mbbq::kMaxBands) return fail(MBB_ERR_ARG, "more than 256 bands in a goodness call");
+    if (nsrc != c->nsrc && c->nsrc != 1)
+        return fail(MBB_ERR_ARG, "the chain's sources must be the context's, or the context hold one source for all");
+    return MBB_OK;
+}
+
+static long long good_kept_steps(const mbb_goodness_spec *sp, int nsteps)
+{
+    return ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
+}
+
+// The argument checks of a goodness call: before anything is allocated, uploaded or launched.
+static int good_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_goodness_spec *sp, const mbb_goodness_out *o)
+{
+    if (!sp || !o || !o->n_used || !o->mean || !o->min || !o->max || !o->status || !o->pct || !o->at_mean || !o->ml ||
+        !o->ml_index || !o->ml_model || !o->best || !o->best_index)
+        return fail(MBB_ERR_ARG, "null goodness argument");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    int rc;
+    if ((rc = good_check_ctx(c, nsrc))) return rc;
+    if (sp->npct < 1 || sp->npct > mbbs::kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per goodness call");
+    for (int k = 0; k < sp->npct; ++k)
+        if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
+    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    if ((long long)nw * good_kept_steps(sp, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
+    if ((size_t)nsrc * 5 > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    return MBB_OK;
+}
+
+// The context's bands on the device as the goodness kernels read them: samples, their logarithms, weights, the band table.
+static int good_upload_bands(mbb_ctx *c, mbbq::FluxArgs &fa)
+{
+    mbb_ctx::GoodWork &w = c->good;
+    const int nb = c->nb, ns = c->band_off[nb];
+    int rc;
+    if ((rc = grow(c, w.samples, (size_t)ns * 3 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.band, (size_t)nb * 3 * sizeof(int32_t)))) return rc;
+    std::vector<int32_t> tab((size_t)nb * 3);
+    memset(&fa, 0, sizeof fa);
+    for (int b = 0; b < nb; ++b) {
+        const int s0 = c->band_off[b], s1 = c->band_off[b + 1];
+        const int single = s1 - s0 == 1 && c->band_wt[s0] == 1.0;
+        tab[3 * b] = s0; tab[3 * b + 1] = s1; tab[3 * b + 2] = single;
+        if (single) ++fa.nsingle; else ++fa.nmany;
+    }
+    double *const d_nu = (double *)w.samples.p, *const d_ln = d_nu + ns, *const d_wt = d_ln + ns;
+    // (pageable sources: the copies have read them when they return)
+    HIPCHK(hipMemcpyAsync(d_nu, c->band_freq.data(), (size_t)ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_wt, c->band_wt.data(), (size_t)ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(w.band.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(mbbq::k_good_lnnu, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream, (const double *)d_nu, ns, d_ln);
+    HIPCHK(hipGetLastError());
+    fa.nu = d_nu; fa.lnnu = d_ln; fa.wt = d_wt;
+    fa.band = (const int32_t *)w.band.p;
+    fa.nb = nb; fa.nsamples = ns;
+    return MBB_OK;
+}
+
+// Band fluxes, chisq and q of the n rows whose records launch_prologue has just made: k_good_flux, then k_good_chi.
+// ca carries where the results go; the rows, the band fluxes and the data are filled in here.
+static int good_eval(mbb_ctx *c, mbbq::FluxArgs &fa, mbbq::ChiArgs &ca, int n)
+{
+    using namespace mbbq;
+    fa.wk = c->sed.wk.d(); fa.status = c->sed.status.d();
+    fa.n = n; fa.mf = (double *)c->good.mf.p;
+    const bool stage = fa.nmany > 0 && fa.nsamples <= kLdsSamples;
+    const size_t lds = stage ? (size_t)fa.nsamples * 3 * sizeof(double) : 0;
+    const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
+    dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
+        if (stage)
+            hipLaunchKernelGGL((k_good_flux<decltype(OT)::value, decltype(NA)::value, true>), grid, dim3(kThreads), lds, c->stream, fa);
+        else
+            hipLaunchKernelGGL((k_good_flux<decltype(OT)::value, decltype(NA)::value, false>), grid, dim3(kThreads), 0, c->stream, fa);
+    });
+    HIPCHK(hipGetLastError());
+    ca.mf = fa.mf; ca.status = fa.status; ca.n = n; ca.nb = c->nb;
+    ca.nsrc_data = c->nsrc;
+    ca.flux = c->data.flux.d(); ca.ivar = c->data.ivar.d();
+    ca.invcov = c->has_cov ? c->data.invcov.d() : nullptr;
+    ca.cov_in_lds = c->has_cov && c->nb <= kLdsCov;
+    const size_t clds = ca.cov_in_lds ? (size_t)c->nb * c->nb * sizeof(double) : 0;
+    hipLaunchKernelGGL(k_good_chi, grid, dim3(kThreads), clds, c->stream, ca);
+    HIPCHK(hipGetLastError());
+    return MBB_OK;
+}
+
+// Goodness of fit of a chain that is on the device in emcee's layout (lnprob may be null).  Synchronous; the results
+// land in the caller's arrays.
+static int good_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
+                    const mbb_goodness_spec *sp, const mbb_goodness_out *o)
+{
+    using namespace mbbq;
+    int rc;
+    if ((rc = good_check(c, nsrc, nw, nsteps, sp, o))) return rc;
+    const int nb = c->nb;
+    const size_t cells = (size_t)nsrc * nw * nsteps, s2 = (size_t)nsrc * 2, ns = (size_t)nsrc, np = (size_t)sp->npct;
+    // theta-bar: the five parameter columns exactly as a summary of this window with neither clipping nor derived
+    // columns reduces them (fill_chain_view chooses the splits from nsrc * ncol: with derived columns they may differ)
+    mbb_summary_spec ss;
+    memset(&ss, 0, sizeof ss);
+    ss.burn = sp->burn; ss.thin = sp->thin;
+    mbbs::SumArgs a5;
+    memset(&a5, 0, sizeof a5);
+    fill_chain_view(a5, d_chain, nsrc, nw, nsteps, &ss, 16384);
+    // the two columns: the window and a column's splits as for the predicted fluxes
+    mbbs::SumArgs a;
+    memset(&a, 0, sizeof a);
+    a.chain = d_chain; a.lnprob = d_lnprob;
+    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
+    a.nkept = (int)good_kept_steps(sp, nsteps);
+    a.n = (long long)nw * a.nkept;
+    a.splits = nsrc >= 256 ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (a.n + 16383) / 16384);
+    a.per_split = (a.n + a.splits - 1) / a.splits;
+    a.npct = sp->npct;
+    for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
+    a.ncol = 2; a.col[0] = 5; a.col[1] = 6;
+    mbb_ctx::GoodWork &w = c->good;
+    const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
+    const size_t nev = 2 * ns;                              // rows evaluated at the end: theta-bar and the ML entry of every source
+    const size_t rows_max = std::max(chunk, nev);
+    // the result block: 64-bit counts, doubles, 32-bit words
+    const size_t out_doubles = s2 * (3 + np) + ns * 7 * 2 + ns * 2 + nev * 2 + nev * nb;
+    const size_t out_bytes = s2 * sizeof(long long) + out_doubles * sizeof(double) + (s2 + ns * 4 + nev) * sizeof(int);
+    if ((rc = grow(c, w.part, std::max(ns * 5 * a5.splits, s2 * a.splits) * mbbs::kStatWords * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.state, ns * 5 * sizeof(mbbs::ColState)))) return rc;
+    if ((rc = grow(c, w.hist, s2 * a.splits * mbbs::kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    if ((rc = grow(c, w.best, ns * a.splits * kBestWords * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.status, s2 * sizeof(int)))) return rc;
+    if ((rc = grow(c, w.rows, nev * 5 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.mf, rows_max * nb * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = grow(c, c->der.der, 2 * cells * sizeof(double)))) return rc;
+    if ((rc = ensure_sed(c, rows_max, 0))) return rc;
+    double *const col0 = (double *)c->der.der.p, *const col1 = col0 + cells;
+    a.der[0] = col0; a.der[1] = col1;
+    a5.part = a.part = (double *)w.part.p; a5.state = a.state = (mbbs::ColState *)w.state.p; a.hist = (unsigned int *)w.hist.p;
+    double *const d_rows = (double *)w.rows.p;
+    FinishArgs f;
+    PickArgs pk;
+    Carve ob{(char *)w.outbuf.p};
+    f.o_nused = ob.take<long long>(s2);
+    f.o_mean = ob.take<double>(s2); f.o_min = ob.take<double>(s2); f.o_max = ob.take<double>(s2);
+    f.o_pct = ob.take<double>(s2 * np);
+    f.o_atmean = ob.take<double>(ns * 7); f.o_ml = pk.o_ml = ob.take<double>(ns * 7);
+    pk.o_best = ob.take<double>(ns * 2);
+    double *const ev_chisq = ob.take<double>(nev), *const ev_q = ob.take<double>(nev), *const ev_mf = ob.take<double>(nev * nb);
+    f.o_status = ob.take<int>(s2);
+    pk.o_mlidx = ob.take<int>(ns * 2); pk.o_bestidx = ob.take<int>(ns * 2);
+    int *const ev_status = ob.take<int>(nev);
+    f.gstatus = (const int *)w.status.p;
+    f.tbar = d_rows; f.ev_chisq = ev_chisq; f.ev_q = ev_q;
+    pk.part = (const double *)w.best.p; pk.ml_row = d_rows + ns * 5;
+    FluxArgs fa;
+    if ((rc = good_upload_bands(c, fa))) return rc;
+    HIPCHK(hipMemsetAsync(w.status.p, 0, s2 * sizeof(int), c->stream));
+    // theta-bar
+    {
+        const size_t ncol5 = ns * 5;
+        hipLaunchKernelGGL(mbbs::k_sum_stats, dim3((unsigned)ncol5, (unsigned)a5.splits), dim3(mbbs::kThreads), 0, c->stream, a5);
+        hipLaunchKernelGGL(mbbs::k_sum_begin, dim3((unsigned)((ncol5 + 63) / 64)), dim3(64), 0, c->stream, a5);
+        hipLaunchKernelGGL(k_good_mean, dim3((unsigned)((ncol5 + 63) / 64)), dim3(64), 0, c->stream, a5, d_rows);
+        HIPCHK(hipGetLastError());
+    }
+    // the columns, a chunk of rows at a time
+    for (size_t off = 0; off < cells; off += chunk) {
+        const int n = (int)std::min(chunk, cells - off);
+        if ((rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+        ChiArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.off = ca.out = (long long)off; ca.rows_per_src = (long long)nw * nsteps;
+        ca.chisq = col0; ca.q = col1;
+        ca.gstatus = (int *)w.status.p; ca.nw = nw; ca.nsteps = nsteps; ca.burn = sp->burn; ca.thin = sp->thin;
+        if ((rc = good_eval(c, fa, ca, n))) return rc;
+    }
+    // their statistics, by the summary's kernels
+    const dim3 gcol((unsigned)s2, (unsigned)a.splits);
+    hipLaunchKernelGGL(mbbs::k_sum_stats, gcol, dim3(mbbs::kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(mbbs::k_sum_begin, dim3((unsigned)((s2 + 63) / 64)), dim3(64), 0, c->stream, a);
+    for (int pass = 0; pass < 8; ++pass) {
+        hipLaunchKernelGGL(mbbs::k_sum_hist, gcol, dim3(mbbs::kThreads), 0, c->stream, a, pass);
+        hipLaunchKernelGGL(mbbs::k_sum_pick, dim3((unsigned)s2), dim3(mbbs::kThreads), 0, c->stream, a);
+    }
+    // the maximum-likelihood and the maximum-lnprob entries
+    hipLaunchKernelGGL(k_good_best, dim3((unsigned)nsrc, (unsigned)a.splits), dim3(kThreads), 0, c->stream, a, (double *)w.best.p);
+    hipLaunchKernelGGL(k_good_pick, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, c->stream, a, pk);
+    HIPCHK(hipGetLastError());
+    // theta-bar and the ML entry of every source, evaluated as rows: row i belongs to source i mod nsrc
+    {
+        if ((rc = launch_prologue(c, d_rows, (int)nev, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+        ChiArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.off = 0; ca.rows_per_src = 1;
+        ca.chisq = ev_chisq; ca.q = ev_q; ca.row_status = ev_status; ca.mf_rows = ev_mf;
+        if ((rc = good_eval(c, fa, ca, (int)nev))) return rc;
+    }
+    hipLaunchKernelGGL(k_good_finish, dim3((unsigned)((s2 + 63) / 64)), dim3(64), 0, c->stream, a, f);
+    HIPCHK(hipGetLastError());
+    std::vector<char> host(out_bytes);
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Carve hb{host.data()};
+    hb.put(o->n_used, s2);
+    hb.put(o->mean, s2); hb.put(o->min, s2); hb.put(o->max, s2);
+    hb.put(o->pct, s2 * np);
+    hb.put(o->at_mean, ns * 7); hb.put(o->ml, ns * 7);
+    hb.put(o->best, ns * 2);
+    hb.take<double>(nev * 2);                                // (the rows' chisq and q: in at_mean and ml already)
+    hb.take<double>(ns * nb);                                // (theta-bar's band fluxes)
+    hb.put(o->ml_model, ns * nb);
+    hb.put(o->status, s2);
+    hb.put(o->ml_index, ns * 2); hb.put(o->best_index, ns * 2);
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_goodness(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                                  const mbb_goodness_spec *spec, const mbb_goodness_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = good_check(c, nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
+        return good_run(c, d, lnprob ? d + cells * 5 : nullptr, nsrc, nw, nsteps, spec, out);
+    });
+}
+
+extern "C" int mbb_sampler_goodness(mbb_ctx *c, void *sp, const mbb_goodness_spec *spec, const mbb_goodness_out *out)
+{
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, spec && out, "tested for goodness of fit", s)) || (rc = resident_chain(s))) return rc;
+    const size_t cells = (size_t)s->rows() * s->resident_nsteps;
+    return good_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+}
+
+extern "C" int mbb_goodness_rows(mbb_ctx *c, const double *pars, int n, double *chisq, double *q, int32_t *status,
+                                 double *model_flux)
+{
+    using namespace mbbq;
+    int rc = use(c);
+    if (rc) return rc;
+    if (!pars || n <= 0 || !chisq || !q || !status) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = good_check_ctx(c, c->nsrc))) return rc;
+    if (n % c->nsrc != 0) return fail(MBB_ERR_ARG, "in multi-source mode the rows must be nsources equal blocks");
+    const int nb = c->nb;
+    const size_t chunk = std::min<size_t>((size_t)n, (size_t)kSumChunkRows);
+    mbb_ctx::GoodWork &w = c->good;
+    const size_t out_bytes = chunk * (2 + (size_t)nb) * sizeof(double) + chunk * sizeof(int);
+    if ((rc = grow(c, w.mf, chunk * nb * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = ensure_sed(c, chunk, 0))) return rc;
+    FluxArgs fa;
+    if ((rc = good_upload_bands(c, fa))) return rc;
+    Carve ob{(char *)w.outbuf.p};
+    double *const d_chisq = ob.take<double>(chunk), *const d_q = ob.take<double>(chunk), *const d_mf = ob.take<double>(chunk * nb);
+    int *const d_status = ob.take<int>(chunk);
+    for (size_t off = 0; off < (size_t)n; off += chunk) {
+        const int m = (int)std::min(chunk, (size_t)n - off);
+        if ((rc = run_prologue(c, pars + off * 5, m, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+        ChiArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.off = (long long)off; ca.rows_per_src = n / c->nsrc;
+        ca.chisq = d_chisq; ca.q = d_q; ca.row_status = d_status; ca.mf_rows = model_flux ? d_mf : nullptr;
+        if ((rc = good_eval(c, fa, ca, m))) return rc;
+        HIPCHK(hipMemcpyAsync(chisq + off, d_chisq, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(q + off, d_q, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(status + off, d_status, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (model_flux)
+            HIPCHK(hipMemcpyAsync(model_flux + off * nb, d_mf, (size_t)m * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     return MBB_OK;
 }
 

@@ -98,7 +98,7 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_`` or ``predictions_``, nothing resident for ``convergence()`` or
+        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_`` or ``predictions_``, nothing resident for ``convergence()`` or
         ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
@@ -119,6 +119,7 @@ class DeviceEnsembleSampler(object):
         self.convergence_ = None
         self.marginals_ = None
         self.draws_ = None
+        self.goodness_ = None
         self._drop_predictions()
         self._resident = 0                    # steps of the last run's chain that are resident on the device
         if self._h is not None:
@@ -210,6 +211,24 @@ class DeviceEnsembleSampler(object):
         _native.check_arg(ctx.lib.mbb_sampler_draws(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return draws.ChainDraws(self.lnprobfn, req, raw, self.nsources > 1, self.k, nkept)
 
+    def goodness(self, percentile=68.3, percentiles=(), burn=0, thin=1):
+        """``goodness.ChainGoodness`` (chisq of every entry against the data whatever the limits and priors, its tail
+        probability, the posterior predictive p-value, DIC, the maximum-likelihood entry and its pulls) of the chain
+        the last run left on the device -- a run with storechain=True or with summary= --; the keywords are
+        ``goodness.chain_goodness``'s.  No chain crosses the bus."""
+        from . import goodness
+        cens, qs = goodness._quantiles(percentile, percentiles)
+        req = goodness._Request(self.lnprobfn, qs, burn, thin)
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: goodness() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset")
+        nkept = req.check_steps(self._resident)
+        ctx, h = self._handle()
+        raw = goodness._Raw(self.nsources, req.ndata, len(req.qs))
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(ctx.lib.mbb_sampler_goodness(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return goodness.ChainGoodness(req, raw, self.nsources > 1, cens[0], self.k, nkept)
+
     def predictions(self, specs, percentile=68.3, percentiles=(), burn=0, thin=1, clip=None, wavenorm=None, keep=True):
         """``predict.ChainPredictions`` (predicted fluxes at wavelengths and through passbands, ``predflux_cen``) of the
         chain the last run left on the device -- a run with storechain=True or with summary= --; the arguments are
@@ -252,7 +271,7 @@ class DeviceEnsembleSampler(object):
         return raw
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
-                 marginals=None, predict=None, draws=None, **unused):
+                 marginals=None, predict=None, draws=None, goodness=None, **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -296,9 +315,14 @@ class DeviceEnsembleSampler(object):
         draws=n, or a dict of ``draws()``'s keywords (``n`` among them): that many cells per source are drawn from the
         chain of this run on the device and ``sampler.draws_`` is the ``draws.ChainDraws`` of them (None again after
         reset() and at the start of the next run).  With storechain=False it needs summary= too; burn, thin, derived
-        and the derived columns' settings default to those given with summary=."""
+        and the derived columns' settings default to those given with summary=.
+
+        goodness=True, or a dict of ``goodness()``'s keywords: the chain of this run is held against the data on the
+        device and ``sampler.goodness_`` is the ``goodness.ChainGoodness`` of it (None again after reset() and at the
+        start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
+        with summary=."""
         self._retire()
-        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws)
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws, goodness)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
@@ -318,11 +342,12 @@ class DeviceEnsembleSampler(object):
             self._resident = 0                # (what is resident is the last chunk: a part)
 
     def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None, predict=None,
-             draws=None):
-        creq = mkw = pkw = dkw = None
+             draws=None, goodness=None):
+        creq = mkw = pkw = dkw = gkw = None
         self.convergence_ = None
         self.marginals_ = None
         self.draws_ = None
+        self.goodness_ = None
         self._drop_predictions()                    # (the chain they could go back to is about to be overwritten)
         if predict is not None and predict is not False:
             from . import predict as _predict
@@ -343,6 +368,23 @@ class DeviceEnsembleSampler(object):
                 raise ValueError("predict= with storechain=False needs summary= too: a run that neither stores "
                                  "nor summarises its chain keeps none on the device")
             preq.check_steps(int(N))
+        if goodness is not None and goodness is not False:
+            from . import goodness as _goodness
+            gkw = {} if goodness is True else dict(goodness)
+            if summary is not None and summary is not False and summary is not True:
+                for key in ("burn", "thin"):
+                    if key in summary:
+                        gkw.setdefault(key, summary[key])
+            unknown = set(gkw) - {"percentile", "percentiles", "burn", "thin"}
+            if unknown:
+                raise TypeError("goodness= got unexpected keyword(s) {}".format(sorted(unknown)))
+            greq = _goodness._Request(self.lnprobfn, _goodness._quantiles(gkw.get("percentile", 68.3),
+                                                                          gkw.get("percentiles", ()))[1],
+                                      gkw.get("burn", 0), gkw.get("thin", 1))
+            if not storechain and (summary is None or summary is False):
+                raise ValueError("goodness= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device")
+            greq.check_steps(int(N))
         if marginals is not None and marginals is not False:
             from . import marginals as _marginals
             mkw = {} if marginals is True else dict(marginals)
@@ -386,6 +428,9 @@ class DeviceEnsembleSampler(object):
         if pkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be predicted from on the device: a rank holds only its own "
                              "walkers' chain")
+        if gkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be tested for goodness of fit on the device: a rank holds "
+                             "only its own walkers' chain")
         if dkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be drawn from on the device: a rank holds only its own "
                              "walkers' chain")
@@ -487,6 +532,8 @@ class DeviceEnsembleSampler(object):
             self.predictions_ = self.predictions(**pkw)
         if dkw is not None:
             self.draws_ = self.draws(**dkw)
+        if gkw is not None:
+            self.goodness_ = self.goodness(**gkw)
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):

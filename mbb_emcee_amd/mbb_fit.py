@@ -138,7 +138,7 @@ class mbb_fitter(object):
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
     def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None,
-            draws=None):
+            draws=None, goodness=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
@@ -151,7 +151,12 @@ class mbb_fitter(object):
         ``predict.chain_predictions``'s keywords (``specs`` among them) -- the fluxes the main chain predicts there,
         ``mbb_fitter.predictions``.
         draws (device sampler only): a number of draws per source, or a dict of ``draws.chain_draws``'s keywords (``n``
-        among them) -- cells drawn from the main chain with their derived values, ``mbb_fitter.draws``."""
+        among them) -- cells drawn from the main chain with their derived values, ``mbb_fitter.draws``.
+        goodness (device sampler only): True or a dict of ``goodness.chain_goodness``'s keywords -- the main chain's
+        chisq against the data, posterior predictive p-value, DIC and maximum-likelihood entry,
+        ``mbb_fitter.goodness``."""
+        if goodness is not None and goodness is not False and not hasattr(self.sampler, "goodness"):
+            raise ValueError("goodness= needs sampler=\"device\"")
         if draws is not None and draws is not False and not hasattr(self.sampler, "draws"):
             raise ValueError("draws= needs sampler=\"device\"")
         if predict is not None and predict is not False and not hasattr(self.sampler, "predictions"):
@@ -204,6 +209,8 @@ class mbb_fitter(object):
             extra["predict"] = predict
         if draws is not None and draws is not False:
             extra["draws"] = draws
+        if goodness is not None and goodness is not False:
+            extra["goodness"] = goodness
         self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, **extra)
         self._sampled = True
 
@@ -247,6 +254,8 @@ mbb_fitter.marginals = property(lambda self: getattr(self.sampler, "marginals_",
                                 doc="marginals.ChainMarginals of the main chain when run() was given marginals=, else None")
 mbb_fitter.predictions = property(lambda self: getattr(self.sampler, "predictions_", None),
                                   doc="predict.ChainPredictions of the main chain when run() was given predict=, else None")
+mbb_fitter.goodness = property(lambda self: getattr(self.sampler, "goodness_", None),
+                               doc="goodness.ChainGoodness of the main chain when run() was given goodness=, else None")
 mbb_fitter.draws = property(lambda self: getattr(self.sampler, "draws_", None),
                             doc="draws.ChainDraws from the main chain when run() was given draws=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,

@@ -54,6 +54,10 @@ def build_parser():
                    help="predict fluxes from the chain on the device: each SPEC a wavelength in um or, with --response, "
                         "the name of a passband of the wheel (needs --sampler device): mean and 68.3%% interval printed, "
                         "and added to the .npz as predict_*")
+    p.add_argument("--goodness", action="store_true",
+                   help="goodness of fit from the chain on the device (needs --sampler device): chisq of every entry "
+                        "against the data, the posterior predictive p-value, DIC and the maximum-likelihood entry "
+                        "printed, and added to the .npz as goodness_*")
     p.add_argument("--draws", type=int, default=0, metavar="N",
                    help="draw N cells of the chain on the device (parameters, lnprob, walker and step; with "
                         "--get_peaklambda the peak wavelength too; needs --sampler device): printed, and added to the "
@@ -122,6 +126,8 @@ def main(argv=None):
                                   derived=("peaklambda",) if a.get_peaklambda else ())
     if a.predict:
         extra["predict"] = parse_predict(a.predict)
+    if a.goodness:
+        extra["goodness"] = True
     if a.draws:
         extra["draws"] = dict(n=a.draws, derived=("peaklambda",) if a.get_peaklambda else ())
     fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary, **extra)
@@ -144,6 +150,9 @@ def main(argv=None):
     if a.predict:
         out.update(fit.predictions.arrays())
         print(fit.predictions)
+    if a.goodness:
+        out.update(fit.goodness.arrays())
+        print(fit.goodness)
     if a.draws:
         out.update(fit.draws.arrays())
         print(fit.draws)
