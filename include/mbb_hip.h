@@ -489,6 +489,69 @@ int mbb_sampler_goodness(mbb_ctx *ctx, void *sampler, const mbb_goodness_spec *s
 int mbb_goodness_rows(mbb_ctx *ctx, const double *pars, int n, double *chisq, double *q, int32_t *status,
                       double *model_flux);
 
+/* ---- the maximum of the posterior, found on the device ---- */
+/* New: the reference has no optimiser; its "best fit" is the chain entry of largest lnprob (results.py:160-165).
+ * -2 ln P is a sum of squares -- the data term, one square per soft upper wall that is exceeded, one per Gaussian prior
+ * (likelihood.py:672-752, :790-834) -- behind the hard lower limits, so a Levenberg-Marquardt search with projection
+ * onto the lower limits finds its minimum.  One workgroup runs the whole search of one (source, start) inside one
+ * launch (csrc/mbb_map.hip.h; the step logic is csrc/mbb_lm.hip.h); several starts per source because the optically
+ * thick models without a prior on lambda0 have more than one optimum.
+ *   start    [nsrc][nstart][5]; fixed[i] != 0 holds parameter i at its start value; lambda0 of an optically thin model
+ *            and alpha of a model without one never move.  The kernel draws nothing.
+ *   stopping predicted reduction of -2 ln P <= ftol max(1, -2 ln P) (MBB_MAP_CONVERGED_F); largest step of a
+ *            parameter relative to its value <= xtol (MBB_MAP_CONVERGED_X); maxiter iterations (MBB_MAP_MAXITER).
+ *            The predicted reduction is that of a step the projection onto the lower limits left alone: while every
+ *            candidate step is clipped onto a limit nothing is concluded, the damping rises and shorter steps follow.
+ *            ftol and xtol are finite and >= 0 (0: that test never stops the search).
+ *   lnprob   the final points of all (source, start) go through mbb_lnlike_batch's own path, so lnprob_all is bit for
+ *            bit what that call gives for params_all; per source the start of largest lnprob is picked, ties to the
+ *            lowest index, a NaN never wins (all NaN: index 0).
+ *   chisq, q, model_flux   of the picked points, by mbb_goodness_rows' path: its bits.
+ *   cov      the Laplace covariance at the picked optimum: the inverse of J^T J (J the Jacobian of the residuals) over
+ *            the parameters that are free and off their lower limit, NaN in the rows and columns of the others; all
+ *            NaN with MBB_MAP_COV_SINGULAR when that matrix is not positive definite.
+ * A start whose lnprob is -inf or NaN (below a lower limit, a failing SED constructor) is MBB_MAP_START_INVALID: its
+ * result is the start itself, zero iterations.  A source's result has the same bits whatever other sources or starts
+ * the call holds.  nsrc is the context's, or the context holds one source whose data then serves all; at most 256
+ * bands; a context that is one rank of a sharded run (mbb_comm_init, mbb_xchg_connect with more than one rank) is
+ * refused with MBB_ERR_STATE. */
+#define MBB_MAP_MAX_STARTS 64
+#define MBB_MAP_MAX_ITER 1000
+enum mbb_map_status {
+    MBB_MAP_CONVERGED_F = 1,
+    MBB_MAP_CONVERGED_X = 2,
+    MBB_MAP_MAXITER = 4,
+    MBB_MAP_START_INVALID = 8,
+    MBB_MAP_COV_SINGULAR = 16,
+    MBB_MAP_ALL_FIXED = 32,       /* no parameter is free: the result is the start, zero iterations               */
+    MBB_MAP_STENCIL_FAILED = 64,  /* the SED constructor failed on a row of the difference stencil beside the current
+                                     point (no merge point, no peak): no Jacobian there, the search ended where it was;
+                                     the result is the best point reached, its covariance NaN (MBB_MAP_COV_SINGULAR)  */
+    MBB_MAP_AT_LOWLIM_SHIFT = 8   /* bit 8 + i: parameter i of the result sits on its lower limit                 */
+};
+typedef struct mbb_map_spec {
+    int32_t nsrc;
+    int32_t nstart;                        /* 1 .. MBB_MAP_MAX_STARTS                                         */
+    int32_t maxiter;                       /* 1 .. MBB_MAP_MAX_ITER                                           */
+    int32_t fixed[5];
+    double ftol, xtol;
+    const double *start;                   /* [nsrc][nstart][5], finite                                       */
+} mbb_map_spec;
+/* Where the results go; every pointer is the caller's, host memory; model_flux, lnprob_all, params_all and status_all
+ * may be NULL, the others are required. */
+typedef struct mbb_map_out {
+    double *params;                        /* [nsrc][5]                                                       */
+    double *lnprob, *chisq, *q;            /* [nsrc]                                                          */
+    double *model_flux;                    /* [nsrc][nb] or NULL                                              */
+    double *cov;                           /* [nsrc][5][5]                                                    */
+    int32_t *niter, *nfev, *start_index;   /* [nsrc]: iterations and row evaluations of the picked start      */
+    int32_t *status;                       /* [nsrc] mbb_map_status bits of the picked start                  */
+    double *lnprob_all;                    /* [nsrc][nstart] or NULL                                          */
+    double *params_all;                    /* [nsrc][nstart][5] or NULL                                       */
+    int32_t *status_all;                   /* [nsrc][nstart] or NULL                                          */
+} mbb_map_out;
+int mbb_map_fit(mbb_ctx *ctx, const mbb_map_spec *spec, const mbb_map_out *out);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

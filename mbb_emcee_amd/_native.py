@@ -105,6 +105,25 @@ class GoodnessOut(C.Structure):
                 ("at_mean", _dp), ("ml", _dp), ("ml_index", _ip), ("ml_model", _dp), ("best", _dp), ("best_index", _ip)]
 
 
+MAP_MAX_STARTS, MAP_MAX_ITER = 64, 1000
+MAP_CONVERGED_F, MAP_CONVERGED_X, MAP_MAXITER, MAP_START_INVALID, MAP_COV_SINGULAR, MAP_ALL_FIXED = 1, 2, 4, 8, 16, 32
+MAP_STENCIL_FAILED = 64
+MAP_AT_LOWLIM_SHIFT = 8
+
+
+class MapSpec(C.Structure):
+    """mbb_map_spec (include/mbb_hip.h)"""
+    _fields_ = [("nsrc", C.c_int32), ("nstart", C.c_int32), ("maxiter", C.c_int32), ("fixed", C.c_int32 * 5),
+                ("ftol", C.c_double), ("xtol", C.c_double), ("start", _dp)]
+
+
+class MapOut(C.Structure):
+    """mbb_map_out (include/mbb_hip.h)"""
+    _fields_ = [("params", _dp), ("lnprob", _dp), ("chisq", _dp), ("q", _dp), ("model_flux", _dp), ("cov", _dp),
+                ("niter", _ip), ("nfev", _ip), ("start_index", _ip), ("status", _ip), ("lnprob_all", _dp),
+                ("params_all", _dp), ("status_all", _ip)]
+
+
 DRAWS_MAX = 1 << 24
 DRAWS_RANDOM, DRAWS_EVEN = 0, 1
 
@@ -162,6 +181,7 @@ SIGNATURES = {
                                      C.POINTER(GoodnessOut)]),
     "mbb_sampler_goodness": (C.c_int, [_vp, _vp, C.POINTER(GoodnessSpec), C.POINTER(GoodnessOut)]),
     "mbb_goodness_rows": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _ip, _dp]),
+    "mbb_map_fit": (C.c_int, [_vp, C.POINTER(MapSpec), C.POINTER(MapOut)]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

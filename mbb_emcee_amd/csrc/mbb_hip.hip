@@ -35,6 +35,7 @@
 #include "mbb_marginals.hip.h"
 #include "mbb_predict.hip.h"
 #include "mbb_goodness.hip.h"
+#include "mbb_map.hip.h"
 #include "mbb_draws.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
@@ -342,6 +343,10 @@ struct mbb_ctx {
     struct PredWork { DevBuf samples, part, state, hist, status, outbuf; } pred;   // ... the predicted fluxes (pred_run)
     struct DrawWork { DevBuf rows, aux; } draw;     // ... the posterior draws (draws_run): the compact block, its lnprob and index
     struct GoodWork { DevBuf samples, band, mf, rows, part, state, hist, best, status, outbuf; } good;   // ... and the goodness of fit (good_run)
+    struct MapWork {                                                            // the posterior's maximum (mbb_map_fit)
+        DevBuf start, outbuf;
+        size_t lds_granted[8] = {};           // whether this context has asked for the dynamic-LDS ceiling, by instantiation of k_map_lm
+    } map;
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -3364,6 +3369,128 @@ extern "C" int mbb_goodness_rows(mbb_ctx *c, const double *pars, int n, double *
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return MBB_OK;
+}
+
+// ---- the maximum of the posterior (mbb_map.hip.h) ------------------------------
+// The argument checks of mbb_map_fit: before anything is allocated, uploaded or launched.
+static int map_check(const mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out *o)
+{
+    if (!sp || !o) return fail(MBB_ERR_ARG, "null map argument");
+    if (!sp->start || !o->params || !o->lnprob || !o->chisq || !o->q || !o->cov || !o->niter || !o->nfev ||
+        !o->start_index || !o->status)
+        return fail(MBB_ERR_ARG, "null map argument");
+    if ((c->comm != nullptr && c->nranks > 1) || (c->x.connected && c->x.n > 1))
+        return fail(MBB_ERR_STATE, "a sharded context cannot run a map fit: every rank would repeat the whole search");
+    if (sp->nsrc < 1) return fail(MBB_ERR_ARG, "a map fit needs a source at least");
+    if (c->nb > mbbmap::kMaxBands) return fail(MBB_ERR_ARG, "more than 256 bands in a map fit");
+    if (sp->nsrc != c->nsrc && c->nsrc != 1)
+        return fail(MBB_ERR_ARG, "the starts' sources must be the context's, or the context hold one source for all");
+    int rc;
+    if ((rc = good_check_ctx(c, sp->nsrc))) return rc;
+    if (sp->nstart < 1 || sp->nstart > MBB_MAP_MAX_STARTS) return fail(MBB_ERR_ARG, "1 to 64 starts per source");
+    if (sp->maxiter < 1 || sp->maxiter > MBB_MAP_MAX_ITER) return fail(MBB_ERR_ARG, "1 to 1000 iterations per map fit");
+    if (!(sp->ftol >= 0.0 && sp->ftol <= 1.7976931348623157e308) || !(sp->xtol >= 0.0 && sp->xtol <= 1.7976931348623157e308))
+        return fail(MBB_ERR_ARG, "ftol and xtol must be finite and not negative");
+    if ((size_t)sp->nsrc * sp->nstart > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    const size_t nval = (size_t)sp->nsrc * sp->nstart * 5;
+    for (size_t i = 0; i < nval; ++i)
+        if (!(fabs(sp->start[i]) <= 1.7976931348623157e308)) {
+            char buf[96];
+            snprintf(buf, sizeof buf, "start of source %zu, start %zu is not finite", i / 5 / sp->nstart, i / 5 % sp->nstart);
+            return fail(MBB_ERR_ARG, buf);
+        }
+    return MBB_OK;
+}
+
+extern "C" int mbb_map_fit(mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out *o)
+{
+    using namespace mbbmap;
+    int rc = use(c);
+    if (rc) return rc;
+    if ((rc = map_check(c, sp, o))) return rc;
+    const int nb = c->nb, nsrc = sp->nsrc, nstart = sp->nstart;
+    const size_t n = (size_t)nsrc * nstart;
+    mbb_ctx::MapWork &w = c->map;
+    const size_t out_bytes = n * (kOutDoubles * sizeof(double) + kOutInts * sizeof(int32_t));
+    if ((rc = grow(c, w.start, n * 5 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    mbbq::FluxArgs fa;
+    if ((rc = good_upload_bands(c, fa))) return rc;
+    HIPCHK(hipMemcpyAsync(w.start.p, sp->start, n * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    MapArgs a;
+    memset(&a, 0, sizeof a);
+    a.start = (const double *)w.start.p; a.nstart = nstart; a.nsrc_data = c->nsrc;
+    a.nu = fa.nu; a.lnnu = fa.lnnu; a.wt = fa.wt; a.band = fa.band; a.nb = nb; a.nsamples = fa.nsamples;
+    a.flux = c->data.flux.d(); a.ivar = c->data.ivar.d();
+    a.invcov = c->has_cov ? c->data.invcov.d() : nullptr;
+    a.cov_in_lds = c->has_cov && nb <= kLdsCov;
+    a.nunorm = kUmToGHz / c->wavenorm; a.lnunorm = log(kUmToGHz / c->wavenorm);
+    for (int i = 0; i < 5; ++i) a.lowlim[i] = c->lowlim[i];
+    for (int i = 0; i < 6; ++i) { a.uplim[i] = c->uplim[i]; a.gmean[i] = c->gmean[i]; a.givar[i] = c->givar[i]; }
+    a.has_uplim = c->has_uplim; a.has_gprior = c->has_gprior;
+    // (mbblm::lm_fixed_mask: the caller's, lambda0 of an optically thin model, alpha of a model without one)
+    for (int i = 0; i < 5; ++i) if (sp->fixed[i]) a.fixed |= 1u << i;
+    if (c->opthin) a.fixed |= 1u << 2;
+    if (c->noalpha) a.fixed |= 1u << 3;
+    a.maxiter = sp->maxiter; a.ftol = sp->ftol; a.xtol = sp->xtol;
+    Carve ob{(char *)w.outbuf.p};
+    a.outd = ob.take<double>(n * kOutDoubles); a.outi = ob.take<int32_t>(n * kOutInts);
+    const bool stage = fa.nmany > 0 && fa.nsamples <= kLdsSamples;
+    const size_t lds = lds_doubles(nb, fa.nsamples, stage, c->has_cov != 0, a.cov_in_lds != 0) * sizeof(double);
+    const int inst = model_of(c) * 2 + (stage ? 1 : 0);
+    rc = MBB_OK;
+    dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
+        auto launch = [&](auto kern) {
+            if (lds > 56 * 1024 && !w.lds_granted[inst]) {
+                // (beyond 64 KB of LDS per workgroup, the kernel's static LDS included, its dynamic-LDS ceiling has to be
+                // raised.  The attribute is the function's, not the context's: every context asks for the same value, the
+                // most a map fit can need, so that none can lower what another relies on)
+                const size_t want = 152 * 1024;
+                const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
+                if (e != hipSuccess) { rc = fail(MBB_ERR_HIP, "hipFuncSetAttribute(k_map_lm)", e); return; }
+                w.lds_granted[inst] = want;
+            }
+            hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(kThreads), lds, c->stream, a);
+        };
+        if (stage) launch(k_map_lm<decltype(OT)::value, decltype(NA)::value, true>);
+        else launch(k_map_lm<decltype(OT)::value, decltype(NA)::value, false>);
+    });
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    std::vector<char> host(out_bytes);
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const double *hd = (const double *)host.data();
+    const int32_t *hi = (const int32_t *)(host.data() + n * kOutDoubles * sizeof(double));
+    // the final points of every (source, start) through the likelihood's own batch path: [nsrc][nstart][5] is its
+    // multi-source layout, and the reported lnprob is what like(params) gives, bit for bit
+    std::vector<double> pall(n * 5), lall(n);
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 5; ++k) pall[i * 5 + k] = hd[i * kOutDoubles + k];
+    if ((rc = mbb_lnlike_batch(c, pall.data(), (int)n, lall.data(), nullptr, nullptr))) return rc;
+    // per source the start of largest lnprob: ties to the lowest index, a NaN never wins
+    std::vector<double> picked((size_t)nsrc * 5);
+    for (int s = 0; s < nsrc; ++s) {
+        int best = -1;
+        for (int j = 0; j < nstart; ++j) {
+            const double v = lall[(size_t)s * nstart + j];
+            if (v != v) continue;
+            if (best < 0 || v > lall[(size_t)s * nstart + best]) best = j;
+        }
+        if (best < 0) best = 0;
+        const size_t i = (size_t)s * nstart + best;
+        for (int k = 0; k < 5; ++k) o->params[(size_t)s * 5 + k] = picked[(size_t)s * 5 + k] = pall[i * 5 + k];
+        for (int k = 0; k < 25; ++k) o->cov[(size_t)s * 25 + k] = hd[i * kOutDoubles + 6 + k];
+        o->lnprob[s] = lall[i];
+        o->niter[s] = hi[i * kOutInts]; o->nfev[s] = hi[i * kOutInts + 1]; o->status[s] = hi[i * kOutInts + 2];
+        o->start_index[s] = best;
+    }
+    if (o->lnprob_all) memcpy(o->lnprob_all, lall.data(), n * sizeof(double));
+    if (o->params_all) memcpy(o->params_all, pall.data(), n * 5 * sizeof(double));
+    if (o->status_all) for (size_t i = 0; i < n; ++i) o->status_all[i] = hi[i * kOutInts + 2];
+    // the picked points through the goodness of fit's own path: its chisq, q and band fluxes
+    std::vector<int32_t> gst((size_t)nsrc);
+    return mbb_goodness_rows(c, picked.data(), nsrc, o->chisq, o->q, gst.data(), o->model_flux);
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

@@ -136,6 +136,58 @@ class mbb_fitter(object):
                         "[{:g}, {:g}] after 100 redraws".format(worst, int(out[:, worst].sum()), self._nwalkers,
                                                                 lo[worst], hi[worst]))
 
+    # ---- the optimum before the chain (optimize.py; no reference counterpart) -----
+    def find_map(self, initvals=None, initsigma=None, nstart=8, start=None, **kw):
+        """The maximum of the posterior per source, found on the device (``optimize.map_fit``); returns a ``MapFit``.
+        The starts are ``nstart`` points of the ``generate_initial_values(initvals, initsigma)`` ball (the same for every
+        source of a catalogue), the fixed parameters are the fitter's.  start="best_fit" polishes ``summary.best_fit`` of
+        a run made with summary= instead; start=array gives the starts as ``map_fit`` takes them.  Further keywords
+        (maxiter, ftol, xtol) go to ``map_fit``."""
+        from . import optimize
+        if isinstance(start, str):
+            if start != "best_fit":
+                raise ValueError("start must be \"best_fit\" or an array of starts")
+            if self.summary is None:
+                raise ValueError("start=\"best_fit\" needs a run made with summary=")
+            pts = np.asarray(self.summary.best_fit[0], dtype=np.float64)
+            return optimize.map_fit(self.like, pts, nstart=1, fixed=self._fixed, **kw)
+        if start is not None:
+            return optimize.map_fit(self.like, start, fixed=self._fixed, **kw)
+        if initvals is None or initsigma is None:
+            raise ValueError("find_map needs initvals and initsigma, or start=")
+        nstart = int(nstart)
+        if not 1 <= nstart <= optimize.MAX_STARTS:
+            raise ValueError("nstart must be 1 to {:d}".format(optimize.MAX_STARTS))
+        ball = self.generate_initial_values(initvals, initsigma)
+        if ball.shape[0] < nstart:
+            raise ValueError("nstart is larger than the number of walkers")
+        pts = np.broadcast_to(ball[:nstart], (self.like.nsources, nstart, 5))
+        return optimize.map_fit(self.like, pts, nstart=nstart, fixed=self._fixed, squeeze=self.like.nsources == 1, **kw)
+
+    def map_initial_values(self, mapfit, initsigma, scale=1.0):
+        """Starting positions [nsources, nwalkers, 5] ([nwalkers, 5] for one source) from a ``MapFit``: per source a
+        Gaussian ball around that source's optimum.  Per parameter the width is min(scale x Laplace sigma, initsigma),
+        and initsigma where the Laplace sigma is NaN (a parameter on its lower limit, a singular curvature).  Every
+        walker respects the limits by ``generate_initial_values``'s rejection rule; a fixed parameter gets no scatter.
+        A source whose fit failed (START_INVALID) gets the plain ball around its start, and a warning says so."""
+        import warnings
+        sigma0 = np.array(initsigma, dtype=np.float64)
+        if sigma0.shape != (5,):
+            raise ValueError("Initial sigma values not expected length")
+        params = np.atleast_2d(mapfit.params)
+        lap = np.atleast_2d(mapfit.sigma)
+        failed = np.atleast_1d(mapfit.failed)
+        out = np.empty((params.shape[0], self._nwalkers, 5))
+        for s in range(params.shape[0]):
+            with np.errstate(invalid="ignore"):
+                width = np.where(np.isfinite(lap[s]) & (lap[s] > 0), np.minimum(float(scale) * lap[s], sigma0), sigma0)
+            if failed[s]:
+                warnings.warn("the MAP fit of source {:d} failed (START_INVALID): its walkers start from the plain ball "
+                              "around its start".format(s))
+                width = sigma0
+            out[s] = self.generate_initial_values(params[s], width)
+        return out if np.ndim(mapfit.params) > 1 else out[0]
+
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
     def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None,
             draws=None, goodness=None):

@@ -58,6 +58,10 @@ def build_parser():
                    help="goodness of fit from the chain on the device (needs --sampler device): chisq of every entry "
                         "against the data, the posterior predictive p-value, DIC and the maximum-likelihood entry "
                         "printed, and added to the .npz as goodness_*")
+    p.add_argument("--map-init", dest="map_init", type=int, nargs="?", const=8, default=0, metavar="NSTART",
+                   help="find the maximum of the posterior on the device first, from NSTART (default 8) points of the "
+                        "initial ball: the optimum with its Laplace errors is printed and added to the .npz as map_*, and "
+                        "the walkers start from a ball around it no wider than the Laplace errors")
     p.add_argument("--draws", type=int, default=0, metavar="N",
                    help="draw N cells of the chain on the device (parameters, lnprob, walker and step; with "
                         "--get_peaklambda the peak wavelength too; needs --sampler device): printed, and added to the "
@@ -114,7 +118,14 @@ def main(argv=None):
         fit.set_gaussian_prior("lambda_peak", a.priorLambdaPeak[0], a.priorLambdaPeak[1])
 
     p0init = np.array([getattr(a, "init" + nm) for nm in NAMES])
-    p0 = fit.generate_initial_values(p0init, np.array([2, 0.2, 100, 0.3, 5.0]))   # :285-291
+    initsigma = np.array([2, 0.2, 100, 0.3, 5.0])
+    mapfit = None
+    if a.map_init:
+        mapfit = fit.find_map(p0init, initsigma, nstart=a.map_init)
+        print(mapfit)
+        p0 = fit.map_initial_values(mapfit, initsigma)
+    else:
+        p0 = fit.generate_initial_values(p0init, initsigma)   # :285-291
     summary = None
     if a.summary:
         summary = dict(percentile=(68.3, 95.4), derived=("peaklambda",) if a.get_peaklambda else ())
@@ -136,6 +147,8 @@ def main(argv=None):
                parnames=np.array(NAMES), noalpha=a.noalpha, opthin=a.opthin, wavenorm=a.wavenorm,
                data_wave=fit.like.data_wave, data_flux=fit.like.data_flux,
                data_flux_unc=fit.like.data_flux_unc)
+    if mapfit is not None:
+        out.update(mapfit.arrays())
     if a.get_peaklambda:
         out["peaklambda"] = postprocess.peak_wavelength(fit.like, chain)
     if a.summary:
