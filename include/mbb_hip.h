@@ -552,6 +552,68 @@ typedef struct mbb_map_out {
 } mbb_map_out;
 int mbb_map_fit(mbb_ctx *ctx, const mbb_map_spec *spec, const mbb_map_out *out);
 
+/* ---- the evidence of a chain: bridge-sampled ln Z per source ---- */
+/* New: the reference has nothing comparable.  Z is the integral of what like(theta) returns -- likelihood x hard lower
+ * limits x soft upper walls x Gaussian priors, unnormalised -- over the free parameters: every parameter but the
+ * caller's fixed ones, lambda0 of an optically thin model, alpha of a model without one, and any whose column is
+ * constant over the window (min == max; what a stretch move started with zero scatter leaves).  Such a parameter is
+ * HELD at the value of the chain's first window cell.  Meng & Wong's optimal bridge with a Gaussian proposal, the
+ * recipe of Gronau et al. 2017 (csrc/mbb_evidence.hip.h; the step logic is csrc/mbb_bridge.hip.h):
+ *   window     of the nkept kept steps (burn, burn + thin, ...) the first nfit = nkept / 2 of every walker fit the
+ *              proposal: mean and covariance (ddof = 1) of the five columns.  The other nkept - nfit of every walker
+ *              are the posterior samples; those whose lnprob is NaN or +-inf are left out, n1 are used.
+ *   proposal   draw i of source s: three Philox4x32-10 blocks at counter (i, first_source + s, 0x42524447, 0..2),
+ *              key = seed; word pairs (0,1) .. (8,9) give five k of 53 bits, u = (k + 1/2) 2^-53, z = PPND16(u)
+ *              (Wichura's AS 241), theta = mean + L z over the free set.  lnP of the draws is mbb_lnlike_batch_device's,
+ *              bit for bit; a draw below a lower limit has lnP = -inf and contributes nothing, which is correct: the
+ *              proposal is normalised over the whole space.  n2 draws per source (0: as many as posterior samples).
+ *   ln l       ln l1_j = lnprob_j - lnq(theta*_j) at the posterior samples, ln l2_i = lnP(theta~_i) - lnq(theta~_i) at
+ *              the draws; l* is the mean of the ln l1 used.
+ *   weights    n1e = neff[s] clamped to [1, n1] when given, otherwise n1; s1 = n1e / (n1e + n2), s2 = n2 / (n1e + n2).
+ *   iteration  rho_0 = 1, rho <- [mean_i l2_i / (s1 l2_i + s2 rho)] / [mean_j 1 / (s1 l1_j + s2 rho)] with l shifted
+ *              by l*; it stops when |rho_new - rho| <= tol rho_new (MBB_EV_CONVERGED) or after maxiter iterations
+ *              (MBB_EV_MAXITER).  lnz = ln rho + l*.
+ *   error      lnz_err = sqrt(RE^2), RE^2 = Var(f1) / (n2 mean(f1)^2) + Var(f2) / (n1e mean(f2)^2) with
+ *              f1 = p / (s1 p + s2) over the draws, f2 = 1 / (s1 p + s2) over the posterior samples, p = l / z
+ *              (Fruehwirth-Schnatter 2004).  Dividing by n1e stands in for the spectral-density term of the original
+ *              formula: the caller says how many independent samples the n1 correlated ones are worth.
+ * A source's result has the same bits whatever other sources the call holds (first_source names it among them).
+ * Refused with MBB_ERR_ARG: fewer than 2 kept steps, n2 < 0 or above 2^22, tol not finite or negative, maxiter
+ * outside 1 .. 100000, a neff that is not finite or not positive.  MBB_ERR_STATE without bands or data, and for a
+ * context that is one rank of a sharded run.  nsrc is the context's, or the context holds one source for all. */
+#define MBB_EV_MAX_N2 (1 << 22)
+#define MBB_EV_MAX_ITER 100000
+enum mbb_evidence_status {
+    MBB_EV_CONVERGED = 1,
+    MBB_EV_MAXITER = 2,
+    MBB_EV_COV_SINGULAR = 4,      /* the covariance has no Cholesky factor; lnz is NaN                            */
+    MBB_EV_POST_LEFT_OUT = 8,     /* some posterior cells were not finite and excluded                            */
+    MBB_EV_NO_OVERLAP = 16,       /* no proposal draw has finite lnP; lnz is NaN                                  */
+    MBB_EV_ALL_HELD = 32,         /* no free parameter: lnz is the lnprob of the first window cell, error 0       */
+    MBB_EV_HELD_SHIFT = 8         /* bit 8 + i: parameter i was held                                              */
+};
+typedef struct mbb_evidence_spec {
+    int32_t burn, thin, n2, maxiter, first_source, fixed[5];
+    double tol;
+    uint64_t seed;
+    const double *neff;                    /* [nsrc] or NULL                                                  */
+} mbb_evidence_spec;
+/* Where the results go: host memory of the caller's.  prop, prop_lnprob, prop_lnq and post_lnq may be NULL.  N1 is
+ * nw (nkept - nkept / 2), N2 the draws per source. */
+typedef struct mbb_evidence_out {
+    double *lnz, *lnz_err;                 /* [nsrc]                                                          */
+    int32_t *niter, *status;               /* [nsrc]                                                          */
+    int64_t *n1, *n2_inside;               /* [nsrc]: posterior cells used; draws of finite lnP               */
+    double *prop_mean;                     /* [nsrc][5]                                                       */
+    double *prop_cov;                      /* [nsrc][5][5], NaN in held rows and columns                      */
+    double *prop;                          /* [nsrc][N2][5] or NULL                                           */
+    double *prop_lnprob, *prop_lnq;        /* [nsrc][N2] or NULL                                              */
+    double *post_lnq;                      /* [nsrc][N1] or NULL                                              */
+} mbb_evidence_out;
+int mbb_chain_evidence(mbb_ctx *ctx, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                       const mbb_evidence_spec *spec, const mbb_evidence_out *out);
+int mbb_sampler_evidence(mbb_ctx *ctx, void *sampler, const mbb_evidence_spec *spec, const mbb_evidence_out *out);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

@@ -19,10 +19,12 @@ from .predict import chain_predictions, ChainPredictions
 from .draws import chain_draws, draw_indices, ChainDraws
 from .goodness import chain_goodness, ChainGoodness
 from .optimize import map_fit, MapFit
+from .evidence import chain_evidence, ChainEvidence
 
 __version__ = "0.1.0"
 __all__ = ["response", "response_set", "modified_blackbody", "alpha_merge_eqn", "isiterable", "likelihood",
            "EnsembleSampler", "DeviceEnsembleSampler", "mbb_fitter", "chain_summary", "ChainSummary",
            "chain_diagnostics", "ChainDiagnostics", "chain_marginals", "ChainMarginals",
            "chain_predictions", "ChainPredictions", "chain_draws", "draw_indices", "ChainDraws",
-           "chain_goodness", "ChainGoodness", "map_fit", "MapFit"]
+           "chain_goodness", "ChainGoodness", "map_fit", "MapFit",
+           "chain_evidence", "ChainEvidence"]

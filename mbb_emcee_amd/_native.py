@@ -124,6 +124,27 @@ class MapOut(C.Structure):
                 ("params_all", _dp), ("status_all", _ip)]
 
 
+EV_MAX_N2, EV_MAX_ITER = 1 << 22, 100000
+EV_CONVERGED, EV_MAXITER, EV_COV_SINGULAR, EV_POST_LEFT_OUT, EV_NO_OVERLAP, EV_ALL_HELD = 1, 2, 4, 8, 16, 32
+EV_HELD_SHIFT = 8
+
+
+class EvidenceSpec(C.Structure):
+    """mbb_evidence_spec (include/mbb_hip.h)"""
+    _fields_ = [("burn", C.c_int32), ("thin", C.c_int32), ("n2", C.c_int32), ("maxiter", C.c_int32),
+                ("first_source", C.c_int32), ("fixed", C.c_int32 * 5), ("tol", C.c_double), ("seed", C.c_uint64),
+                ("neff", C.POINTER(C.c_double))]
+
+
+class EvidenceOut(C.Structure):
+    """mbb_evidence_out (include/mbb_hip.h)"""
+    _fields_ = [("lnz", C.POINTER(C.c_double)), ("lnz_err", C.POINTER(C.c_double)), ("niter", C.POINTER(C.c_int32)),
+                ("status", C.POINTER(C.c_int32)), ("n1", C.POINTER(C.c_int64)), ("n2_inside", C.POINTER(C.c_int64)),
+                ("prop_mean", C.POINTER(C.c_double)), ("prop_cov", C.POINTER(C.c_double)),
+                ("prop", C.POINTER(C.c_double)), ("prop_lnprob", C.POINTER(C.c_double)),
+                ("prop_lnq", C.POINTER(C.c_double)), ("post_lnq", C.POINTER(C.c_double))]
+
+
 DRAWS_MAX = 1 << 24
 DRAWS_RANDOM, DRAWS_EVEN = 0, 1
 
@@ -182,6 +203,9 @@ SIGNATURES = {
     "mbb_sampler_goodness": (C.c_int, [_vp, _vp, C.POINTER(GoodnessSpec), C.POINTER(GoodnessOut)]),
     "mbb_goodness_rows": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _ip, _dp]),
     "mbb_map_fit": (C.c_int, [_vp, C.POINTER(MapSpec), C.POINTER(MapOut)]),
+    "mbb_chain_evidence": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(EvidenceSpec),
+                                     C.POINTER(EvidenceOut)]),
+    "mbb_sampler_evidence": (C.c_int, [_vp, _vp, C.POINTER(EvidenceSpec), C.POINTER(EvidenceOut)]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -36,6 +36,7 @@
 #include "mbb_predict.hip.h"
 #include "mbb_goodness.hip.h"
 #include "mbb_map.hip.h"
+#include "mbb_evidence.hip.h"
 #include "mbb_draws.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
@@ -347,6 +348,7 @@ struct mbb_ctx {
         DevBuf start, outbuf;
         size_t lds_granted[8] = {};           // whether this context has asked for the dynamic-LDS ceiling, by instantiation of k_map_lm
     } map;
+    struct EvWork { DevBuf mom, ints, slab, l1, l2, postq, neff, outbuf; } ev;  // the evidence of a chain (evidence_run)
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -3491,6 +3493,169 @@ extern "C" int mbb_map_fit(mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out
     // the picked points through the goodness of fit's own path: its chisq, q and band fluxes
     std::vector<int32_t> gst((size_t)nsrc);
     return mbb_goodness_rows(c, picked.data(), nsrc, o->chisq, o->q, gst.data(), o->model_flux);
+}
+
+// ---- the evidence of a chain (mbb_evidence.hip.h) ------------------------------
+static_assert(mbbev::kMaxN2 == MBB_EV_MAX_N2 && mbbev::kMaxIter == MBB_EV_MAX_ITER, "the header's limits are the kernels'");
+static_assert(mbbev::kConverged == MBB_EV_CONVERGED && mbbev::kMaxIterHit == MBB_EV_MAXITER &&
+              mbbev::kCovSingular == MBB_EV_COV_SINGULAR && mbbev::kPostLeftOut == MBB_EV_POST_LEFT_OUT &&
+              mbbev::kNoOverlap == MBB_EV_NO_OVERLAP && mbbev::kAllHeld == MBB_EV_ALL_HELD &&
+              mbbev::kHeldShift == MBB_EV_HELD_SHIFT, "the header's status bits are the kernels'");
+static long long ev_kept_steps(const mbb_evidence_spec *sp, int nsteps)
+{
+    return ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
+}
+
+// The argument checks of an evidence call: before anything is allocated, uploaded or launched.
+static int ev_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_evidence_spec *sp, const mbb_evidence_out *o)
+{
+    if (!sp || !o || !o->lnz || !o->lnz_err || !o->niter || !o->status || !o->n1 || !o->n2_inside || !o->prop_mean ||
+        !o->prop_cov)
+        return fail(MBB_ERR_ARG, "null evidence argument");
+    if ((c->comm != nullptr && c->nranks > 1) || (c->x.connected && c->x.n > 1))
+        return fail(MBB_ERR_STATE, "a sharded context cannot estimate an evidence: a rank holds only its own walkers' chain");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    int rc;
+    if ((rc = good_check_ctx(c, nsrc))) return rc;
+    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    const long long nkept = ev_kept_steps(sp, nsteps);
+    if (nkept < 2) return fail(MBB_ERR_ARG, "an evidence needs two kept steps at least: one half fits the proposal, the other is bridged to");
+    if (sp->n2 < 0 || sp->n2 > MBB_EV_MAX_N2) return fail(MBB_ERR_ARG, "0 to 2^22 proposal draws per source");
+    if ((long long)nw * nkept > 0x7fffffffll) return fail(MBB_ERR_ARG, "more than 2^31 - 1 samples per source");
+    if (sp->n2 == 0 && (long long)nw * (nkept - nkept / 2) > MBB_EV_MAX_N2)
+        return fail(MBB_ERR_ARG, "n2 = 0 asks for as many draws as posterior samples: more than 2^22, name n2");
+    if (!(sp->tol >= 0.0 && sp->tol <= 1.7976931348623157e308)) return fail(MBB_ERR_ARG, "tol must be finite and not negative");
+    if (sp->maxiter < 1 || sp->maxiter > MBB_EV_MAX_ITER) return fail(MBB_ERR_ARG, "1 to 100000 iterations per evidence");
+    if (sp->first_source < 0) return fail(MBB_ERR_ARG, "first_source must not be negative");
+    if ((size_t)nsrc > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    if (sp->neff)
+        for (int s = 0; s < nsrc; ++s)
+            if (!(sp->neff[s] > 0.0 && sp->neff[s] <= 1.7976931348623157e308))
+                return fail(MBB_ERR_ARG, "neff must be finite and positive");
+    return MBB_OK;
+}
+
+// The evidence of a chain that is on the device in emcee's layout, with its lnprob.  Synchronous; the results land in
+// the caller's arrays.
+static int evidence_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
+                        const mbb_evidence_spec *sp, const mbb_evidence_out *o)
+{
+    using namespace mbbev;
+    int rc;
+    if ((rc = ev_check(c, nsrc, nw, nsteps, sp, o))) return rc;
+    if (!d_lnprob) return fail(MBB_ERR_ARG, "an evidence needs the chain's lnprob");
+    EvArgs a;
+    memset(&a, 0, sizeof a);
+    a.chain = d_chain; a.lnprob = d_lnprob;
+    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
+    a.nkept = (int)ev_kept_steps(sp, nsteps);
+    a.n = (long long)nw * a.nkept;
+    a.nfit = a.nkept / 2; a.n1k = a.nkept - a.nfit;
+    a.n1max = (long long)nw * a.n1k;
+    a.n2 = sp->n2 ? sp->n2 : (int)a.n1max;
+    // (mbblm::lm_fixed_mask, a device function in this build: the caller's, lambda0 of a thin model, alpha without one)
+    for (int i = 0; i < 5; ++i) if (sp->fixed[i]) a.fixed |= 1u << i;
+    if (c->opthin) a.fixed |= 1u << 2;
+    if (c->noalpha) a.fixed |= 1u << 3;
+    a.first_source = sp->first_source; a.seed = sp->seed; a.tol = sp->tol; a.maxiter = sp->maxiter;
+    const size_t ns = (size_t)nsrc, n1 = (size_t)a.n1max, n2 = (size_t)a.n2;
+    // a slab: draws [k m, (k + 1) m) of every source, [nsrc][m][5] -- the likelihood's multi-source row grouping
+    const size_t m = std::min<size_t>(n2, std::max<size_t>(1, (size_t)kSumChunkRows / ns));
+    const size_t srows = ns * m;
+    mbb_ctx::EvWork &w = c->ev;
+    const size_t out_bytes = ns * (2 * sizeof(long long) + 2 * sizeof(double) + sizeof(int));
+    if ((rc = grow(c, w.mom, ns * kMomWords * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.ints, ns * 2 * sizeof(int)))) return rc;
+    if ((rc = grow(c, w.slab, srows * (7 * sizeof(double) + sizeof(int32_t))))) return rc;
+    if ((rc = grow(c, w.l1, ns * n1 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.l2, ns * n2 * sizeof(double)))) return rc;
+    if (o->post_lnq && (rc = grow(c, w.postq, ns * n1 * sizeof(double)))) return rc;
+    if (sp->neff && (rc = grow(c, w.neff, ns * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    a.mom = (double *)w.mom.p;
+    a.free_ = (int *)w.ints.p; a.status = a.free_ + ns;
+    a.l1 = (double *)w.l1.p; a.l2 = (double *)w.l2.p;
+    a.post_lnq = o->post_lnq ? (double *)w.postq.p : nullptr;
+    Carve sb{(char *)w.slab.p};
+    a.s_rows = sb.take<double>(srows * 5); a.s_lnq = sb.take<double>(srows);
+    double *const s_lnl = sb.take<double>(srows);
+    int32_t *const s_status = sb.take<int32_t>(srows);
+    a.s_lnl = s_lnl;
+    Carve ob{(char *)w.outbuf.p};
+    a.o_n1 = ob.take<long long>(ns); a.o_inside = ob.take<long long>(ns);
+    a.o_lnz = ob.take<double>(ns); a.o_err = ob.take<double>(ns);
+    a.o_niter = ob.take<int>(ns);
+    if (sp->neff) {
+        // (a pageable source: the copy has read it when it returns)
+        HIPCHK(hipMemcpyAsync(w.neff.p, sp->neff, ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        a.neff = (const double *)w.neff.p;
+    }
+    hipLaunchKernelGGL(k_ev_moments, dim3((unsigned)nsrc), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_ev_factor, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(k_ev_post, dim3((unsigned)((ns * n1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    for (size_t i0 = 0; i0 < n2; i0 += m) {
+        const size_t mm = std::min(m, n2 - i0), rows = ns * mm;
+        a.i0 = (int)i0; a.m = (int)mm;
+        const dim3 grid((unsigned)((rows + kThreads - 1) / kThreads));
+        hipLaunchKernelGGL(k_ev_propose, grid, dim3(kThreads), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_rows(c, a.s_rows, (int)rows, s_lnl, s_status, nullptr))) return rc;
+        hipLaunchKernelGGL(k_ev_l2, grid, dim3(kThreads), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+        // the slab's rows, lnP and lnq into the caller's [nsrc][N2] arrays where asked for
+        if (o->prop)
+            HIPCHK(hipMemcpy2DAsync(o->prop + i0 * 5, n2 * 5 * sizeof(double), a.s_rows, mm * 5 * sizeof(double),
+                                    mm * 5 * sizeof(double), ns, hipMemcpyDeviceToHost, c->stream));
+        if (o->prop_lnprob)
+            HIPCHK(hipMemcpy2DAsync(o->prop_lnprob + i0, n2 * sizeof(double), s_lnl, mm * sizeof(double),
+                                    mm * sizeof(double), ns, hipMemcpyDeviceToHost, c->stream));
+        if (o->prop_lnq)
+            HIPCHK(hipMemcpy2DAsync(o->prop_lnq + i0, n2 * sizeof(double), a.s_lnq, mm * sizeof(double),
+                                    mm * sizeof(double), ns, hipMemcpyDeviceToHost, c->stream));
+        if (o->prop || o->prop_lnprob || o->prop_lnq) HIPCHK(hipStreamSynchronize(c->stream));   // (before the slab is reused)
+    }
+    hipLaunchKernelGGL(k_ev_bridge, dim3((unsigned)nsrc), dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    std::vector<char> host(out_bytes);
+    std::vector<double> mom(ns * kMomWords);
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(mom.data(), w.mom.p, mom.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(o->status, a.status, ns * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (o->post_lnq)
+        HIPCHK(hipMemcpyAsync(o->post_lnq, w.postq.p, ns * n1 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Carve hb{host.data()};
+    hb.put((long long *)o->n1, ns); hb.put((long long *)o->n2_inside, ns);
+    hb.put(o->lnz, ns); hb.put(o->lnz_err, ns);
+    hb.put(o->niter, ns);
+    for (size_t s = 0; s < ns; ++s) {
+        memcpy(o->prop_mean + s * 5, &mom[s * kMomWords + kMomMean], 5 * sizeof(double));
+        memcpy(o->prop_cov + s * 25, &mom[s * kMomWords + kMomCov], 25 * sizeof(double));
+    }
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_evidence(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                                  const mbb_evidence_spec *spec, const mbb_evidence_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!chain || !lnprob) return fail(MBB_ERR_ARG, "bad arguments: an evidence needs the chain and its lnprob");
+    if ((rc = ev_check(c, nsrc, nw, nsteps, spec, out))) return rc;        // (before the chain is uploaded)
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
+        return evidence_run(c, d, d + cells * 5, nsrc, nw, nsteps, spec, out);
+    });
+}
+
+extern "C" int mbb_sampler_evidence(mbb_ctx *c, void *sp, const mbb_evidence_spec *spec, const mbb_evidence_out *out)
+{
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, spec && out, "bridged to an evidence", s)) || (rc = resident_chain(s))) return rc;
+    const size_t cells = (size_t)s->rows() * s->resident_nsteps;
+    return evidence_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

@@ -98,7 +98,7 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_`` or ``predictions_``, nothing resident for ``convergence()`` or
+        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_``, ``evidence_`` or ``predictions_``, nothing resident for ``convergence()`` or
         ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
@@ -120,6 +120,7 @@ class DeviceEnsembleSampler(object):
         self.marginals_ = None
         self.draws_ = None
         self.goodness_ = None
+        self.evidence_ = None
         self._drop_predictions()
         self._resident = 0                    # steps of the last run's chain that are resident on the device
         if self._h is not None:
@@ -229,6 +230,34 @@ class DeviceEnsembleSampler(object):
         _native.check_arg(ctx.lib.mbb_sampler_goodness(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return goodness.ChainGoodness(req, raw, self.nsources > 1, cens[0], self.k, nkept)
 
+    def evidence(self, n2=None, fixed=None, neff="auto", seed=None, burn=0, thin=1, tol=None, maxiter=None, keep=False):
+        """``evidence.ChainEvidence`` (bridge-sampled ln Z per source with its error) of the chain the last run left on
+        the device -- a run with storechain=True or with summary= --; the keywords are ``evidence.chain_evidence``'s,
+        ``seed`` defaulting to the sampler's.  neff="auto" takes the smallest ess over the free parameters from
+        ``convergence()`` of the bridged half of the window (of all its steps: with thin > 1 that is an upper bound,
+        and the count is clamped to the number of samples).  No chain crosses the bus."""
+        from . import evidence
+        req = evidence._Request(self.lnprobfn, n2, fixed, self.seed if seed is None else seed, burn, thin,
+                                evidence.TOL if tol is None else tol, evidence.MAXITER if maxiter is None else maxiter,
+                                0, keep)
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: evidence() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset")
+        nkept, nfit = req.check_steps(self._resident)
+        n1 = self.k * (nkept - nfit)
+        if isinstance(neff, str):
+            if neff != "auto":
+                raise ValueError("neff must be 'auto', None, a number or one number per source")
+            dg = self.convergence(burn=req.burn + nfit * req.thin)
+            req.set_neff(req.neff_from_ess(dg.ess, dg.status, n1), self.nsources)
+        else:
+            req.set_neff(neff, self.nsources)
+        ctx, h = self._handle()
+        raw = evidence._Raw(self.nsources, n1, req.n2 or n1, req.keep)
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(ctx.lib.mbb_sampler_evidence(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return evidence.ChainEvidence(req, raw, self.nsources > 1, self.k, nkept)
+
     def predictions(self, specs, percentile=68.3, percentiles=(), burn=0, thin=1, clip=None, wavenorm=None, keep=True):
         """``predict.ChainPredictions`` (predicted fluxes at wavelengths and through passbands, ``predflux_cen``) of the
         chain the last run left on the device -- a run with storechain=True or with summary= --; the arguments are
@@ -271,7 +300,7 @@ class DeviceEnsembleSampler(object):
         return raw
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
-                 marginals=None, predict=None, draws=None, goodness=None, **unused):
+                 marginals=None, predict=None, draws=None, goodness=None, evidence=None, **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -320,9 +349,14 @@ class DeviceEnsembleSampler(object):
         goodness=True, or a dict of ``goodness()``'s keywords: the chain of this run is held against the data on the
         device and ``sampler.goodness_`` is the ``goodness.ChainGoodness`` of it (None again after reset() and at the
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
+        with summary=.
+
+        evidence=True, or a dict of ``evidence()``'s keywords: ln Z of the chain of this run is bridge-sampled on the
+        device and ``sampler.evidence_`` is the ``evidence.ChainEvidence`` of it (None again after reset() and at the
+        start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
         with summary=."""
         self._retire()
-        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws, goodness)
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws, goodness, evidence)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
@@ -342,8 +376,9 @@ class DeviceEnsembleSampler(object):
             self._resident = 0                # (what is resident is the last chunk: a part)
 
     def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None, predict=None,
-             draws=None, goodness=None):
-        creq = mkw = pkw = dkw = gkw = None
+             draws=None, goodness=None, evidence=None):
+        creq = mkw = pkw = dkw = gkw = ekw = None
+        self.evidence_ = None
         self.convergence_ = None
         self.marginals_ = None
         self.draws_ = None
@@ -385,6 +420,27 @@ class DeviceEnsembleSampler(object):
                 raise ValueError("goodness= with storechain=False needs summary= too: a run that neither stores "
                                  "nor summarises its chain keeps none on the device")
             greq.check_steps(int(N))
+        if evidence is not None and evidence is not False:
+            from . import evidence as _evidence
+            ekw = {} if evidence is True else dict(evidence)
+            if summary is not None and summary is not False and summary is not True:
+                for key in ("burn", "thin"):
+                    if key in summary:
+                        ekw.setdefault(key, summary[key])
+            unknown = set(ekw) - {"n2", "fixed", "neff", "seed", "burn", "thin", "tol", "maxiter", "keep"}
+            if unknown:
+                raise TypeError("evidence= got unexpected keyword(s) {}".format(sorted(unknown)))
+            ereq = _evidence._Request(self.lnprobfn, ekw.get("n2"), ekw.get("fixed"), ekw.get("seed", self.seed),
+                                      ekw.get("burn", 0), ekw.get("thin", 1), ekw.get("tol", _evidence.TOL),
+                                      ekw.get("maxiter", _evidence.MAXITER))
+            if not storechain and (summary is None or summary is False):
+                raise ValueError("evidence= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device")
+            ereq.check_steps(int(N))
+            if not isinstance(ekw.get("neff", "auto"), str):
+                ereq.set_neff(ekw["neff"], self.nsources)
+            elif ekw.get("neff", "auto") != "auto":
+                raise ValueError("neff must be 'auto', None, a number or one number per source")
         if marginals is not None and marginals is not False:
             from . import marginals as _marginals
             mkw = {} if marginals is True else dict(marginals)
@@ -431,6 +487,9 @@ class DeviceEnsembleSampler(object):
         if gkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be tested for goodness of fit on the device: a rank holds "
                              "only its own walkers' chain")
+        if ekw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be bridged to an evidence on the device: a rank holds only "
+                             "its own walkers' chain")
         if dkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be drawn from on the device: a rank holds only its own "
                              "walkers' chain")
@@ -534,6 +593,8 @@ class DeviceEnsembleSampler(object):
             self.draws_ = self.draws(**dkw)
         if gkw is not None:
             self.goodness_ = self.goodness(**gkw)
+        if ekw is not None:
+            self.evidence_ = self.evidence(**ekw)
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):

@@ -190,7 +190,7 @@ class mbb_fitter(object):
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
     def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None,
-            draws=None, goodness=None):
+            draws=None, goodness=None, evidence=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
@@ -206,7 +206,12 @@ class mbb_fitter(object):
         among them) -- cells drawn from the main chain with their derived values, ``mbb_fitter.draws``.
         goodness (device sampler only): True or a dict of ``goodness.chain_goodness``'s keywords -- the main chain's
         chisq against the data, posterior predictive p-value, DIC and maximum-likelihood entry,
-        ``mbb_fitter.goodness``."""
+        ``mbb_fitter.goodness``.
+        evidence (device sampler only): True or a dict of ``evidence.chain_evidence``'s keywords -- the main chain's
+        bridge-sampled ln Z per source, ``mbb_fitter.evidence``; the fitter's own fixed parameters are passed on as
+        ``fixed`` unless the dict names others."""
+        if evidence is not None and evidence is not False and not hasattr(self.sampler, "evidence"):
+            raise ValueError("evidence= needs sampler=\"device\"")
         if goodness is not None and goodness is not False and not hasattr(self.sampler, "goodness"):
             raise ValueError("goodness= needs sampler=\"device\"")
         if draws is not None and draws is not False and not hasattr(self.sampler, "draws"):
@@ -263,6 +268,10 @@ class mbb_fitter(object):
             extra["draws"] = draws
         if goodness is not None and goodness is not False:
             extra["goodness"] = goodness
+        if evidence is not None and evidence is not False:
+            ekw = {} if evidence is True else dict(evidence)
+            ekw.setdefault("fixed", [bool(f) for f in self._fixed])
+            extra["evidence"] = ekw
         self.sampler.run_mcmc(pos, nsteps, rstate0=rstate, **extra)
         self._sampled = True
 
@@ -308,6 +317,8 @@ mbb_fitter.predictions = property(lambda self: getattr(self.sampler, "prediction
                                   doc="predict.ChainPredictions of the main chain when run() was given predict=, else None")
 mbb_fitter.goodness = property(lambda self: getattr(self.sampler, "goodness_", None),
                                doc="goodness.ChainGoodness of the main chain when run() was given goodness=, else None")
+mbb_fitter.evidence = property(lambda self: getattr(self.sampler, "evidence_", None),
+                               doc="evidence.ChainEvidence of the main chain when run() was given evidence=, else None")
 mbb_fitter.draws = property(lambda self: getattr(self.sampler, "draws_", None),
                             doc="draws.ChainDraws from the main chain when run() was given draws=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,

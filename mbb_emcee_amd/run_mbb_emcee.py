@@ -58,6 +58,10 @@ def build_parser():
                    help="goodness of fit from the chain on the device (needs --sampler device): chisq of every entry "
                         "against the data, the posterior predictive p-value, DIC and the maximum-likelihood entry "
                         "printed, and added to the .npz as goodness_*")
+    p.add_argument("--evidence", type=int, nargs="?", const=-1, default=None, metavar="N2",
+                   help="the evidence ln Z of the fit, bridge-sampled from the chain on the device with N2 proposal draws "
+                        "(default: as many as posterior samples; needs --sampler device): printed, and added to the "
+                        ".npz as evidence_*")
     p.add_argument("--map-init", dest="map_init", type=int, nargs="?", const=8, default=0, metavar="NSTART",
                    help="find the maximum of the posterior on the device first, from NSTART (default 8) points of the "
                         "initial ball: the optimum with its Laplace errors is printed and added to the .npz as map_*, and "
@@ -139,6 +143,8 @@ def main(argv=None):
         extra["predict"] = parse_predict(a.predict)
     if a.goodness:
         extra["goodness"] = True
+    if a.evidence is not None:
+        extra["evidence"] = dict(n2=None if a.evidence < 0 else a.evidence)
     if a.draws:
         extra["draws"] = dict(n=a.draws, derived=("peaklambda",) if a.get_peaklambda else ())
     fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary, **extra)
@@ -166,6 +172,9 @@ def main(argv=None):
     if a.goodness:
         out.update(fit.goodness.arrays())
         print(fit.goodness)
+    if a.evidence is not None:
+        out.update(fit.evidence.arrays())
+        print(fit.evidence)
     if a.draws:
         out.update(fit.draws.arrays())
         print(fit.draws)
