@@ -1,6 +1,6 @@
 // _device_probe.hip -- test-only entry points onto the device functions of mbb_math.hip.h,
-// mbb_device.hip.h and mbb_stretch.hip.h (tests/test_device_math_gpu.py, tests/test_device_math_cpu.py,
-// tests/test_sampler_statistics_gpu.py).  Never part of the
+// mbb_device.hip.h, mbb_stretch.hip.h and mbb_gammq.hip.h (tests/test_device_math_gpu.py, tests/test_device_math_cpu.py,
+// tests/test_sampler_statistics_gpu.py, tests/test_goodness_gpu.py).  Never part of the
 // product library: tests/_device_probe.py compiles it, together with csrc/mbb_host_tables.cpp (the
 // builder of the polynomial tables the product uploads), into tests/device_probe/libmbb_device_probe.so with the
 // product's own device flags.
@@ -19,7 +19,15 @@
 #include "../mbb_emcee_amd/csrc/mbb_host_tables.h"
 
 enum { PROBE_OK = 0, PROBE_ERR_ARG = -1, PROBE_ERR_DOMAIN = -2, PROBE_ERR_HIP = -3 };
-enum { OP_EXP = 0, OP_EXPM1 = 1, OP_LOG = 2, OP_DIV = 3, OP_EXP_T = 4, OP_COUNT = 5 };
+enum { OP_EXP = 0, OP_EXPM1 = 1, OP_LOG = 2, OP_DIV = 3, OP_EXP_T = 4, OP_GAMMQ = 5, OP_COUNT = 6 };
+
+// OP_GAMMQ: x = chisq (anything), y = nb as a double, which must be an integer in [1, 256] (NaN fails the comparisons)
+static int gammq_domain_ok(const double *y, long n)
+{
+    for (long i = 0; i < n; ++i)
+        if (!(y[i] >= 1.0 && y[i] <= 256.0 && y[i] == (double)(int)y[i])) return 0;
+    return 1;
+}
 
 // X = 8 x must name a row of the table: [0, 8 * 48] for b, [0, 8 * 37] for C (NaN fails both comparisons)
 static int poly_domain_ok(int which, const double *X, long n)
@@ -33,18 +41,21 @@ static int poly_domain_ok(int which, const double *X, long n)
 #ifdef MBB_MATH_HOST
 // ------------------------------------------------------------------ host build
 #include "../mbb_emcee_amd/csrc/mbb_math.hip.h"
+#include "../mbb_emcee_amd/csrc/mbb_gammq.hip.h"
 
 extern "C" int probe_is_host(void) { return 1; }
 
 extern "C" int probe_math(int op, const double *x, const double *y, long n, double *out)
 {
-    if (op < 0 || op >= OP_COUNT || !x || !out || n <= 0 || (op == OP_DIV && !y)) return PROBE_ERR_ARG;
+    if (op < 0 || op >= OP_COUNT || !x || !out || n <= 0 || ((op == OP_DIV || op == OP_GAMMQ) && !y)) return PROBE_ERR_ARG;
+    if (op == OP_GAMMQ && !gammq_domain_ok(y, n)) return PROBE_ERR_DOMAIN;
     for (long i = 0; i < n; ++i) {
         switch (op) {
         case OP_EXP: out[i] = mbbm::m_exp(x[i]); break;
         case OP_EXPM1: out[i] = mbbm::m_expm1(x[i]); break;
         case OP_LOG: out[i] = mbbm::m_log(x[i]); break;
         case OP_DIV: out[i] = mbbm::m_div(x[i], y[i]); break;
+        case OP_GAMMQ: out[i] = mbbm::m_gammq_half((int)y[i], x[i]); break;
         default: out[i] = mbbm::m_exp_t(x[i], mbbm::kExp2Tab); break;
         }
     }
@@ -68,6 +79,7 @@ extern "C" int probe_poly(int which, const double *X, long n, double *out)
 
 #include "../mbb_emcee_amd/csrc/mbb_device.hip.h"
 #include "../mbb_emcee_amd/csrc/mbb_stretch.hip.h"
+#include "../mbb_emcee_amd/csrc/mbb_gammq.hip.h"
 
 using namespace mbbd;
 
@@ -119,6 +131,7 @@ __global__ void k_math(int op, const double *x, const double *y, long n, double 
     case OP_EXPM1: r = m_expm1(x[i]); break;
     case OP_LOG: r = m_log(x[i]); break;
     case OP_DIV: r = m_div(x[i], y[i]); break;
+    case OP_GAMMQ: r = mbbm::m_gammq_half((int)y[i], x[i]); break;
     default: r = m_exp_t(x[i], kExp2Tab); break;
     }
     out[i] = r;
@@ -271,12 +284,13 @@ extern "C" int probe_is_host(void) { return 0; }
 
 extern "C" int probe_math(int op, const double *x, const double *y, long n, double *out)
 {
-    if (op < 0 || op >= OP_COUNT || !x || !out || n <= 0 || (op == OP_DIV && !y)) return PROBE_ERR_ARG;
+    if (op < 0 || op >= OP_COUNT || !x || !out || n <= 0 || ((op == OP_DIV || op == OP_GAMMQ) && !y)) return PROBE_ERR_ARG;
+    if (op == OP_GAMMQ && !gammq_domain_ok(y, n)) return PROBE_ERR_DOMAIN;
     DevBuf dx, dy, dout;
     const size_t bytes = (size_t)n * sizeof(double);
     PCHK(dx.alloc(bytes)); PCHK(dy.alloc(bytes)); PCHK(dout.alloc(bytes));
     PCHK(hipMemcpy(dx.p, x, bytes, hipMemcpyHostToDevice));
-    PCHK(hipMemcpy(dy.p, op == OP_DIV ? y : x, bytes, hipMemcpyHostToDevice));
+    PCHK(hipMemcpy(dy.p, op == OP_DIV || op == OP_GAMMQ ? y : x, bytes, hipMemcpyHostToDevice));
     const int threads = 256;
     hipLaunchKernelGGL(k_math, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, 0, op,
                        dx.as<double>(), dy.as<double>(), n, dout.as<double>());

@@ -30,12 +30,12 @@ CSRC = os.path.join(ROOT, "mbb_emcee_amd", "csrc")
 SRC_TABLES = os.path.join(CSRC, "mbb_host_tables.cpp")
 DEPS = [SRC, SRC_TABLES] + [os.path.join(CSRC, f) for f in
                             ("mbb_host_tables.h", "mbb_math.hip.h", "mbb_device.hip.h", "mbb_exp2_tab.inc",
-                             "mbb_flow_index.h", "mbb_stretch.hip.h")]
+                             "mbb_flow_index.h", "mbb_stretch.hip.h", "mbb_gammq.hip.h")]
 LIBDIR = os.path.join(HERE, "device_probe")
 SO = os.path.join(LIBDIR, "libmbb_device_probe.so")
 SO_HOST = os.path.join(LIBDIR, "libmbb_device_probe_host.so")
 
-OPS = {"m_exp": 0, "m_expm1": 1, "m_log": 2, "m_div": 3, "m_exp_t": 4}
+OPS = {"m_exp": 0, "m_expm1": 1, "m_log": 2, "m_div": 3, "m_exp_t": 4, "m_gammq_half": 5}
 ERRORS = {-1: "bad arguments", -2: "an input outside the probed function's domain", -3: "HIP error"}
 
 _dp = C.POINTER(C.c_double)
@@ -109,7 +109,7 @@ class Probe(object):
 
     # ---- primitives
     def math(self, name, x, y=None, chunk=1 << 20):
-        """m_exp / m_expm1 / m_log / m_div(x, y) / m_exp_t of every element"""
+        """m_exp / m_expm1 / m_log / m_div(x, y) / m_exp_t / m_gammq_half(nb = y, chisq = x) of every element"""
         x = _f64(x).ravel()
         y = _f64(y).ravel() if y is not None else None
         assert y is None or y.shape == x.shape
@@ -122,6 +122,12 @@ class Probe(object):
                    "probe_math(%s)" % name)
             out[i:i + chunk] = o
         return out
+
+    def gammq(self, nb, chisq):
+        """m_gammq_half(nb, chisq) of csrc/mbb_gammq.hip.h: Q(nb/2, chisq/2), nb (integers in [1, 256], or the probe
+        refuses) broadcast against chisq (any double)"""
+        y, x = np.broadcast_arrays(_f64(nb), _f64(chisq))
+        return self.math("m_gammq_half", x, y).reshape(x.shape)
 
     def poly_tables(self):
         """the product's tables of b and C, rows of kPolyStride doubles (mbbh_poly_tables)"""

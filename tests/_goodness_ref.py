@@ -44,6 +44,43 @@ def q_mp(nb, chisq_value):
         return mpmath.gammainc(mpmath.mpf(nb) / 2, mpmath.mpf(x) / 2, mpmath.inf, regularized=True)
 
 
+MAX_NB = 256               # kGammqMaxNb: the orders m_gammq_half accepts are 1 .. MAX_NB
+_ORDER_TRUTH = {}
+
+
+def order_grid(nb):
+    """The 70 chisq values order nb is judged on: sixty from 1e-3 to 2999, seven around the order's own mean nb (where
+    q falls from 1 to 0 for a large order), and the edge of the range (from chisq = 3000 on the function returns 0)."""
+    x = np.unique(np.concatenate([np.geomspace(1e-3, 2999.0, 60), nb * np.array([0.25, 0.5, 0.9, 1.0, 1.1, 2.0, 4.0]),
+                                  [1416.0, 1490.0, 2999.0, 3001.0]]))
+    assert x.size == 70, (nb, x.size)
+    return x
+
+
+def order_truth(nb):
+    """(order_grid(nb), [q_mp(nb, x) for x in it], which of them are >= Q_FLOOR), computed once per session"""
+    if nb not in _ORDER_TRUTH:
+        x = order_grid(nb)
+        t = [q_mp(nb, v) for v in x]
+        _ORDER_TRUTH[nb] = (x, t, np.array([v >= Q_FLOOR for v in t]))
+    return _ORDER_TRUTH[nb]
+
+
+def horner_bound_eps(nb):
+    """The derived bound on the relative error of m_gammq_half where no library function enters (even nb on the device;
+    every nb on the host, whose erfc is the host libm's within an ulp), in units of eps: m_exp twice at 2 ulp each,
+    ceil(nb/2) Horner steps of one IEEE division and one fma at 1.5 ulp a step at the worst, three products, and two
+    for erfc and its first-order correction: 4 + 1.5 ceil(nb/2) + 3 + 2."""
+    return 9.0 + 1.5 * ((nb + 1) // 2)
+
+
+def rel_errors(truth, big, got):
+    """relative errors of got against the mpmath numbers truth, where big"""
+    import mpmath
+    with mpmath.workdps(50):
+        return np.array([float(abs(mpmath.mpf(float(g)) - t) / t) for g, t, b in zip(got, truth, big) if b])
+
+
 def q_errors(nb, chisq_values, got):
     """(relative errors of `got` where the true q >= Q_FLOOR, the values of `got` where it is below), against mpmath
     at the very doubles chisq_values."""

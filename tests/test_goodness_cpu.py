@@ -3,10 +3,14 @@ tests/_goodness_ref.py against scipy, the HOST build of csrc/mbb_gammq.hip.h aga
 quantities on hand-made raw results, the request's refusals, the ``goodness=`` rules of the sampler and the fitter on a
 faked device, and the declarations of the new entry points.
 
-Bound of the host build: relative 64 eps where the true q >= 1e-290, for nb <= 64.  Where it comes from: e^-x is
-m_exp(-x/2) applied twice, 2 ulp each (mbb_math.hip.h); the Horner sum has at most 32 steps of one division and one fma,
-all terms positive, 1.5 ulp a step at the worst; three more products; erfc of the host's libm within an ulp and its
-first-order correction for the rounding of sqrt, whose neglected second order is (x eps)^2.  4 + 48 + 3 + 2 = 57."""
+Bound of the host build, for every order 1 <= nb <= 256 the function accepts: relative (9 + 1.5 ceil(nb/2)) eps where
+the true q >= 1e-290 (_goodness_ref.horner_bound_eps), and never more than 64 eps for nb <= 64.  Where it comes from:
+e^-x is m_exp(-x/2) applied twice, 2 ulp each (mbb_math.hip.h); the Horner sum has at most ceil(nb/2) steps of one
+division and one fma, all terms positive, 1.5 ulp a step at the worst; three more products; erfc of the host's libm
+within an ulp and its first-order correction for the rounding of sqrt, whose neglected second order is (x eps)^2.
+At nb = 64: 4 + 48 + 3 + 2 = 57; at nb = 256: 4 + 192 + 3 + 2 = 201.  Every order is judged on the 70 points of
+_goodness_ref.order_grid, of which at least 60 have a true q >= 1e-290 and at least one is below (asserted); the
+orders of NBS also on _grid()."""
 import ctypes as C
 import os
 import shutil
@@ -104,19 +108,62 @@ def test_host_build_edges(host_q):
         assert np.all(np.diff(q[big]) <= 4 * GR.EPS * q[big][:-1]), nb
 
 
+def _host_bound_eps(n):
+    """(9 + 1.5 ceil(nb/2)) eps, the docstring's derivation with the step count left free; never above the 64 eps the
+    orders up to 64 have been held to"""
+    return min(64.0, GR.horner_bound_eps(n)) if n <= 64 else GR.horner_bound_eps(n)
+
+
 def test_host_build_against_mpmath(host_q):
+    """Every order the function accepts, 1 .. 256: the orders of NBS on _grid(), every order on its 70 points of
+    _goodness_ref.order_grid."""
     pytest.importorskip("mpmath")
+    assert [_host_bound_eps(n) for n in (1, 2, 64, 65, 255, 256)] == [10.5, 10.5, 57.0, 58.5, 201.0, 201.0]
     nb, x = _grid()
     got = host_q(nb, x)
-    worst = 0.0
+    worst, worst_of = 0.0, 0.0
     for n in NBS:
         sel = nb == n
         rel, low = GR.q_errors(n, x[sel], got[sel])
         assert np.all(low >= 0) and np.all(low <= 1e-289), (n, low)
         if rel.size:
             worst = max(worst, rel.max())
-            assert rel.max() <= 64 * GR.EPS, (n, rel.max(), x[sel][np.argmax(rel)])
-    print("host build of m_gammq_half against mpmath: max relative error %.3g (%.1f eps)" % (worst, worst / GR.EPS))
+            assert rel.max() <= _host_bound_eps(n) * GR.EPS, (n, rel.max(), x[sel][np.argmax(rel)])
+    for n in range(1, GR.MAX_NB + 1):
+        xs, truth, big = GR.order_truth(n)
+        assert big.sum() >= 60 and (~big).sum() >= 1, (n, big.sum())        # (the grid judges the function at this order)
+        q = host_q(n, xs)
+        rel = GR.rel_errors(truth, big, q)
+        assert np.all(q[~big] >= 0) and np.all(q[~big] <= 1e-289), (n, q[~big])
+        worst = max(worst, rel.max())
+        worst_of = max(worst_of, rel.max() / (_host_bound_eps(n) * GR.EPS))
+        assert rel.max() <= _host_bound_eps(n) * GR.EPS, (n, rel.max() / GR.EPS, xs[big][np.argmax(rel)])
+    print("host build of m_gammq_half against mpmath, orders 1 .. %d: max relative error %.3g (%.1f eps), %.3f of its bound"
+          % (GR.MAX_NB, worst, worst / GR.EPS, worst_of))
+
+
+def test_probe_op_is_the_function(host_q):
+    """The test-only probe's op for m_gammq_half (tests/_device_probe.hip, here its host build): the same bits as the
+    host build above at every order, any chisq accepted, and an order that is no integer in [1, 256] refused with the
+    probe's domain code before anything is evaluated."""
+    import _device_probe as P
+    probe = P.load_host()
+    assert P.OPS["m_gammq_half"] == 5 and len(set(P.OPS.values())) == len(P.OPS) == 6
+    assert os.path.join(P.CSRC, "mbb_gammq.hip.h") in P.DEPS               # (a change to the header rebuilds the probe)
+    inf, nan = float("inf"), float("nan")
+    x = np.concatenate([GR.order_grid(7), [0.0, -0.0, -5.0, -inf, inf, nan, 1e10, 1e300, 5e-324]])
+    orders = np.arange(1, GR.MAX_NB + 1)
+    got = probe.gammq(orders[:, None], x)
+    assert got.shape == (GR.MAX_NB, x.size)
+    assert np.array_equal(got, host_q(np.repeat(orders, x.size).reshape(got.shape), np.tile(x, (GR.MAX_NB, 1))), equal_nan=True)
+    out = np.full(1, 7.0)
+    for bad in (0.0, 257.0, 1.5, -1.0, nan, inf, 1e300):
+        y = np.array([bad])
+        assert probe.lib.probe_math(5, P._d(np.ones(1)), P._d(y), 1, P._d(out)) == -2 and out[0] == 7.0, bad
+        with pytest.raises(RuntimeError, match="domain"):
+            probe.gammq(bad, [1.0])
+    assert probe.lib.probe_math(5, P._d(np.ones(1)), None, 1, P._d(out)) == -1                # no order given
+    assert probe.lib.probe_math(6, P._d(np.ones(1)), P._d(np.ones(1)), 1, P._d(out)) == -1    # one past the last op
 
 
 # ---------------------------------------------------------------- ChainGoodness on hand-made raw results

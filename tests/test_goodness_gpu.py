@@ -14,16 +14,40 @@ Tolerances, and where they come from:
     a 1 x 1 window per entry): tests/test_predict_gpu.py's bounds -- the mean within 64 eps mean|x| of numpy's,
     percentiles within 4 ulp of numpy's inside the bracket of their two order statistics, min, max and n_used exact;
   * the band fluxes of the maximum-likelihood entry: relative 1e-12 from the oracle's (SURVEY 8c);
+  * every row's band fluxes (goodness_rows(want_flux=True)) in the band layouts of section 10: relative 1e-12 from the
+    oracle's (SURVEY 8c);
+  * q at every order 1 .. 256 through the test-only probe (section 11): on the order's 70 points
+    (_goodness_ref.order_grid; asserted: at least 60 with a true q >= 1e-290, at least one below), relative 4 x the
+    largest error scipy.special.gammaincc shows on those points; the even orders also (9 + 1.5 ceil(nb/2)) eps -- no
+    library function enters them: m_exp twice at 2 ulp each, ceil(nb/2) Horner steps of one IEEE division and one fma
+    at 1.5 ulp a step, three products (tests/test_goodness_cpu.py's derivation with the step count left free) --; the
+    odd orders have the device library's erfc, the one term whose error this project does not own, and keep the outer
+    bound only, their observed maximum recorded;
+  * the kernel's q against the probe's m_gammq_half at the kernel's own chisq: bit for bit (one header, one set of
+    device flags, no contraction: -ffp-contract=off);
   * counts, indices, status bits and everything said to be "the same bits": exact.
 The entries are every row of the fixture chains tests/test_predict_gpu.py uses (tests/golden/results.npz: 32 x 16 per
-model variant)."""
+model variant).
+
+Section 10 runs what k_good_flux, k_good_chi and their host driver branch on (LAYOUTS): one-sample and many-sample
+bands in one launch, many-sample bands shorter than a wave, samples read from global memory (STAGE = false) and the
+2560 / 2561 seam of that decision, C^-1 in LDS and in global memory at 64 / 65 bands, kMaxBands = 256 bands with and
+without a covariance, row counts off the wave and the workgroup, failing rows at their ends, several sources beyond the
+seams, the row-chunk loop of mbb_goodness_rows, and the refusal at 257 bands.  The uncertainty scales of each case were
+chosen on the CPU with the oracle alone (LAYOUT_SCALES); what they have to achieve is asserted.
+
+The MAP fit reports these functions' values: tests/test_map_gpu.py asserts MapFit.chisq, q and model_flux bit for bit
+equal to mbb_goodness_rows', so what they are worth rests on the tests here."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
-from conftest import golden_bands, rec_allclose
+from conftest import ROOT, golden_bands, parity_record, rec_allclose
 import _goodness_ref as GR
+import _hp_common as hp
+import _map_ref as MR
 import _summary_ref as SR
 
 pytestmark = pytest.mark.gpu
@@ -636,3 +660,452 @@ def test_native_refusals_leave_the_context_usable(mbb, oracle, g_lnl, g_pb, g_re
     s.npct = 1
     assert sctx.lib.mbb_sampler_goodness(sctx.h, h, C.byref(s), C.byref(out8)) == 0
     assert _same_bits(sm.goodness(), mbb.chain_goodness(lk, sm.chain, lnprob=sm.lnprobability))
+
+
+# ---------------------------------------------------------------- 10. the band layouts the kernels branch on
+MIX_ORDER = ["PACS_100um", "D_delta_70um", "PACS_160um", "E_delta_1100um", "SPIRE_250um", "SPIRE_350um", "SPIRE_500um",
+             "SCUBA2_850um"]                                          # MIX_BANDS, one-sample and many-sample bands in turn
+SHORT_BANDS = ["ALMA_box_145_7.5", "ALMA_alma_343", "SMA_gauss_345_8", "GISMO_2mm", "LABOCA_870um"]    # 11, 29, 43, 53, 94
+LDS_SAMPLES, LDS_COV, MAX_BANDS = 2560, 64, 256                      # kLdsSamples, kLdsCov, kMaxBands (held to the source below)
+# case -> (passbands, number of plain wavelengths, rho of the covariance, samples all bands have together, what is run)
+LAYOUTS = {
+    "mix": (MIX_ORDER, None, None, 1690, "both halves of k_good_flux in one launch, band order"),
+    "short": (SHORT_BANDS, None, None, 230, "many-sample bands shorter than a wave"),
+    "big": (MR.BIG_BANDS, None, None, 2796, "STAGE = false"),
+    "seam2560": (MR.BIG_BANDS[:-1] + ["FILL"], None, None, LDS_SAMPLES, "the last staged count"),
+    "seam2561": (MR.BIG_BANDS[:-1] + ["FILL"], None, None, LDS_SAMPLES + 1, "the first unstaged count"),
+    "cov64": (None, LDS_COV, 0.2, LDS_COV, "the largest C^-1 in LDS"),
+    "cov65": (None, LDS_COV + 1, 0.2, LDS_COV + 1, "the smallest C^-1 in global memory"),
+    "cov256": (None, MAX_BANDS, 0.2, MAX_BANDS, "kMaxBands, nb^2 = 65 536 terms per row"),
+    "delta256": (None, MAX_BANDS, None, MAX_BANDS, "kMaxBands, diagonal"),
+    "bigcov": (MR.BIG_BANDS, None, 0.3, 2796, "unstaged samples and a covariance together"),
+}
+V = {v[0]: v for v in VARIANTS}
+ONE_THIN_ONE_THICK = {"short": ("thin_walpha", "thick_noalpha"), "seam2560": ("thin_noalpha", "thick_walpha"),
+                      "seam2561": ("thin_noalpha", "thick_walpha"), "cov64": ("thin_walpha", "thick_walpha"),
+                      "cov65": ("thin_walpha", "thick_walpha"), "cov256": ("thin_noalpha", "thick_noalpha"),
+                      "delta256": ("thin_walpha", "thick_noalpha"), "bigcov": ("thin_noalpha", "thick_walpha")}
+LAYOUT_RUNS = [(c, v) for c in LAYOUTS for v in ([x[0] for x in VARIANTS] if c in ("mix", "big") else ONE_THIN_ONE_THICK[c])]
+
+
+def _filler(tmp, n):
+    """A passband of exactly n samples, from a file (tests/test_gpu_parity.py's way)."""
+    from mbb_emcee_amd import response
+    x = np.linspace(380.0, 520.0, n)
+    t = np.exp(-0.5 * ((x - 450.0) / 40.0) ** 2)
+    fn = os.path.join(str(tmp), "fill%d.txt" % n)
+    np.savetxt(fn, np.column_stack([x, t]))
+    r = response("FILL%d" % n)
+    r.setup(fn, xtype="wave", xunits="microns", senstype="energy", normtype="power", xnorm=450.0, normparam=-1.0)
+    return r
+
+
+class _Layout(object):
+    """A band case on both sides: the device likelihood, the oracle's band fluxes of the chain's rows (they do not depend
+    on the data), and the data of _setup's recipe -- the oracle's model at the chain's middle row pushed 5% up and down
+    band by band -- whose uncertainties scale (0.1 flux + 1), correlated with rho where the case has one, set() puts in
+    place."""
+
+    def __init__(self, mbb, oracle, g_pb, chain, opthin, noalpha, case, tmp):
+        names, nwave, self.rho, self.nsamples, _ = LAYOUTS[case]
+        self.case, self.rows = case, np.ascontiguousarray(np.asarray(chain).reshape(-1, 5))
+        free = dict(opthin=opthin, noalpha=noalpha, lowlim=np.full(5, -np.inf), has_uplim=[0] * 6)
+        if names is None:
+            self.first = np.geomspace(60.0, 1500.0, nwave)
+            self.like = mbb.likelihood(opthin=opthin, noalpha=noalpha)
+            okw = dict(wave=self.first)
+        else:
+            self.like = mbb.likelihood(response=True, opthin=opthin, noalpha=noalpha)
+            self.first, tables = [], []
+            for n in names:
+                if n == "FILL":
+                    r = _filler(tmp, self.nsamples - (2796 - 1108))      # (BIG_BANDS without SCUBA2_450um has 1688 samples)
+                    self.like._responsewheel._responses[r.name] = r
+                    self.first.append(r.name)
+                    tables.append((r.wavelength, r._sedmult, r._normfac))
+                else:
+                    self.first.append(n)
+                    tables.extend(MR.band_tables(g_pb, [n]))
+            okw = dict(bands=tables)
+        self.nb = len(self.first)
+        orc = oracle.OracleLikelihood(np.ones(self.nb), np.ones(self.nb), **okw, **free)
+        self.model = orc(self.rows, return_flux=True)[1]
+        assert np.all(orc.status == 0) and np.all(np.isfinite(self.model)) and self.model.shape == (self.rows.shape[0], self.nb)
+        self.flux = self.model[self.rows.shape[0] // 2] * (1.0 + 0.05 * (-1.0) ** np.arange(self.nb))
+        self.set(1.0)
+
+    def set(self, scale):
+        unc = scale * (0.1 * self.flux + 1.0)
+        self.like.set_phot(self.first, self.flux, unc)
+        if self.rho is not None:
+            n = self.nb
+            self.like.set_cov(np.outer(unc, unc) * (np.eye(n) + self.rho * (1.0 - np.eye(n))))      # (_map_ref.covariance's)
+        return self.like
+
+    def reference(self):
+        """(chisq in longdouble on the oracle's band fluxes, its bound), for the data set() put in place"""
+        w = _weights(self.like)
+        return GR.chisq(self.like._flux, self.model, **w), GR.chisq_bound(self.like._flux, self.model, **w)
+
+
+@pytest.fixture(scope="module")
+def layouts(mbb, oracle, g_pb, g_res, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("goodness_fill")
+
+    def get(case, name):
+        if ("layout", case, name) not in _CACHE:
+            _CACHE[("layout", case, name)] = _Layout(mbb, oracle, g_pb, g_res[name + "/chain"], V[name][1], V[name][2], case, tmp)
+        return _CACHE[("layout", case, name)]
+    return get
+
+
+LAYOUT_SCALES = {           # chosen on the CPU with the oracle alone (the conditions on them are asserted in the test)
+    ("mix", "thin_walpha"): (1.0, 1.5, 2.0), ("mix", "thick_walpha"): (1.0, 1.5, 2.0),
+    ("mix", "thick_noalpha"): (0.5, 0.7, 1.0), ("mix", "thin_noalpha"): (2.0, 3.0, 5.0),
+    ("short", "thin_walpha"): (0.3, 0.5, 1.0), ("short", "thick_noalpha"): (0.5, 0.7, 1.0),
+    ("big", "thin_walpha"): (1.0, 1.5, 2.0), ("big", "thick_walpha"): (1.0, 1.5, 2.0),
+    ("big", "thick_noalpha"): (0.5, 0.7, 1.5), ("big", "thin_noalpha"): (1.5, 2.0, 3.0),
+    ("seam2560", "thin_noalpha"): (1.5, 2.0, 3.0), ("seam2560", "thick_walpha"): (1.0, 1.5, 2.0),
+    ("seam2561", "thin_noalpha"): (1.5, 2.0, 3.0), ("seam2561", "thick_walpha"): (1.0, 1.5, 2.0),
+    ("cov64", "thin_walpha"): (1.0, 1.5, 2.0), ("cov64", "thick_walpha"): (1.0, 1.5, 2.0),
+    ("cov65", "thin_walpha"): (1.0, 1.5, 2.0), ("cov65", "thick_walpha"): (1.0, 1.5, 2.0),
+    ("cov256", "thin_noalpha"): (1.0, 1.5, 2.0), ("cov256", "thick_noalpha"): (1.5, 2.0, 3.0),
+    ("delta256", "thin_walpha"): (2.0, 3.0, 5.0), ("delta256", "thick_noalpha"): (2.0, 3.0, 5.0),
+    ("bigcov", "thin_noalpha"): (1.5, 2.0, 3.0), ("bigcov", "thick_walpha"): (1.0, 1.5, 2.0),
+}
+
+
+@pytest.fixture(scope="module")
+def probe():
+    p = hp.probe_module().load()
+    assert not p.is_host
+    return p
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _ulps_apart(a, b):
+    """distance in representable doubles between two arrays of non-negative finite doubles"""
+    return np.abs(_bits(a) - _bits(b))
+
+
+def _same_entry_point(probe, nb, chi, q):
+    """The kernel's q is the probe's m_gammq_half at the kernel's own chisq: the function part A judged is the one
+    k_good_chi calls.  Both are compiled from csrc/mbb_gammq.hip.h with the same device flags; bit for bit."""
+    want = probe.gammq(nb, chi)
+    nan = np.isnan(chi)
+    assert np.array_equal(np.isnan(q), nan) and np.array_equal(np.isnan(want), nan)
+    apart = _ulps_apart(q[~nan], want[~nan])
+    parity_record("q of the kernel vs the probe's m_gammq_half [ulp]", apart.max() if apart.size else 0, 0)
+    assert np.array_equal(q, want, equal_nan=True), (nb, apart.max(), chi[~nan][apart.argmax()])
+
+
+def test_layout_constants_are_the_sources():
+    src = open(os.path.join(ROOT, "mbb_emcee_amd", "csrc", "mbb_goodness.hip.h")).read()
+    assert "constexpr int kLdsSamples = %d;" % LDS_SAMPLES in src and "constexpr int kLdsCov = %d;" % LDS_COV in src
+    assert "constexpr int kLdsSamples = 2560;" in src and "constexpr int kLdsCov = 64;" in src
+    assert "constexpr int kMaxBands = mbbm::kGammqMaxNb;" in src
+    gq = open(os.path.join(ROOT, "mbb_emcee_amd", "csrc", "mbb_gammq.hip.h")).read()
+    assert "constexpr int kGammqMaxNb = %d;" % MAX_BANDS in gq and GR.MAX_NB == MAX_BANDS
+    assert set(LAYOUT_SCALES) == set(LAYOUT_RUNS)
+    for c in LAYOUTS:                                                   # at least one thin and one thick variant of each
+        vs = [v for cc, v in LAYOUT_RUNS if cc == c]
+        assert any(V[v][1] for v in vs) and any(not V[v][1] for v in vs), c
+
+
+@pytest.mark.parametrize("case,name", LAYOUT_RUNS)
+def test_band_layouts(mbb, oracle, layouts, probe, case, name):
+    """10. Every row of the fixture chain at three uncertainty scales, in a band layout the kernels branch on (LAYOUTS):
+    every row's band fluxes against the oracle's, chisq within its bound through the chain path and through
+    goodness_rows (the same bits), q against mpmath at the device's own chisq and bit for bit the probe's
+    m_gammq_half."""
+    pytest.importorskip("mpmath")
+    from scipy.special import gammaincc
+    from mbb_emcee_amd import goodness
+    L = layouts(case, name)
+    nb, rows = L.nb, L.rows
+    pts_x, pts_q = [], []
+    for scale in LAYOUT_SCALES[(case, name)]:
+        like = L.set(scale)
+        freq, wt, offs = like.band_tables()
+        assert freq.size == L.nsamples and offs.size == nb + 1, (case, freq.size)
+        assert like._has_covmatrix == (L.rho is not None)
+        chi, q, st, fl = goodness.goodness_rows(like, rows, want_flux=True)
+        assert np.all(st == 0) and fl.shape == (rows.shape[0], nb)
+        rec_allclose(fl, L.model, rtol=1e-12, kind="band flux per row vs oracle")
+        cc, qc, g = _entries(mbb, like, rows)
+        assert np.array_equal(cc, chi) and np.array_equal(qc, q)            # the chain path: the same bits
+        ref, bound = L.reference()
+        err = np.abs((chi.astype(GR.LD) - ref).astype(np.float64)) / bound
+        print("    %s %s scale %g: chisq %.3g .. %.3g, worst %.3g of its bound" % (name, case, scale, chi.min(), chi.max(), err.max()))
+        rec_allclose(err, 0.0, rtol=0, atol=1, kind="chisq per entry, band layouts [its bound]")
+        assert g.ndata == nb and np.array_equal(g._raw.ml_model, fl)        # (one entry per source: it is the ML entry)
+        _same_entry_point(probe, nb, chi, q)
+        pts_x.append(chi); pts_q.append(q)
+    x, q = np.concatenate(pts_x), np.concatenate(pts_q)
+    truth = [GR.q_mp(nb, v) for v in x]
+    big = np.array([t >= GR.Q_FLOOR for t in truth])
+    informative = np.array([GR.Q_FLOOR <= t <= 0.99 for t in truth])
+    print("    %s %s: %d of %d entries with 1e-290 <= true q <= 0.99, %d above, %d below 1e-290"
+          % (name, case, informative.sum(), x.size, sum(t > 0.99 for t in truth), (~big).sum()))
+    # conditions on the inputs: the scales make the case judge the function
+    assert 4 * informative.sum() >= x.size and any(t > 0.99 for t in truth) and (~big).sum() >= 1
+    scipy_err = GR.rel_errors(truth, big, gammaincc(0.5 * nb, 0.5 * x)).max()
+    rec_allclose(scipy_err, 0.0, rtol=0, atol=1e-12, kind="scipy gammaincc vs mpmath on the test's points")
+    dev = GR.rel_errors(truth, big, q)
+    print("    %s %s: q worst relative %.3g; scipy's on the same points %.3g" % (name, case, dev.max(), scipy_err))
+    rec_allclose(dev / (4.0 * scipy_err), 0.0, rtol=0, atol=1, kind="q per entry, band layouts [4 x scipy's error]")
+    assert np.all(q[~big] >= 0.0) and np.all(q[~big] <= 1e-289) and np.all((q >= 0) & (q <= 1))
+
+
+def test_staging_seam_shares_its_bands_bit_for_bit(layouts):
+    """2560 samples are staged in LDS, 2561 are read from global memory: the six bands the two cases share give the same
+    bits in both, so moving the seam by one (<= to < in good_eval) changes nothing that is right on both sides."""
+    from mbb_emcee_amd import goodness
+    for name in ONE_THIN_ONE_THICK["seam2560"]:
+        a, b = layouts("seam2560", name), layouts("seam2561", name)
+        la, lb = a.set(1.0), b.set(1.0)
+        na, nb_ = la.band_tables()[0].size, lb.band_tables()[0].size
+        assert (na, nb_) == (LDS_SAMPLES, LDS_SAMPLES + 1) and a.nb == b.nb == 7
+        assert np.array_equal(la.band_tables()[2][:7], lb.band_tables()[2][:7])          # the shared bands: the same samples
+        _, _, sa, fa = goodness.goodness_rows(la, a.rows, want_flux=True)
+        _, _, sb, fb = goodness.goodness_rows(lb, b.rows, want_flux=True)
+        assert np.all(sa == 0) and np.all(sb == 0)
+        assert np.array_equal(fa[:, :6], fb[:, :6]), name
+        assert not np.array_equal(fa[:, 6], fb[:, 6])                                     # (the filler bands do differ)
+        # ... and with the filler's datum given no weight, chisq and q too
+        for L in (a, b):
+            unc = 0.1 * L.flux + 1.0
+            unc[6] = np.inf
+            L.like.set_phot(L.first, L.flux, unc)
+        ca, qa, _ = goodness.goodness_rows(a.like, a.rows)
+        cb, qb, _ = goodness.goodness_rows(b.like, b.rows)
+        assert np.array_equal(ca, cb) and np.array_equal(qa, qb) and np.all(np.isfinite(ca)) and np.all(ca > 0)
+    # the same for C^-1 in LDS and in global memory: 64 wavelengths are the first 64 of no 65-wavelength case (geomspace),
+    # so that seam is held by cov64 and cov65 each being right; here only that they are on either side of kLdsCov
+    assert LAYOUTS["cov64"][1] == LDS_COV and LAYOUTS["cov65"][1] == LDS_COV + 1
+
+
+def test_mix_layout_runs_both_halves(layouts):
+    """A condition on the input of `mix`: one-sample bands of weight exactly 1 (k_good_flux's lane-per-row half) between
+    bands of many samples (its wave-per-row half)."""
+    like = layouts("mix", "thin_walpha").set(1.0)
+    freq, wt, offs = like.band_tables()
+    n = np.diff(offs)
+    assert list(n == 1) == [False, True, False, True, False, False, False, False] and np.all(wt[offs[:-1][n == 1]] == 1.0)
+    assert freq.size == 1690 and np.all(n[n > 1] % 64 != 0)
+    short = layouts("short", "thin_walpha").set(1.0)
+    assert list(np.diff(short.band_tables()[2])) == [11, 29, 43, 53, 94]
+
+
+@pytest.mark.parametrize("name", ["thin_walpha", "thick_noalpha"])
+def test_row_counts_off_the_wave_and_the_workgroup(layouts, name):
+    """goodness_rows on the first n rows of `mix`, n around the wave (64) and the workgroup (256): chisq, q, status and
+    fluxes are those of the same rows inside the 512-row call."""
+    from mbb_emcee_amd import goodness
+    L = layouts("mix", name)
+    like = L.set(LAYOUT_SCALES[("mix", name)][1])
+    full = goodness.goodness_rows(like, L.rows, want_flux=True)
+    assert np.all(full[2] == 0) and np.all(np.isfinite(full[3]))
+    for n in (1, 63, 64, 65, 255, 257):
+        part = goodness.goodness_rows(like, L.rows[:n], want_flux=True)
+        for got, want in zip(part, full):
+            assert got.shape[0] == n and np.array_equal(got, want[:n]), n
+
+
+@pytest.mark.parametrize("name", ["thin_walpha", "thick_walpha"])
+def test_failing_rows_in_a_mixed_layout(layouts, name):
+    """Rows the constructor refuses (test_bad_rows': alpha <= 0, beta < 0, a NaN) at the ends of waves and workgroups
+    of a 300-row `mix` call: a nonzero status, NaN in every band, one-sample and many-sample alike, NaN chisq and q;
+    every other row keeps its bits."""
+    from mbb_emcee_amd import goodness
+    L = layouts("mix", name)
+    like = L.set(LAYOUT_SCALES[("mix", name)][1])
+    rows = L.rows[:300].copy()
+    clean = goodness.goodness_rows(like, rows, want_flux=True)
+    assert np.all(clean[2] == 0)
+    where = [0, 63, 64, 255, 256, 299]
+    for k, i in enumerate(where):
+        if k % 3 == 0:
+            rows[i, 3] = -1.0
+        elif k % 3 == 1:
+            rows[i, 1] = -0.5
+        else:
+            rows[i, 0] = np.nan
+    chi, q, st, fl = goodness.goodness_rows(like, rows, want_flux=True)
+    assert np.all(st[where] != 0) and np.all(np.isnan(fl[where])) and np.all(np.isnan(chi[where])) and np.all(np.isnan(q[where]))
+    rest = np.setdiff1d(np.arange(300), where)
+    for got, want in zip((chi, q, st, fl), clean):
+        assert np.array_equal(got[rest], want[rest])
+
+
+@pytest.mark.parametrize("case", ["cov65", "big"])
+def test_multi_source_beyond_the_seams(mbb, layouts, case):
+    """Three sources of different scale with diagonal uncertainties, 65 wavelengths (more than C^-1 has LDS for, were
+    there one) and `big` (unstaged samples): each source is bit for bit its own one-source call."""
+    from mbb_emcee_amd import goodness
+    L = layouts(case, "thick_walpha")
+    response = not isinstance(L.first, np.ndarray)
+    flux = L.flux[None, :] * np.array([1.0, 37.0, 0.004])[:, None]
+    unc = 0.1 * flux + np.array([1.0, 5.0, 0.01])[:, None]
+    multi = mbb.likelihood(response=response, opthin=False, noalpha=False)
+    multi.set_phot_multi(L.first, flux, unc)
+    rows = L.rows[:3 * 100]
+    c3, q3, s3, f3 = goodness.goodness_rows(multi, rows, want_flux=True)
+    chain = np.ascontiguousarray(rows.reshape(3, 10, 10, 5))
+    g = mbb.chain_goodness(multi, chain, percentile=(68.3, 95.4), burn=1, thin=2)
+    assert np.all(s3 == 0) and len(set(g.chisq_mean)) == 3
+    one = mbb.likelihood(response=response, opthin=False, noalpha=False)
+    for s in range(3):
+        one.set_phot(L.first, flux[s], unc[s])
+        c1, q1, s1, f1 = goodness.goodness_rows(one, rows[100 * s:100 * (s + 1)], want_flux=True)
+        sl = slice(100 * s, 100 * (s + 1))
+        assert np.array_equal(c3[sl], c1) and np.array_equal(q3[sl], q1) and np.array_equal(f3[sl], f1) and np.all(s1 == 0)
+        alone = mbb.chain_goodness(one, chain[s], percentile=(68.3, 95.4), burn=1, thin=2)
+        for f in RAW_FIELDS:
+            assert np.array_equal(getattr(g._raw, f)[s], getattr(alone._raw, f)[0], equal_nan=True), (case, s, f)
+
+
+def test_row_chunks_of_goodness_rows(mbb, oracle, g_lnl, g_pb, g_res):
+    """The row-chunk loop of mbb_goodness_rows (2^18 rows a chunk), two wavelengths, rows tiled from a fixture chain:
+    one source and 2^18 + 65 rows -- the rows around the seam and the first 64 are bit for bit a call of those rows
+    alone --; three sources of 87 403 rows, the seam inside the last -- each is bit for bit its one-source call."""
+    from mbb_emcee_amd import goodness
+    seam = SR.chunk_rows(ROOT)
+    assert seam == 1 << 18
+    like, _ = _setup(mbb, oracle, g_lnl, g_pb, g_res["thick_walpha/chain"], False, False, "delta2")
+    base = g_res["thick_walpha/chain"].reshape(-1, 5)
+    n = seam + 65
+    rows = np.ascontiguousarray(np.tile(base, (n // base.shape[0] + 1, 1))[:n])
+    chi, q, st, fl = goodness.goodness_rows(like, rows, want_flux=True)
+    # (a chain repeats the rows of rejected moves; enough of the 129 rows around the seam differ for a misplaced one to show)
+    assert np.all(st == 0) and np.all(np.isfinite(chi)) and len(set(chi[seam - 64:seam + 65])) > 64
+    for sl in (slice(seam - 64, seam + 65), slice(0, 64)):
+        part = goodness.goodness_rows(like, rows[sl], want_flux=True)
+        for got, want in zip(part, (chi, q, st, fl)):
+            assert np.array_equal(got, want[sl]), sl
+    # ... and every row is the row of the chain it was tiled from
+    c0, q0, _, f0 = goodness.goodness_rows(like, base, want_flux=True)
+    idx = np.arange(n) % base.shape[0]
+    assert np.array_equal(chi, c0[idx]) and np.array_equal(q, q0[idx]) and np.array_equal(fl, f0[idx])
+    per = 87403
+    assert 2 * per < seam < 3 * per
+    flux = like._flux[None, :] * np.array([1.0, 37.0, 0.004])[:, None]
+    unc = 0.1 * flux + np.array([1.0, 5.0, 0.01])[:, None]
+    multi = mbb.likelihood()
+    multi.set_phot_multi(DELTA[:2], flux, unc)
+    rows3 = np.ascontiguousarray(np.tile(base, (3 * per // base.shape[0] + 1, 1))[:3 * per])
+    c3, q3, s3 = goodness.goodness_rows(multi, rows3)
+    one = mbb.likelihood()
+    for s in range(3):
+        one.set_phot(DELTA[:2], flux[s], unc[s])
+        sl = slice(per * s, per * (s + 1))
+        c1, q1, s1 = goodness.goodness_rows(one, rows3[sl])
+        assert np.array_equal(c3[sl], c1) and np.array_equal(q3[sl], q1) and np.array_equal(s3[sl], s1) and np.all(s1 == 0), s
+    assert len({c3[0], c3[per], c3[2 * per]}) == 3
+
+
+def test_257_bands_are_refused_through_the_c_abi(layouts):
+    """A context with 257 bands: mbb_chain_goodness and mbb_goodness_rows return MBB_ERR_ARG with their message and
+    write nothing; the same context then serves a 256-band call correctly."""
+    from mbb_emcee_amd import _native, goodness
+    from mbb_emcee_amd.modified_blackbody import um_to_GHz
+    L = layouts("delta256", "thin_walpha")
+    ref = goodness.goodness_rows(L.set(3.0), L.rows[:64], want_flux=True)
+    ctx = _native.Context(None)
+    ctx.set_model(True, False, 500.0)
+    wave = np.geomspace(60.0, 1500.0, 257)
+    ctx.set_bands(um_to_GHz / wave, np.ones(257), np.arange(258, dtype=np.int32))
+    ctx.set_data(np.ones(257), ivar=np.ones(257))
+    p = np.ascontiguousarray(L.rows[:64])
+    c, q, fl = np.full(64, 7.0), np.full(64, 7.0), np.full((64, 257), 7.0)
+    st = np.full(64, 7, dtype=np.int32)
+    rc = ctx.lib.mbb_goodness_rows(ctx.h, _native._d(p), 64, _native._d(c), _native._d(q), _native._i(st), _native._d(fl))
+    assert rc == -2 and ctx.lib.mbb_last_error().decode() == "more than 256 bands in a goodness call"
+    assert np.all(c == 7.0) and np.all(q == 7.0) and np.all(st == 7) and np.all(fl == 7.0)
+    s = _native.GoodnessSpec()
+    s.npct, s.burn, s.thin = 1, 0, 1
+    s.pct[0] = 50.0
+    raw = goodness._Raw(1, 257, 1)
+    before = {f: getattr(raw, f).copy() for f in RAW_FIELDS}
+    out = raw.out()
+    chain = np.ascontiguousarray(p.reshape(1, 4, 16, 5))
+    rc = ctx.lib.mbb_chain_goodness(ctx.h, _native._d(chain), None, 1, 4, 16, C.byref(s), C.byref(out))
+    assert rc == -2 and ctx.lib.mbb_last_error().decode() == "more than 256 bands in a goodness call"
+    for f in RAW_FIELDS:
+        assert np.array_equal(getattr(raw, f), before[f], equal_nan=True), f
+    # the same context, 256 bands: the likelihood's own answer
+    ctx.set_bands(*L.like.band_tables())
+    ctx.set_data(L.like._flux, ivar=L.like._ivar)
+    fl = np.full((64, 256), 7.0)
+    rc = ctx.lib.mbb_goodness_rows(ctx.h, _native._d(p), 64, _native._d(c), _native._d(q), _native._i(st), _native._d(fl))
+    assert rc == 0
+    for got, want in zip((c, q, st, fl), ref):
+        assert np.array_equal(got, want)
+    raw = goodness._Raw(1, 256, 1)
+    out = raw.out()
+    assert ctx.lib.mbb_chain_goodness(ctx.h, _native._d(chain), None, 1, 4, 16, C.byref(s), C.byref(out)) == 0
+    rc, own, _ = _native_call(L.like, chain, qs=(50.0,))                    # (the likelihood's own context)
+    assert rc == 0 and raw.n_used[0, 0] == 64 and raw.min[0, 0] == ref[0].min() and raw.ml[0, 5] == ref[0].min()
+    for f in RAW_FIELDS:
+        assert np.array_equal(getattr(raw, f), getattr(own, f), equal_nan=True), f
+
+
+# ---------------------------------------------------------------- 11. Q(nb/2, chisq/2) at every order, on the device
+@pytest.mark.parametrize("parity", [0, 1], ids=["even", "odd"])
+def test_q_at_every_order(probe, parity):
+    """11. m_gammq_half through the probe at every order of one parity, 2 .. 256 or 1 .. 255, on the order's 70 points
+    (_goodness_ref.order_grid) against mpmath.  Outer bound, every order: 4 x the largest relative error
+    scipy.special.gammaincc shows on the order's own points.  Even orders also the derived bound (9 + 1.5 ceil(nb/2)) eps
+    (_goodness_ref.horner_bound_eps): no library function enters them.  Odd orders have the device library's erfc."""
+    pytest.importorskip("mpmath")
+    from scipy.special import gammaincc
+    orders = [n for n in range(1, GR.MAX_NB + 1) if n % 2 == parity]
+    assert len(orders) == 128
+    grids = [GR.order_truth(n) for n in orders]
+    got = probe.gammq(np.array(orders, dtype=np.float64)[:, None], np.array([g[0] for g in grids]))       # one call
+    assert got.shape == (128, 70)
+    worst_eps, worst_outer, worst_derived, least_outer = 0.0, 0.0, 0.0, np.inf
+    for n, (x, truth, big), q in zip(orders, grids, got):
+        # the condition of the grid itself: it judges the function at this order, on both sides of the floor
+        assert big.sum() >= 60 and (~big).sum() >= 1, (n, big.sum())
+        assert np.all(q[~big] >= 0.0) and np.all(q[~big] <= 1e-289), (n, q[~big])
+        rel = GR.rel_errors(truth, big, q)
+        outer = 4.0 * GR.rel_errors(truth, big, gammaincc(0.5 * n, 0.5 * x)).max()
+        at = x[big][rel.argmax()]
+        worst_eps, worst_outer = max(worst_eps, rel.max() / GR.EPS), max(worst_outer, rel.max() / outer)
+        least_outer = min(least_outer, outer / GR.EPS)
+        assert rel.max() <= outer, (n, rel.max() / GR.EPS, outer / GR.EPS, at)
+        if parity == 0:
+            worst_derived = max(worst_derived, rel.max() / (GR.horner_bound_eps(n) * GR.EPS))
+            assert rel.max() <= GR.horner_bound_eps(n) * GR.EPS, (n, rel.max() / GR.EPS, GR.horner_bound_eps(n), at)
+    name = "q per order, %s nb" % ("odd", "even")[parity == 0]
+    print("    %s: worst %.1f eps, %.3g of 4 x scipy's error on the order's points%s"
+          % (name, worst_eps, worst_outer, ", %.3g of the derived bound" % worst_derived if parity == 0 else ""))
+    parity_record(name + " [4 x scipy's error on the order's points]", worst_outer, 1.0)
+    # what was seen, in eps; beside it the smallest outer bound any order of this parity had (each order is held to its own)
+    parity_record(name + " [eps; beside it the smallest outer bound of any order]", worst_eps, least_outer)
+    if parity == 0:
+        parity_record(name + " [(9 + 1.5 ceil(nb/2)) eps]", worst_derived, 1.0)
+
+
+def test_q_edges_on_the_device(probe):
+    """tests/test_goodness_cpu.py's test_host_build_edges through the probe's device build."""
+    inf, nan = float("inf"), float("nan")
+    orders = (1, 2, 3, 8, 63, 64, 255, 256)
+    q = probe.gammq(np.array(orders, dtype=np.float64)[:, None], np.array([0.0, -0.0, -5.0, -inf, inf, nan, 1e10, 1e300, 5e-324]))
+    for nb, v in zip(orders, q):
+        assert np.array_equal(v[:4], np.ones(4)) and v[4] == 0.0 and np.isnan(v[5]), (nb, v)
+        assert v[6] == 0.0 and v[7] == 0.0 and v[8] == 1.0, (nb, v)
+    x = np.concatenate([np.geomspace(1e-300, 1e12, 2000), np.linspace(1380.0, 3100.0, 500)])
+    x.sort()
+    for nb, v in zip(orders, probe.gammq(np.array(orders, dtype=np.float64)[:, None], x)):
+        assert not np.isnan(v).any() and np.all(v >= 0) and np.all(v <= 1), nb
+        big = v > 1e-280
+        assert np.all(np.diff(v[big]) <= 4 * GR.EPS * v[big][:-1]), nb
+    # what the probe refuses, before any launch
+    for bad in (0.0, 257.0, 1.5, nan, -1.0, inf):
+        with pytest.raises(RuntimeError, match="domain"):
+            probe.gammq(bad, [1.0])
