@@ -489,6 +489,61 @@ int mbb_sampler_goodness(mbb_ctx *ctx, void *sampler, const mbb_goodness_spec *s
 int mbb_goodness_rows(mbb_ctx *ctx, const double *pars, int n, double *chisq, double *q, int32_t *status,
                       double *model_flux);
 
+/* ---- out-of-sample fit of a chain: WAIC and PSIS-LOO per source and band ---- */
+/* New: the reference has nothing comparable.  Everything is per source and per band b of the context, over a summary's
+ * window: steps burn, burn + thin, ... of every walker, in [walker][step] order, which is the window index below.
+ * r = f - m(theta), m the band fluxes exactly as mbb_goodness_rows returns them; Lambda = C^-1 when the data has a
+ * covariance and diag(ivar) otherwise; g = Lambda r.
+ *   ll_b(theta) = (ln Lambda_bb - ln 2 pi) / 2 - g_b^2 / (2 Lambda_bb)
+ *           = ln p(f_b | f_-b, theta), the conditional Gaussian (Buerkner, Gabry & Vehtari 2021); without a covariance
+ *           the usual -r_b^2 ivar_b / 2 + ln(ivar_b / 2 pi) / 2.  It knows no limits or priors, like chisq.  A row the
+ *           SED constructor fails on gives NaN in every band and its row-status bit when it is inside the window.
+ * With S the window's entries of finite ll_b:
+ *   n_used = S;  lppd = LSE_s ll - ln S;  p_waic = var(ll), ddof 1, in two passes (NaN for S < 2);
+ *   elpd_waic = lppd - p_waic.
+ * PSIS (Vehtari, Simpson, Gelman, Yao & Gabry; `loo` 2.x psislw): lw = -ll - max(-ll); M = ceil(min(0.2 S, 3 sqrt S));
+ * the tail is the M entries largest in (lw, window index) order, the cutoff c the largest lw not in it;
+ * x_i = exp(lw_i) - exp(c) ascending; (k, sigma) by Zhang & Stephens (2009): m = 30 + floor(sqrt M),
+ * x* = x[floor(M/4 + 1/2)] (1-based), theta_j = 1/x_M + (1 - sqrt(m / (j - 1/2))) / (3 x*), k_j = mean log1p(-theta_j x),
+ * l_j = M (ln(-theta_j / k_j) - k_j - 1), w = softmax(l) (maximum subtracted), theta^ = sum theta_j w_j,
+ * k = mean log1p(-theta^ x), sigma = -k / theta^, k^ = (k M + 5) / (M + 10).  The tail entry of ascending rank i gets
+ * lw = ln(sigma expm1(-k^ log1p(-p_i)) / k^ + exp(c)), p_i = (i - 1/2) / M; every lw is capped at 0.
+ * The raw lw are kept (truncated importance sampling) and k^ = +inf when M < 5 (S <= 20: MBB_PW_TAIL_SHORT), or the
+ * tail is constant, x* <= 0, or any of k, sigma, k^ is not finite (MBB_PW_TAIL_FLAT).
+ *   elpd_loo = LSE(ll + lw) - LSE(lw);  p_loo = lppd - elpd_loo;
+ *   loo_pit = sum_s w^_s Phi(g_b / sqrt Lambda_bb), w^ the normalised weights: the leave-one-band-out probability that
+ *           a replicated flux lies below the measured one (Phi through erfc);  tail_len = M.
+ * Every sum has a fixed order, the tail's ascending; a row's ll is the same bits whatever the call's shape; the results
+ * do not depend on how many bands are worked on at a time (option "pointwise_budget_mb").  At most 256 bands.  The tail
+ * is sorted by one workgroup: a window of more than MBB_PW_MAX_WINDOW entries per source is MBB_ERR_ARG. */
+#define MBB_PW_TAIL_MAX 4096
+#define MBB_PW_MAX_WINDOW 1864135          /* the largest S with ceil(3 sqrt S) <= MBB_PW_TAIL_MAX */
+enum mbb_pointwise_status {                /* beside the mbb_summary_status bits EMPTY, HAS_NAN (entries left out), ROW_SHIFT */
+    MBB_PW_K_HIGH = 16,                    /* k^ > 0.7 (a fallback's +inf included)                            */
+    MBB_PW_TAIL_SHORT = 32,
+    MBB_PW_TAIL_FLAT = 64,
+    MBB_PW_WAIC_VAR_HIGH = 128             /* p_waic > 0.4                                                     */
+};
+typedef struct mbb_pointwise_spec {
+    int32_t burn, thin;                    /* window: steps burn, burn + thin, ...                            */
+} mbb_pointwise_spec;
+/* Where the results go: [nsrc][nb] each; every pointer is the caller's, host memory, required. */
+typedef struct mbb_pointwise_out {
+    int64_t *n_used;
+    int32_t *tail_len, *status;
+    double *lppd, *p_waic, *elpd_waic, *elpd_loo, *p_loo, *khat, *loo_pit;
+} mbb_pointwise_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5].  Arguments are checked before anything is allocated, uploaded
+ * or launched: MBB_ERR_STATE with no bands or data set, MBB_ERR_ARG otherwise, with a message. */
+int mbb_chain_pointwise(mbb_ctx *ctx, const double *chain, int nsrc, int nw, int nsteps, const mbb_pointwise_spec *spec,
+                        const mbb_pointwise_out *out);
+/* The same of the chain the sampler's last stored or summarised run left on the device.  MBB_ERR_STATE when there is
+ * none, and for a sharded run, as mbb_sampler_goodness. */
+int mbb_sampler_pointwise(mbb_ctx *ctx, void *sampler, const mbb_pointwise_spec *spec, const mbb_pointwise_out *out);
+/* ll [n][nb] and the row status of n parameter rows: the device function the chain's entries go through.  Rows are
+ * grouped by source as for mbb_lnlike_batch. */
+int mbb_pointwise_rows(mbb_ctx *ctx, const double *pars, int n, double *ll, int32_t *status);
+
 /* ---- the maximum of the posterior, found on the device ---- */
 /* New: the reference has no optimiser; its "best fit" is the chain entry of largest lnprob (results.py:160-165).
  * -2 ln P is a sum of squares -- the data term, one square per soft upper wall that is exceeded, one per Gaussian prior

@@ -105,6 +105,21 @@ class GoodnessOut(C.Structure):
                 ("at_mean", _dp), ("ml", _dp), ("ml_index", _ip), ("ml_model", _dp), ("best", _dp), ("best_index", _ip)]
 
 
+PW_TAIL_MAX, PW_MAX_WINDOW = 4096, 1864135
+PW_K_HIGH, PW_TAIL_SHORT, PW_TAIL_FLAT, PW_WAIC_VAR_HIGH = 16, 32, 64, 128
+
+
+class PointwiseSpec(C.Structure):
+    """mbb_pointwise_spec (include/mbb_hip.h)"""
+    _fields_ = [("burn", C.c_int32), ("thin", C.c_int32)]
+
+
+class PointwiseOut(C.Structure):
+    """mbb_pointwise_out (include/mbb_hip.h)"""
+    _fields_ = [("n_used", _lp), ("tail_len", _ip), ("status", _ip), ("lppd", _dp), ("p_waic", _dp), ("elpd_waic", _dp),
+                ("elpd_loo", _dp), ("p_loo", _dp), ("khat", _dp), ("loo_pit", _dp)]
+
+
 MAP_MAX_STARTS, MAP_MAX_ITER = 64, 1000
 MAP_CONVERGED_F, MAP_CONVERGED_X, MAP_MAXITER, MAP_START_INVALID, MAP_COV_SINGULAR, MAP_ALL_FIXED = 1, 2, 4, 8, 16, 32
 MAP_STENCIL_FAILED = 64
@@ -202,6 +217,10 @@ SIGNATURES = {
                                      C.POINTER(GoodnessOut)]),
     "mbb_sampler_goodness": (C.c_int, [_vp, _vp, C.POINTER(GoodnessSpec), C.POINTER(GoodnessOut)]),
     "mbb_goodness_rows": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _ip, _dp]),
+    "mbb_chain_pointwise": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(PointwiseSpec),
+                                      C.POINTER(PointwiseOut)]),
+    "mbb_sampler_pointwise": (C.c_int, [_vp, _vp, C.POINTER(PointwiseSpec), C.POINTER(PointwiseOut)]),
+    "mbb_pointwise_rows": (C.c_int, [_vp, _dp, C.c_int, _dp, _ip]),
     "mbb_map_fit": (C.c_int, [_vp, C.POINTER(MapSpec), C.POINTER(MapOut)]),
     "mbb_chain_evidence": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(EvidenceSpec),
                                      C.POINTER(EvidenceOut)]),

@@ -37,6 +37,7 @@
 #include "mbb_goodness.hip.h"
 #include "mbb_map.hip.h"
 #include "mbb_evidence.hip.h"
+#include "mbb_pointwise.hip.h"
 #include "mbb_draws.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
@@ -349,6 +350,8 @@ struct mbb_ctx {
         size_t lds_granted[8] = {};           // whether this context has asked for the dynamic-LDS ceiling, by instantiation of k_map_lm
     } map;
     struct EvWork { DevBuf mom, ints, slab, l1, l2, postq, neff, outbuf; } ev;  // the evidence of a chain (evidence_run)
+    struct PwWork { DevBuf cols, part, state, sel, hist, status, outbuf; } pw;  // the out-of-sample fit of a chain (pw_run)
+    long opt_pw_budget_mb = 16384;   // ... its two columns per band of a group may take this much; at least one band a group
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
     long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
@@ -3373,6 +3376,212 @@ extern "C" int mbb_goodness_rows(mbb_ctx *c, const double *pars, int n, double *
     return MBB_OK;
 }
 
+// ---- out-of-sample fit of a chain (mbb_pointwise.hip.h) -----------------------
+// The argument checks of a pointwise call: before anything is allocated, uploaded or launched.
+static int pw_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_pointwise_spec *sp, const mbb_pointwise_out *o)
+{
+    if (!sp || !o || !o->n_used || !o->tail_len || !o->status || !o->lppd || !o->p_waic || !o->elpd_waic || !o->elpd_loo ||
+        !o->p_loo || !o->khat || !o->loo_pit)
+        return fail(MBB_ERR_ARG, "null pointwise argument");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    int rc;
+    if ((rc = good_check_ctx(c, nsrc))) return rc;
+    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    const long long kept = ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
+    if ((long long)nw * kept > MBB_PW_MAX_WINDOW || mbbps::ps_tail_len((long long)nw * kept) > mbbps::kTailMax)
+        return fail(MBB_ERR_ARG, "the window's tail would be longer than one workgroup sorts (MBB_PW_MAX_WINDOW entries per source)");
+    if ((size_t)nsrc * c->nb > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    return MBB_OK;
+}
+
+// k_good_flux on the n rows whose records launch_prologue has just made, as good_eval launches it
+static int pw_flux(mbb_ctx *c, mbbq::FluxArgs &fa, int n)
+{
+    using namespace mbbq;
+    fa.wk = c->sed.wk.d(); fa.status = c->sed.status.d();
+    fa.n = n; fa.mf = (double *)c->good.mf.p;
+    const bool stage = fa.nmany > 0 && fa.nsamples <= kLdsSamples;
+    const size_t lds = stage ? (size_t)fa.nsamples * 3 * sizeof(double) : 0;
+    const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
+    dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
+        if (stage)
+            hipLaunchKernelGGL((k_good_flux<decltype(OT)::value, decltype(NA)::value, true>), grid, dim3(kThreads), lds, c->stream, fa);
+        else
+            hipLaunchKernelGGL((k_good_flux<decltype(OT)::value, decltype(NA)::value, false>), grid, dim3(kThreads), 0, c->stream, fa);
+    });
+    HIPCHK(hipGetLastError());
+    return MBB_OK;
+}
+
+// ... and k_pw_g on their band fluxes.  ga carries where the results go and the group.
+static int pw_g(mbb_ctx *c, const mbbq::FluxArgs &fa, mbbpw::GArgs &ga, int n)
+{
+    ga.mf = fa.mf; ga.status = fa.status; ga.n = n; ga.nb = c->nb;
+    ga.nsrc_data = c->nsrc;
+    ga.flux = c->data.flux.d(); ga.ivar = c->data.ivar.d();
+    ga.invcov = c->has_cov ? c->data.invcov.d() : nullptr;
+    ga.cov_in_lds = c->has_cov && c->nb <= mbbq::kLdsCov;
+    const size_t clds = ga.cov_in_lds ? (size_t)c->nb * c->nb * sizeof(double) : 0;
+    hipLaunchKernelGGL(mbbpw::k_pw_g, dim3((unsigned)((n + mbbq::kThreads - 1) / mbbq::kThreads)), dim3(mbbq::kThreads), clds,
+                       c->stream, ga);
+    HIPCHK(hipGetLastError());
+    return MBB_OK;
+}
+
+// WAIC and PSIS-LOO of a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's
+// arrays.  The bands are worked on a group at a time: two columns of the chain's length per band of a group.
+static int pw_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nsteps, const mbb_pointwise_spec *sp,
+                  const mbb_pointwise_out *o)
+{
+    using namespace mbbpw;
+    int rc;
+    if ((rc = pw_check(c, nsrc, nw, nsteps, sp, o))) return rc;
+    const int nb = c->nb;
+    const size_t cells = (size_t)nsrc * nw * nsteps, ns = (size_t)nsrc, tab = ns * nb;
+    const long long budget = (c->opt_pw_budget_mb > 0 ? c->opt_pw_budget_mb : 0) * (1ll << 20);
+    const int group = (int)std::max<long long>(1, std::min<long long>(nb, budget / (long long)(2 * cells * sizeof(double))));
+    PwArgs a;
+    memset(&a, 0, sizeof a);
+    a.chain = d_chain;
+    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
+    a.nkept = (int)(((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin);
+    a.n = (long long)nw * a.nkept;
+    a.splits = nsrc >= 256 ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (a.n + 16383) / 16384);
+    a.per_split = (a.n + a.splits - 1) / a.splits;
+    a.nb = nb; a.cells = (long long)cells;
+    a.ivar = c->data.ivar.d(); a.invcov = c->has_cov ? c->data.invcov.d() : nullptr; a.nsrc_data = c->nsrc;
+    mbb_ctx::PwWork &w = c->pw;
+    mbb_ctx::GoodWork &gw = c->good;
+    const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
+    const size_t nsel = (size_t)((group + kSelCols - 1) / kSelCols) * ns * kSelCols;
+    const size_t out_bytes = tab * sizeof(long long) + tab * 7 * sizeof(double) + tab * 2 * sizeof(int);
+    if ((rc = grow(c, w.cols, (size_t)group * 2 * cells * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.part, ns * group * a.splits * (kPartWords + 1) * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.state, ns * group * sizeof(PwState)))) return rc;
+    if ((rc = grow(c, w.sel, nsel * sizeof(mbbs::ColState)))) return rc;
+    if ((rc = grow(c, w.hist, ns * kSelCols * a.splits * mbbs::kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    if ((rc = grow(c, w.status, ns * sizeof(int)))) return rc;
+    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = grow(c, gw.mf, chunk * nb * sizeof(double)))) return rc;
+    if ((rc = ensure_sed(c, chunk, 0))) return rc;
+    a.gcol = (double *)w.cols.p; a.lwcol = a.gcol + (size_t)group * cells;
+    a.part = (double *)w.part.p; a.part2 = a.part + ns * group * a.splits * kPartWords;
+    a.state = (PwState *)w.state.p; a.sel = (mbbs::ColState *)w.sel.p;
+    a.gstatus = (const int *)w.status.p;
+    Carve ob{(char *)w.outbuf.p};
+    a.o_nused = ob.take<long long>(tab);
+    a.o_lppd = ob.take<double>(tab); a.o_pwaic = ob.take<double>(tab); a.o_elpdwaic = ob.take<double>(tab);
+    a.o_elpdloo = ob.take<double>(tab); a.o_ploo = ob.take<double>(tab); a.o_khat = ob.take<double>(tab);
+    a.o_pit = ob.take<double>(tab);
+    a.o_tail = ob.take<int>(tab); a.o_status = ob.take<int>(tab);
+    mbbq::FluxArgs fa;
+    if ((rc = good_upload_bands(c, fa))) return rc;
+    HIPCHK(hipMemsetAsync(w.status.p, 0, ns * sizeof(int), c->stream));
+    for (int b0 = 0; b0 < nb; b0 += group) {
+        a.b0 = b0; a.ng = std::min(group, nb - b0);
+        // g of the group's bands, a chunk of rows at a time: one band-flux fill per group
+        for (size_t off = 0; off < cells; off += chunk) {
+            const int n = (int)std::min(chunk, cells - off);
+            if ((rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+            if ((rc = pw_flux(c, fa, n))) return rc;
+            GArgs ga;
+            memset(&ga, 0, sizeof ga);
+            ga.off = (long long)off; ga.rows_per_src = (long long)nw * nsteps;
+            ga.b0 = b0; ga.ng = a.ng; ga.gcol = a.gcol; ga.cells = (long long)cells;
+            ga.gstatus = b0 == 0 ? (int *)w.status.p : nullptr;
+            ga.nw = nw; ga.nsteps = nsteps; ga.burn = sp->burn; ga.thin = sp->thin;
+            if ((rc = pw_g(c, fa, ga, n))) return rc;
+        }
+        const size_t ncid = ns * a.ng;
+        const dim3 gcol((unsigned)ncid, (unsigned)a.splits);
+        hipLaunchKernelGGL(k_pw_stat1, gcol, dim3(kThreads), 0, c->stream, a);
+        hipLaunchKernelGGL(k_pw_begin, dim3((unsigned)((ncid + 63) / 64)), dim3(64), 0, c->stream, a);
+        hipLaunchKernelGGL(k_pw_stat2, gcol, dim3(kThreads), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+        // the cutoffs, by the summary's select: kSelCols bands of the group per launch, as its derived columns
+        for (int q = 0; q * kSelCols < a.ng; ++q) {
+            mbbs::SumArgs s;
+            memset(&s, 0, sizeof s);
+            static_cast<mbbc::ChainView &>(s) = static_cast<const mbbc::ChainView &>(a);
+            s.ncol = std::min(kSelCols, a.ng - q * kSelCols);
+            for (int k = 0; k < s.ncol; ++k) { s.col[k] = 5 + k; s.der[k] = a.lwcol + (size_t)(q * kSelCols + k) * cells; }
+            s.state = a.sel + (size_t)q * ns * kSelCols;
+            s.hist = (unsigned int *)w.hist.p;
+            const dim3 gsel((unsigned)(ns * s.ncol), (unsigned)a.splits);
+            for (int pass = 0; pass < 8; ++pass) {
+                hipLaunchKernelGGL(mbbs::k_sum_hist, gsel, dim3(mbbs::kThreads), 0, c->stream, s, pass);
+                hipLaunchKernelGGL(mbbs::k_sum_pick, dim3((unsigned)(ns * s.ncol)), dim3(mbbs::kThreads), 0, c->stream, s);
+            }
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_pw_tail, dim3((unsigned)ncid), dim3(kThreads), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<char> host(out_bytes);
+    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Carve hb{host.data()};
+    hb.put(o->n_used, tab);
+    hb.put(o->lppd, tab); hb.put(o->p_waic, tab); hb.put(o->elpd_waic, tab); hb.put(o->elpd_loo, tab);
+    hb.put(o->p_loo, tab); hb.put(o->khat, tab); hb.put(o->loo_pit, tab);
+    hb.put(o->tail_len, tab); hb.put(o->status, tab);
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_pointwise(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
+                                   const mbb_pointwise_spec *spec, const mbb_pointwise_out *out)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if ((rc = pw_check(c, nsrc, nw, nsteps, spec, out))) return rc;        // (before the chain is read or uploaded)
+    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    return with_uploaded_chain(c, chain, nullptr, cells, [&](const double *d) {
+        return pw_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
+}
+
+extern "C" int mbb_sampler_pointwise(mbb_ctx *c, void *sp, const mbb_pointwise_spec *spec, const mbb_pointwise_out *out)
+{
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, spec && out, "cross-validated", s)) || (rc = resident_chain(s))) return rc;
+    return pw_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
+}
+
+extern "C" int mbb_pointwise_rows(mbb_ctx *c, const double *pars, int n, double *ll, int32_t *status)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!pars || n <= 0 || !ll || !status) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = good_check_ctx(c, c->nsrc))) return rc;
+    if (n % c->nsrc != 0) return fail(MBB_ERR_ARG, "in multi-source mode the rows must be nsources equal blocks");
+    const int nb = c->nb;
+    const size_t chunk = std::min<size_t>((size_t)n, (size_t)kSumChunkRows);
+    if ((rc = grow(c, c->good.mf, chunk * nb * sizeof(double)))) return rc;
+    if ((rc = grow(c, c->pw.outbuf, chunk * nb * sizeof(double) + chunk * sizeof(int)))) return rc;
+    if ((rc = ensure_sed(c, chunk, 0))) return rc;
+    mbbq::FluxArgs fa;
+    if ((rc = good_upload_bands(c, fa))) return rc;
+    Carve ob{(char *)c->pw.outbuf.p};
+    double *const d_ll = ob.take<double>(chunk * nb);
+    int *const d_status = ob.take<int>(chunk);
+    for (size_t off = 0; off < (size_t)n; off += chunk) {
+        const int m = (int)std::min(chunk, (size_t)n - off);
+        if ((rc = run_prologue(c, pars + off * 5, m, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+        if ((rc = pw_flux(c, fa, m))) return rc;
+        mbbpw::GArgs ga;
+        memset(&ga, 0, sizeof ga);
+        ga.off = (long long)off; ga.rows_per_src = n / c->nsrc;
+        ga.b0 = 0; ga.ng = nb; ga.ll_rows = d_ll; ga.row_status = d_status;
+        if ((rc = pw_g(c, fa, ga, m))) return rc;
+        HIPCHK(hipMemcpyAsync(ll + off * nb, d_ll, (size_t)m * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(status + off, d_status, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return MBB_OK;
+}
+
 // ---- the maximum of the posterior (mbb_map.hip.h) ------------------------------
 // The argument checks of mbb_map_fit: before anything is allocated, uploaded or launched.
 static int map_check(const mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out *o)
@@ -3856,6 +4065,7 @@ extern "C" int mbb_set_option(mbb_ctx *c, const char *name, long value)
     else if (!strcmp(name, "sharded_flow_sampler")) c->opt_xflow = value;
     else if (!strcmp(name, "roof_wgs_per_cu")) c->opt_roof_wgs = value;
     else if (!strcmp(name, "roof_threads")) c->opt_roof_threads = value;
+    else if (!strcmp(name, "pointwise_budget_mb")) c->opt_pw_budget_mb = value < 0 ? 0 : value;
     else return fail(MBB_ERR_ARG, "unknown option");
     return MBB_OK;
 }

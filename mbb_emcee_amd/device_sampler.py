@@ -98,7 +98,7 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_``, ``evidence_`` or ``predictions_``, nothing resident for ``convergence()`` or
+        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_``, ``loo_``, ``evidence_`` or ``predictions_``, nothing resident for ``convergence()`` or
         ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
@@ -120,6 +120,7 @@ class DeviceEnsembleSampler(object):
         self.marginals_ = None
         self.draws_ = None
         self.goodness_ = None
+        self.loo_ = None
         self.evidence_ = None
         self._drop_predictions()
         self._resident = 0                    # steps of the last run's chain that are resident on the device
@@ -230,6 +231,22 @@ class DeviceEnsembleSampler(object):
         _native.check_arg(ctx.lib.mbb_sampler_goodness(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
         return goodness.ChainGoodness(req, raw, self.nsources > 1, cens[0], self.k, nkept)
 
+    def loo(self, burn=0, thin=1):
+        """``loo.ChainLoo`` (WAIC and PSIS-LOO per source and band: elpd_loo, p_loo, the Pareto k-hat, LOO-PIT, lppd,
+        p_waic, elpd_waic) of the chain the last run left on the device -- a run with storechain=True or with
+        summary= --; the keywords are ``loo.chain_loo``'s.  No chain crosses the bus."""
+        from . import loo
+        req = loo._Request(self.lnprobfn, burn, thin)
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: loo() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset")
+        nkept = req.check_steps(self._resident, self.k)
+        ctx, h = self._handle()
+        raw = loo._Raw(self.nsources, req.ndata)
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(ctx.lib.mbb_sampler_pointwise(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return loo.ChainLoo(req, raw, self.nsources > 1, self.k, nkept)
+
     def evidence(self, n2=None, fixed=None, neff="auto", seed=None, burn=0, thin=1, tol=None, maxiter=None, keep=False):
         """``evidence.ChainEvidence`` (bridge-sampled ln Z per source with its error) of the chain the last run left on
         the device -- a run with storechain=True or with summary= --; the keywords are ``evidence.chain_evidence``'s,
@@ -300,7 +317,7 @@ class DeviceEnsembleSampler(object):
         return raw
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
-                 marginals=None, predict=None, draws=None, goodness=None, evidence=None, **unused):
+                 marginals=None, predict=None, draws=None, goodness=None, evidence=None, loo=None, **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -346,6 +363,10 @@ class DeviceEnsembleSampler(object):
         reset() and at the start of the next run).  With storechain=False it needs summary= too; burn, thin, derived
         and the derived columns' settings default to those given with summary=.
 
+        loo=True, or a dict of ``loo()``'s keywords (burn, thin): the chain of this run is cross-validated on the device
+        and ``sampler.loo_`` is the ``loo.ChainLoo`` of it (None again after reset() and at the start of the next run).
+        With storechain=False it needs summary= too; burn and thin default to those given with summary=.
+
         goodness=True, or a dict of ``goodness()``'s keywords: the chain of this run is held against the data on the
         device and ``sampler.goodness_`` is the ``goodness.ChainGoodness`` of it (None again after reset() and at the
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
@@ -356,7 +377,7 @@ class DeviceEnsembleSampler(object):
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
         with summary=."""
         self._retire()
-        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws, goodness, evidence)
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws, goodness, evidence, loo)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
@@ -376,8 +397,9 @@ class DeviceEnsembleSampler(object):
             self._resident = 0                # (what is resident is the last chunk: a part)
 
     def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None, predict=None,
-             draws=None, goodness=None, evidence=None):
-        creq = mkw = pkw = dkw = gkw = ekw = None
+             draws=None, goodness=None, evidence=None, loo=None):
+        creq = mkw = pkw = dkw = gkw = ekw = lkw = None
+        self.loo_ = None
         self.evidence_ = None
         self.convergence_ = None
         self.marginals_ = None
@@ -403,6 +425,21 @@ class DeviceEnsembleSampler(object):
                 raise ValueError("predict= with storechain=False needs summary= too: a run that neither stores "
                                  "nor summarises its chain keeps none on the device")
             preq.check_steps(int(N))
+        if loo is not None and loo is not False:
+            from . import loo as _loo
+            lkw = {} if loo is True else dict(loo)
+            if summary is not None and summary is not False and summary is not True:
+                for key in ("burn", "thin"):
+                    if key in summary:
+                        lkw.setdefault(key, summary[key])
+            unknown = set(lkw) - {"burn", "thin"}
+            if unknown:
+                raise TypeError("loo= got unexpected keyword(s) {}".format(sorted(unknown)))
+            lreq = _loo._Request(self.lnprobfn, lkw.get("burn", 0), lkw.get("thin", 1))
+            if not storechain and (summary is None or summary is False):
+                raise ValueError("loo= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device")
+            lreq.check_steps(int(N), self.k)
         if goodness is not None and goodness is not False:
             from . import goodness as _goodness
             gkw = {} if goodness is True else dict(goodness)
@@ -483,6 +520,9 @@ class DeviceEnsembleSampler(object):
                              "walkers' chain")
         if pkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be predicted from on the device: a rank holds only its own "
+                             "walkers' chain")
+        if lkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be cross-validated on the device: a rank holds only its own "
                              "walkers' chain")
         if gkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
             raise ValueError("a sharded sampler run cannot be tested for goodness of fit on the device: a rank holds "
@@ -595,6 +635,8 @@ class DeviceEnsembleSampler(object):
             self.goodness_ = self.goodness(**gkw)
         if ekw is not None:
             self.evidence_ = self.evidence(**ekw)
+        if lkw is not None:
+            self.loo_ = self.loo(**lkw)
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):

@@ -190,7 +190,7 @@ class mbb_fitter(object):
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
     def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None,
-            draws=None, goodness=None, evidence=None):
+            draws=None, goodness=None, evidence=None, loo=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
@@ -207,11 +207,15 @@ class mbb_fitter(object):
         goodness (device sampler only): True or a dict of ``goodness.chain_goodness``'s keywords -- the main chain's
         chisq against the data, posterior predictive p-value, DIC and maximum-likelihood entry,
         ``mbb_fitter.goodness``.
+        loo (device sampler only): True or a dict of ``loo.chain_loo``'s keywords -- the main chain's WAIC and PSIS-LOO
+        per band, ``mbb_fitter.loo``.
         evidence (device sampler only): True or a dict of ``evidence.chain_evidence``'s keywords -- the main chain's
         bridge-sampled ln Z per source, ``mbb_fitter.evidence``; the fitter's own fixed parameters are passed on as
         ``fixed`` unless the dict names others."""
         if evidence is not None and evidence is not False and not hasattr(self.sampler, "evidence"):
             raise ValueError("evidence= needs sampler=\"device\"")
+        if loo is not None and loo is not False and not hasattr(self.sampler, "loo"):
+            raise ValueError("loo= needs sampler=\"device\"")
         if goodness is not None and goodness is not False and not hasattr(self.sampler, "goodness"):
             raise ValueError("goodness= needs sampler=\"device\"")
         if draws is not None and draws is not False and not hasattr(self.sampler, "draws"):
@@ -268,6 +272,8 @@ class mbb_fitter(object):
             extra["draws"] = draws
         if goodness is not None and goodness is not False:
             extra["goodness"] = goodness
+        if loo is not None and loo is not False:
+            extra["loo"] = loo
         if evidence is not None and evidence is not False:
             ekw = {} if evidence is True else dict(evidence)
             ekw.setdefault("fixed", [bool(f) for f in self._fixed])
@@ -317,6 +323,8 @@ mbb_fitter.predictions = property(lambda self: getattr(self.sampler, "prediction
                                   doc="predict.ChainPredictions of the main chain when run() was given predict=, else None")
 mbb_fitter.goodness = property(lambda self: getattr(self.sampler, "goodness_", None),
                                doc="goodness.ChainGoodness of the main chain when run() was given goodness=, else None")
+mbb_fitter.loo = property(lambda self: getattr(self.sampler, "loo_", None),
+                          doc="loo.ChainLoo of the main chain when run() was given loo=, else None")
 mbb_fitter.evidence = property(lambda self: getattr(self.sampler, "evidence_", None),
                                doc="evidence.ChainEvidence of the main chain when run() was given evidence=, else None")
 mbb_fitter.draws = property(lambda self: getattr(self.sampler, "draws_", None),

@@ -58,6 +58,10 @@ def build_parser():
                    help="goodness of fit from the chain on the device (needs --sampler device): chisq of every entry "
                         "against the data, the posterior predictive p-value, DIC and the maximum-likelihood entry "
                         "printed, and added to the .npz as goodness_*")
+    p.add_argument("--loo", action="store_true",
+                   help="WAIC and PSIS leave-one-band-out cross-validation from the chain on the device (needs --sampler "
+                        "device): elpd_loo, the Pareto k-hat and the LOO-PIT of every band printed, and added to the "
+                        ".npz as loo_*")
     p.add_argument("--evidence", type=int, nargs="?", const=-1, default=None, metavar="N2",
                    help="the evidence ln Z of the fit, bridge-sampled from the chain on the device with N2 proposal draws "
                         "(default: as many as posterior samples; needs --sampler device): printed, and added to the "
@@ -143,6 +147,8 @@ def main(argv=None):
         extra["predict"] = parse_predict(a.predict)
     if a.goodness:
         extra["goodness"] = True
+    if a.loo:
+        extra["loo"] = True
     if a.evidence is not None:
         extra["evidence"] = dict(n2=None if a.evidence < 0 else a.evidence)
     if a.draws:
@@ -172,6 +178,9 @@ def main(argv=None):
     if a.goodness:
         out.update(fit.goodness.arrays())
         print(fit.goodness)
+    if a.loo:
+        out.update(fit.loo.arrays())
+        print(fit.loo)
     if a.evidence is not None:
         out.update(fit.evidence.arrays())
         print(fit.evidence)
