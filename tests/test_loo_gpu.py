@@ -10,118 +10,29 @@ Tolerances, and where they come from:
     one over this file's cases, computed here on the CPU from the reference alone; the factor covers the device's
     tree-ordered sums and an exp / log within 2 ulp that is not correctly rounded; the bound is asserted < 1e-9;
   * n_used, tail_len, status and everything said to be "the same bits": exact.
-The chains are rows of the fixture chains of tests/golden/results.npz, repeated as a stretch-move chain repeats them."""
+The chains are rows of the fixture chains of tests/golden/results.npz, repeated as a stretch-move chain repeats them.
+The likelihoods, chains, reference and comparisons are in tests/_loo_cases.py, which tests/test_loo_seams_gpu.py shares:
+that file holds the routes of several splits, partial band groups, long tails and 256 sources to the same reference."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from conftest import golden_bands, parity_record
+from conftest import parity_record
 import _loo_ref as LR
+from _loo_cases import (BANDS4, LD, TABLES, VARIANTS, _chain, _check_tables, _reference, _same_bits, _setup, _weights,
+                        _with_budget)
 
 pytestmark = pytest.mark.gpu
 
-LD = LR.LD
-VARIANTS = [("thin_walpha", True, False), ("thick_walpha", False, False),
-            ("thick_noalpha", False, True), ("thin_noalpha", True, True)]
-BANDS4 = ["PACS_160um", "SPIRE_250um", "SPIRE_500um", "SCUBA2_850um"]
-DELTA = [250.0, 500.0, 850.0]
 SCALES = (100.0, 1.0, 0.01)
-TABLES = ("n_used", "tail_len", "status") + LR.FLOATS
 NW, NSTEPS = 34, 64
-_CACHE = {}
 
 
 @pytest.fixture(scope="module")
 def mbb():
     import mbb_emcee_amd
     return mbb_emcee_amd
-
-
-def _same_bits(a, b):
-    return all(np.array_equal(getattr(a._raw, f), getattr(b._raw, f), equal_nan=True) for f in TABLES)
-
-
-def _setup(mbb, oracle, g_lnl, g_pb, chain, opthin, noalpha, case, scale=1.0):
-    """A likelihood of a band case: the data is the oracle's model at the chain's middle row, pushed 5% up and down band
-    by band, with uncertainties scale (0.1 flux + 1); cov12 gives them cfg4's correlations, cov65 is 65 delta bands
-    with correlation 0.3^|i-j|."""
-    key = ("setup", opthin, noalpha, case, scale)
-    if key in _CACHE:
-        return _CACHE[key]
-    if case.startswith("delta") or case == "cov65":
-        wave = DELTA[:int(case[5:])] if case.startswith("delta") else list(np.linspace(100.0, 900.0, 65))
-        okw = dict(wave=wave)
-        like = mbb.likelihood(opthin=opthin, noalpha=noalpha)
-        first = wave
-    else:
-        names = BANDS4 if case == "bands4" else [str(b) for b in g_lnl["cfg4/bands"]]
-        okw = dict(bands=golden_bands(g_pb, names))
-        like = mbb.likelihood(response=True, opthin=opthin, noalpha=noalpha)
-        first = names
-    nb = len(first)
-    free = dict(opthin=opthin, noalpha=noalpha, lowlim=np.full(5, -np.inf), has_uplim=[0] * 6)
-    rows = np.asarray(chain).reshape(-1, 5)
-    truth = rows[rows.shape[0] // 2]
-    model = oracle.OracleLikelihood(np.ones(nb), np.ones(nb), **okw, **free)(truth, return_flux=True)[1][0]
-    flux = model * (1.0 + 0.05 * (-1.0) ** np.arange(nb))
-    unc = scale * (0.1 * flux + 1.0)
-    cov = None
-    if case == "cov12":
-        c4 = g_lnl["cfg4/thick_walpha/cov"]
-        d = np.sqrt(np.diag(c4))
-        cov = (c4 / d[:, None] / d[None, :]) * unc[:, None] * unc[None, :]
-    if case == "cov65":
-        idx = np.arange(nb)
-        cov = 0.3 ** np.abs(idx[:, None] - idx[None, :]) * unc[:, None] * unc[None, :]
-    like.set_phot(first, flux, unc)
-    if cov is not None:
-        like.set_cov(cov)
-    _CACHE[key] = like
-    return like
-
-
-def _weights(like):
-    return dict(invcov=like._invcovmatrix) if like._has_covmatrix else dict(ivar=like._ivar)
-
-
-def _chain(g_res, name, shape, seed=1):
-    """A chain of the given [nsrc, nw, nsteps] whose rows are the fixture chain's, a third of them repeats of the row
-    before, as rejected stretch moves leave them."""
-    rows = g_res[name + "/chain"].reshape(-1, 5)
-    rng = np.random.RandomState(seed)
-    n = int(np.prod(shape))
-    pick = rng.randint(0, rows.shape[0], n)
-    out = rows[pick] * (1.0 + 1e-3 * rng.standard_normal((n, 5)))
-    out = out.reshape(shape[0] * shape[1], shape[2], 5)
-    rep = rng.uniform(size=out.shape[:2]) < 1.0 / 3.0
-    for t in range(1, shape[2]):
-        out[rep[:, t], t] = out[rep[:, t], t - 1]
-    return np.ascontiguousarray(out.reshape(tuple(shape) + (5,)))
-
-
-def _reference(mbb, like, chain4, burn=0, thin=1, dtype=LD, keep=None):
-    """_loo_ref.column of every (source, band) of a window of a chain through a one-source likelihood, fed the device's
-    own ll; z from the device's band fluxes in longdouble."""
-    from mbb_emcee_amd import goodness, loo
-    out = []
-    for src in range(chain4.shape[0]):
-        rows = np.ascontiguousarray(chain4[src][:, burn::thin].reshape(-1, 5))
-        ll, st = loo.loo_rows(like, rows)
-        model = goodness.goodness_rows(like, rows, want_flux=True)[3]
-        _, g, d = LR.ll_rows(like._flux, model, **_weights(like))
-        z = (g / np.sqrt(d)[None, :]).astype(np.float64)
-        cols = []
-        for b in range(ll.shape[1]):
-            ok = np.isfinite(ll[:, b])
-            phi = keep.get((src, b)) if keep is not None else None
-            if phi is None:
-                phi = LR.norm_cdf_mp(z[ok, b])
-                if keep is not None:
-                    keep[(src, b)] = phi
-            cols.append(LR.column(ll[:, b], z[:, b], dtype=dtype, phi=phi.astype(dtype)))
-        out.append(cols)
-    return out
 
 
 # ---------------------------------------------------------------- 1. per row
@@ -183,20 +94,6 @@ def stat_cases(mbb, oracle, g_lnl, g_pb, g_res):
     return cases
 
 
-def _check_tables(dev, ref, bound, label):
-    raw = dev._raw
-    worst = 0.0
-    for src, cols in enumerate(ref):
-        for b, r in enumerate(cols):
-            where = "%s source %d band %d" % (label, src, b)
-            assert raw.n_used[src, b] == r["n_used"], where
-            assert raw.tail_len[src, b] == r["tail_len"], where
-            assert raw.status[src, b] == r["status"], (where, raw.status[src, b], r["status"])
-            got = {k: getattr(raw, k)[src, b] for k in LR.FLOATS}
-            worst = max(worst, LR.distance(got, r))
-    return worst
-
-
 def test_statistics_against_longdouble(stat_cases):
     """2. The device's tables against the longdouble reference fed the device's own ll: counts, tail lengths and status
     exact, the floating-point outputs within 64 x the float64 restatement's own distance from longdouble."""
@@ -206,7 +103,7 @@ def test_statistics_against_longdouble(stat_cases):
     assert 0.0 < bound < 1e-9
     worst = 0.0
     for label, dev, ref, _ in stat_cases:
-        w = _check_tables(dev, ref, bound, label)
+        w = _check_tables(dev, ref, label)
         print("    %-28s worst %.3g" % (label, w))
         worst = max(worst, w)
     parity_record("loo tables vs longdouble [max(1, |x|)]", worst, bound)
@@ -244,7 +141,7 @@ def test_ties(mbb, oracle, g_lnl, g_pb, g_res, stat_cases):
     dev = mbb.chain_loo(like, triple)
     ref = _reference(mbb, like, triple)
     assert np.all(dev._raw.n_used == 300) and np.all(dev._raw.tail_len == 52)
-    assert _check_tables(dev, ref, 64 * spread, "triples") <= 64 * spread
+    assert _check_tables(dev, ref, "triples") <= 64 * spread
     # repeats of the cutoff's own row: find the cutoff entry of band 0 and plant four more copies of it
     ll = mbb.loo_rows(like, rows)[0][:, 0]
     asc = np.argsort(-ll, kind="stable")                                # ascending lw
@@ -255,20 +152,10 @@ def test_ties(mbb, oracle, g_lnl, g_pb, g_res, stat_cases):
     ref = _reference(mbb, like, strad)
     lw = np.sort(-mbb.loo_rows(like, strad.reshape(-1, 5))[0][:, 0])
     assert lw[104 - m - 1] == lw[104 - m], "the repeats do not straddle the cutoff"
-    assert _check_tables(dev, ref, 64 * spread, "straddle") <= 64 * spread
+    assert _check_tables(dev, ref, "straddle") <= 64 * spread
 
 
 # ---------------------------------------------------------------- 4. group independence
-def _with_budget(mbb, like, mb, chain, **kw):
-    from mbb_emcee_amd import _native
-    ctx = _native.analysis_context(like)
-    ctx.set_option("pointwise_budget_mb", mb)
-    try:
-        return mbb.chain_loo(like, chain, **kw)
-    finally:
-        ctx.set_option("pointwise_budget_mb", 16384)
-
-
 def test_group_independence(mbb, oracle, g_lnl, g_pb, g_res):
     """4. One band per group and all bands in one give the same bits (4 bands, and 12 with a covariance: the select
     then runs in launches of 3, 3, 3, 3 against 1 twelve times); a smaller call after a larger one; three sources of
