@@ -2250,37 +2250,90 @@ static int resident_chain(const mbb_sampler_state *s)
     return fail(MBB_ERR_STATE, "no chain of this sampler is resident on the device");
 }
 
+// The entry of an analysis of a host chain: check() has the entry's own refusals (a null chain among them where the
+// entry hears of it first), then the chain goes up and run(d_chain, d_lnprob or null) works on it.
+template <typename Check, typename Run>
+static int analyse_chain(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps, Check &&check,
+                         Run &&run)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if ((rc = check())) return rc;                                      // (before the chain is read or uploaded)
+    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
+    const size_t cells = (size_t)nsrc * nw * nsteps;
+    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
+        return run(d, lnprob ? d + cells * 5 : nullptr);
+    });
+}
+
+// ... and of the chain a sampler's last run left on the device: run(d_chain, d_lnprob or null, nsrc, nw, nsteps).
+template <typename Run>
+static int analyse_sampler(mbb_ctx *c, void *sp, bool args_ok, const char *verb, bool with_lnprob, Run &&run)
+{
+    mbb_sampler_state *s;
+    int rc;
+    if ((rc = analysed_sampler(c, sp, args_ok, verb, s)) || (rc = resident_chain(s))) return rc;
+    const double *const d = s->d_chain_out.d();
+    const size_t cells = (size_t)s->rows() * s->resident_nsteps;
+    return run(d, with_lnprob ? d + cells * 5 : nullptr, s->nsrc, s->nw, s->resident_nsteps);
+}
+
+// The window [burn::thin] of a chain's nsteps, for every analysis that has one.
+static int check_burn_thin(int burn, int thin, int nsteps)
+{
+    if (burn < 0 || burn >= nsteps || thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    return MBB_OK;
+}
+
+// Its kept steps per walker, in 64 bits: nsteps + thin may be beyond an int (at most nsteps once the window is checked).
+static long long kept_steps(int burn, int thin, int nsteps)
+{
+    return ((long long)nsteps - burn + thin - 1) / thin;
+}
+
 // The checks of an mbb_summary_spec that every analysis with derived columns makes, in the order they are made.
 static int check_window(const mbb_summary_spec *sp, int nsteps)
 {
-    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    if (const int rc = check_burn_thin(sp->burn, sp->thin, nsteps)) return rc;
     if (sp->derived & ~7) return fail(MBB_ERR_ARG, "unknown derived column");
     return MBB_OK;
 }
 
-// (in 64 bits: nsteps + thin may be beyond an int)
-static int kept_steps(const mbb_summary_spec *sp, int nsteps)
-{
-    return (int)(((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin);
-}
-
 static int check_sample_cap(const mbb_summary_spec *sp, int nw, int nsteps)
 {
-    if ((long long)nw * kept_steps(sp, nsteps) > 0xffffffffll)
+    if ((long long)nw * kept_steps(sp->burn, sp->thin, nsteps) > 0xffffffffll)
         return fail(MBB_ERR_ARG, "more than 2^32 samples per column");
     return MBB_OK;
 }
 
+// A checked window of a chain as the kernels read it (the columns and their splits are the caller's).
+static void fill_window(mbbc::ChainView &v, const double *d_chain, int nsrc, int nw, int nsteps, int burn, int thin)
+{
+    v.chain = d_chain;
+    v.nsrc = nsrc; v.nw = nw; v.nsteps = nsteps; v.burn = burn; v.thin = thin;
+    v.nkept = (int)kept_steps(burn, thin, nsteps);
+    v.n = (long long)nw * v.nkept;
+}
+
+// ... with every column cut into splits of at most 16384 samples, one split from 256 sources on: the predicted
+// fluxes, the goodness of fit and the pointwise terms.  (Not fill_chain_view's rule, which looks at the number of
+// active columns: a spec's sums must not depend on how many specs share its group, and the two columns of a goodness
+// of fit are cut as the predicted fluxes are.)
+static void fill_window_fixed(mbbc::ChainView &v, const double *d_chain, int nsrc, int nw, int nsteps, int burn, int thin)
+{
+    fill_window(v, d_chain, nsrc, nw, nsteps, burn, thin);
+    v.splits = nsrc >= 256 ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (v.n + 16383) / 16384);
+    v.per_split = (v.n + v.splits - 1) / v.splits;
+}
+
 // The columns of a checked spec's window of a chain: the active slots, and each column cut into splits of at most
 // split_samples samples whose partial results are merged -- unless the (source, column) pairs fill the device by
-// themselves: then one workgroup per column.
+// themselves: then one workgroup per column.  (With derived columns the splits may differ from a call's without: the
+// goodness of fit takes theta-bar from the five parameter columns alone for that reason.)
 static void fill_chain_view(mbbc::ChainView &v, const double *d_chain, int nsrc, int nw, int nsteps,
                             const mbb_summary_spec *sp, int split_samples)
 {
-    v.chain = d_chain;
-    v.nsrc = nsrc; v.nw = nw; v.nsteps = nsteps; v.burn = sp->burn; v.thin = sp->thin;
-    v.nkept = kept_steps(sp, nsteps);
-    v.n = (long long)nw * v.nkept;
+    fill_window(v, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
     v.ncol = 5;
     for (int k = 0; k < 5; ++k) v.col[k] = k;
     for (int k = 0; k < 3; ++k) if ((sp->derived >> k) & 1) v.col[v.ncol++] = 5 + k;
@@ -2554,15 +2607,11 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
 extern "C" int mbb_chain_summary(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
                                  const mbb_summary_spec *spec, const mbb_summary_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!chain || !lnprob || nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "bad arguments");
     // (per-source values are checked before the chain goes up; everything else where it always was, in summary_run)
-    if (spec && (spec->src_redshift || spec->src_lumdist_mpc) && (rc = summary_check_cosmology(spec, nsrc))) return rc;
-    const size_t cells = (size_t)nsrc * nw * nsteps;
-    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
-        return summary_run(c, d, d + cells * 5, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, lnprob, nsrc, nw, nsteps, [&]() -> int {
+        if (!chain || !lnprob || nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "bad arguments");
+        return spec && (spec->src_redshift || spec->src_lumdist_mpc) ? summary_check_cosmology(spec, nsrc) : MBB_OK;
+    }, [&](const double *d, const double *dl) { return summary_run(c, d, dl, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_run_summary(mbb_ctx *c, void *sp, int nsteps, double stretch_a, const mbb_summary_spec *spec,
@@ -2660,21 +2709,16 @@ static int diag_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
 extern "C" int mbb_chain_diagnostics(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
                                      const mbb_diag_spec *spec, const mbb_diag_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
-    if ((rc = diag_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
-    return with_uploaded_chain(c, chain, nullptr, (size_t)nsrc * nw * nsteps, [&](const double *d) {
-        return diag_run(c, d, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, nullptr, nsrc, nw, nsteps, [&] {
+        return !chain ? fail(MBB_ERR_ARG, "bad arguments") : diag_check(nsrc, nw, nsteps, spec, out);
+    }, [&](const double *d, const double *) { return diag_run(c, d, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_diagnostics(mbb_ctx *c, void *sp, const mbb_diag_spec *spec, const mbb_diag_out *out)
 {
-    mbb_sampler_state *s;
-    int rc;
-    if ((rc = analysed_sampler(c, sp, spec && out, "diagnosed", s)) || (rc = resident_chain(s))) return rc;
-    return diag_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return analyse_sampler(c, sp, spec && out, "diagnosed", false, [&](const double *d, const double *, int nsrc, int nw, int nsteps) {
+        return diag_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 // ---- binned marginals of a chain (mbb_marginals.hip.h) ------------------------
@@ -2778,30 +2822,19 @@ static int marg_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
 extern "C" int mbb_chain_marginals(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
                                    const mbb_marginals_spec *spec, const mbb_marginals_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
-    if ((rc = marg_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
-    return with_uploaded_chain(c, chain, nullptr, (size_t)nsrc * nw * nsteps, [&](const double *d) {
-        return marg_run(c, d, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, nullptr, nsrc, nw, nsteps, [&] {
+        return !chain ? fail(MBB_ERR_ARG, "bad arguments") : marg_check(nsrc, nw, nsteps, spec, out);
+    }, [&](const double *d, const double *) { return marg_run(c, d, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_marginals(mbb_ctx *c, void *sp, const mbb_marginals_spec *spec, const mbb_marginals_out *out)
 {
-    mbb_sampler_state *s;
-    int rc;
-    if ((rc = analysed_sampler(c, sp, spec && out, "binned", s)) || (rc = resident_chain(s))) return rc;
-    return marg_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return analyse_sampler(c, sp, spec && out, "binned", false, [&](const double *d, const double *, int nsrc, int nw, int nsteps) {
+        return marg_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 // ---- predicted fluxes of a chain (mbb_predict.hip.h) ------------------------
-// Kept steps per walker of a prediction's window, in 64 bits: burn + thin may be beyond an int.
-static long long pred_kept_steps(const mbb_predict_spec *sp, int nsteps)
-{
-    return ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
-}
-
 // The argument checks of a prediction call: before anything is allocated, uploaded or launched.
 static int pred_check(int nsrc, int nw, int nsteps, const mbb_predict_spec *sp, const mbb_predict_out *o)
 {
@@ -2828,9 +2861,9 @@ static int pred_check(int nsrc, int nw, int nsteps, const mbb_predict_spec *sp, 
     if (sp->npct < 1 || sp->npct > mbbs::kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per prediction call");
     for (int k = 0; k < sp->npct; ++k)
         if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
-    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
+    if (const int rc = check_burn_thin(sp->burn, sp->thin, nsteps)) return rc;
     if (!(sp->wavenorm >= 0.0 && sp->wavenorm < INFINITY)) return fail(MBB_ERR_ARG, "wavenorm must be positive (0: the context's)");
-    if ((long long)nw * pred_kept_steps(sp, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
+    if ((long long)nw * kept_steps(sp->burn, sp->thin, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
     if ((size_t)nsrc * mbbp::kGroup > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
     return MBB_OK;
 }
@@ -2845,16 +2878,9 @@ static int pred_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     const int nspec = sp->nspec, ns = sp->sample_off[nspec];
     const size_t cells = (size_t)nsrc * nw * nsteps, sn = (size_t)nsrc * nspec, np = (size_t)sp->npct;
     const double wavenorm = sp->wavenorm > 0.0 ? sp->wavenorm : c->wavenorm;
-    // the window of the chain and a column's splits.  (Not fill_chain_view's rule, which looks at the number of active
-    // columns: a spec's sums must not depend on how many specs share its group.)
     mbbs::SumArgs a;
     memset(&a, 0, sizeof a);
-    a.chain = d_chain;
-    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
-    a.nkept = (int)pred_kept_steps(sp, nsteps);          // (at most nsteps)
-    a.n = (long long)nw * a.nkept;
-    a.splits = nsrc >= 256 ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (a.n + 16383) / 16384);
-    a.per_split = (a.n + a.splits - 1) / a.splits;
+    fill_window_fixed(a, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
     a.npct = sp->npct;
     for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
     const int ngmax = std::min(nspec, kGroup);
@@ -2952,21 +2978,16 @@ static int pred_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
 extern "C" int mbb_chain_predict(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
                                  const mbb_predict_spec *spec, const mbb_predict_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
-    if ((rc = pred_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
-    return with_uploaded_chain(c, chain, nullptr, (size_t)nsrc * nw * nsteps, [&](const double *d) {
-        return pred_run(c, d, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, nullptr, nsrc, nw, nsteps, [&] {
+        return !chain ? fail(MBB_ERR_ARG, "bad arguments") : pred_check(nsrc, nw, nsteps, spec, out);
+    }, [&](const double *d, const double *) { return pred_run(c, d, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_predict(mbb_ctx *c, void *sp, const mbb_predict_spec *spec, const mbb_predict_out *out)
 {
-    mbb_sampler_state *s;
-    int rc;
-    if ((rc = analysed_sampler(c, sp, spec && out, "predicted from", s)) || (rc = resident_chain(s))) return rc;
-    return pred_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return analyse_sampler(c, sp, spec && out, "predicted from", false, [&](const double *d, const double *, int nsrc, int nw, int nsteps) {
+        return pred_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 // ---- posterior draws of a chain (mbb_draws.hip.h) ------------------------
@@ -3051,23 +3072,16 @@ static int draws_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, 
 extern "C" int mbb_chain_draws(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
                                const mbb_draws_spec *spec, const mbb_draws_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
-    if ((rc = draws_check(nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
-    const size_t cells = (size_t)nsrc * nw * nsteps;
-    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
-        return draws_run(c, d, lnprob ? d + cells * 5 : nullptr, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, lnprob, nsrc, nw, nsteps, [&] {
+        return !chain ? fail(MBB_ERR_ARG, "bad arguments") : draws_check(nsrc, nw, nsteps, spec, out);
+    }, [&](const double *d, const double *dl) { return draws_run(c, d, dl, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_draws(mbb_ctx *c, void *sp, const mbb_draws_spec *spec, const mbb_draws_out *out)
 {
-    mbb_sampler_state *s;
-    int rc;
-    if ((rc = analysed_sampler(c, sp, spec && out, "drawn from", s)) || (rc = resident_chain(s))) return rc;
-    const size_t cells = (size_t)s->rows() * s->resident_nsteps;
-    return draws_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return analyse_sampler(c, sp, spec && out, "drawn from", true, [&](const double *d, const double *dl, int nsrc, int nw, int nsteps) {
+        return draws_run(c, d, dl, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 extern "C" int mbb_draw_indices(mbb_ctx *c, int nsrc, int nw, int nsteps, int burn, int thin, int n, int how,
@@ -3107,11 +3121,6 @@ static int good_check_ctx(const mbb_ctx *c, int nsrc)
     return MBB_OK;
 }
 
-static long long good_kept_steps(const mbb_goodness_spec *sp, int nsteps)
-{
-    return ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
-}
-
 // The argument checks of a goodness call: before anything is allocated, uploaded or launched.
 static int good_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_goodness_spec *sp, const mbb_goodness_out *o)
 {
@@ -3124,8 +3133,8 @@ static int good_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_
     if (sp->npct < 1 || sp->npct > mbbs::kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per goodness call");
     for (int k = 0; k < sp->npct; ++k)
         if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
-    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
-    if ((long long)nw * good_kept_steps(sp, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
+    if ((rc = check_burn_thin(sp->burn, sp->thin, nsteps))) return rc;
+    if ((long long)nw * kept_steps(sp->burn, sp->thin, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
     if ((size_t)nsrc * 5 > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
     return MBB_OK;
 }
@@ -3159,9 +3168,8 @@ static int good_upload_bands(mbb_ctx *c, mbbq::FluxArgs &fa)
     return MBB_OK;
 }
 
-// Band fluxes, chisq and q of the n rows whose records launch_prologue has just made: k_good_flux, then k_good_chi.
-// ca carries where the results go; the rows, the band fluxes and the data are filled in here.
-static int good_eval(mbb_ctx *c, mbbq::FluxArgs &fa, mbbq::ChiArgs &ca, int n)
+// Band fluxes of the n rows whose records launch_prologue has just made: k_good_flux.
+static int good_flux(mbb_ctx *c, mbbq::FluxArgs &fa, int n)
 {
     using namespace mbbq;
     fa.wk = c->sed.wk.d(); fa.status = c->sed.status.d();
@@ -3176,13 +3184,29 @@ static int good_eval(mbb_ctx *c, mbbq::FluxArgs &fa, mbbq::ChiArgs &ca, int n)
             hipLaunchKernelGGL((k_good_flux<decltype(OT)::value, decltype(NA)::value, false>), grid, dim3(kThreads), 0, c->stream, fa);
     });
     HIPCHK(hipGetLastError());
-    ca.mf = fa.mf; ca.status = fa.status; ca.n = n; ca.nb = c->nb;
-    ca.nsrc_data = c->nsrc;
-    ca.flux = c->data.flux.d(); ca.ivar = c->data.ivar.d();
-    ca.invcov = c->has_cov ? c->data.invcov.d() : nullptr;
-    ca.cov_in_lds = c->has_cov && c->nb <= kLdsCov;
-    const size_t clds = ca.cov_in_lds ? (size_t)c->nb * c->nb * sizeof(double) : 0;
-    hipLaunchKernelGGL(k_good_chi, grid, dim3(kThreads), clds, c->stream, ca);
+    return MBB_OK;
+}
+
+// Those band fluxes and the context's data as the kernel behind them reads both (mbbq::ChiArgs, mbbpw::GArgs: the same
+// fields); returns the LDS bytes its launch needs for the covariance.
+template <typename Args>
+static size_t bind_data(const mbb_ctx *c, const mbbq::FluxArgs &fa, Args &a, int n)
+{
+    a.mf = fa.mf; a.status = fa.status; a.n = n; a.nb = c->nb;
+    a.nsrc_data = c->nsrc;
+    a.flux = c->data.flux.d(); a.ivar = c->data.ivar.d();
+    a.invcov = c->has_cov ? c->data.invcov.d() : nullptr;
+    a.cov_in_lds = c->has_cov && c->nb <= mbbq::kLdsCov;
+    return a.cov_in_lds ? (size_t)c->nb * c->nb * sizeof(double) : 0;
+}
+
+// ... and their chisq and q: k_good_flux, then k_good_chi.  ca carries where the results go.
+static int good_eval(mbb_ctx *c, mbbq::FluxArgs &fa, mbbq::ChiArgs &ca, int n)
+{
+    using namespace mbbq;
+    if (const int rc = good_flux(c, fa, n)) return rc;
+    const size_t clds = bind_data(c, fa, ca, n);
+    hipLaunchKernelGGL(k_good_chi, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), clds, c->stream, ca);
     HIPCHK(hipGetLastError());
     return MBB_OK;
 }
@@ -3198,22 +3222,18 @@ static int good_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, i
     const int nb = c->nb;
     const size_t cells = (size_t)nsrc * nw * nsteps, s2 = (size_t)nsrc * 2, ns = (size_t)nsrc, np = (size_t)sp->npct;
     // theta-bar: the five parameter columns exactly as a summary of this window with neither clipping nor derived
-    // columns reduces them (fill_chain_view chooses the splits from nsrc * ncol: with derived columns they may differ)
+    // columns reduces them
     mbb_summary_spec ss;
     memset(&ss, 0, sizeof ss);
     ss.burn = sp->burn; ss.thin = sp->thin;
     mbbs::SumArgs a5;
     memset(&a5, 0, sizeof a5);
     fill_chain_view(a5, d_chain, nsrc, nw, nsteps, &ss, 16384);
-    // the two columns: the window and a column's splits as for the predicted fluxes
+    // the two columns
     mbbs::SumArgs a;
     memset(&a, 0, sizeof a);
-    a.chain = d_chain; a.lnprob = d_lnprob;
-    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
-    a.nkept = (int)good_kept_steps(sp, nsteps);
-    a.n = (long long)nw * a.nkept;
-    a.splits = nsrc >= 256 ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (a.n + 16383) / 16384);
-    a.per_split = (a.n + a.splits - 1) / a.splits;
+    fill_window_fixed(a, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
+    a.lnprob = d_lnprob;
     a.npct = sp->npct;
     for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
     a.ncol = 2; a.col[0] = 5; a.col[1] = 6;
@@ -3318,62 +3338,67 @@ static int good_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, i
 extern "C" int mbb_chain_goodness(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
                                   const mbb_goodness_spec *spec, const mbb_goodness_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
-    if ((rc = good_check(c, nsrc, nw, nsteps, spec, out))) return rc;      // (before the chain is uploaded)
-    const size_t cells = (size_t)nsrc * nw * nsteps;
-    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
-        return good_run(c, d, lnprob ? d + cells * 5 : nullptr, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, lnprob, nsrc, nw, nsteps, [&] {
+        return !chain ? fail(MBB_ERR_ARG, "bad arguments") : good_check(c, nsrc, nw, nsteps, spec, out);
+    }, [&](const double *d, const double *dl) { return good_run(c, d, dl, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_goodness(mbb_ctx *c, void *sp, const mbb_goodness_spec *spec, const mbb_goodness_out *out)
 {
-    mbb_sampler_state *s;
-    int rc;
-    if ((rc = analysed_sampler(c, sp, spec && out, "tested for goodness of fit", s)) || (rc = resident_chain(s))) return rc;
-    const size_t cells = (size_t)s->rows() * s->resident_nsteps;
-    return good_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return analyse_sampler(c, sp, spec && out, "tested for goodness of fit", true,
+                           [&](const double *d, const double *dl, int nsrc, int nw, int nsteps) {
+        return good_run(c, d, dl, nsrc, nw, nsteps, spec, out);
+    });
+}
+
+// The rows entries' shell (mbb_goodness_rows, mbb_pointwise_rows): n parameter rows of the context's sources, a chunk at
+// a time -- their records by run_prologue, then eval(fa, off, m, chunk) evaluates rows [off, off + m) and enqueues the
+// copies out of outbuf (null with a null context), which holds per row of a chunk a double per band and extra_bytes.
+template <typename Eval>
+static int eval_rows(mbb_ctx *c, const double *pars, int n, bool args_ok, DevBuf *outbuf, size_t extra_bytes, Eval &&eval)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if (!pars || n <= 0 || !args_ok) return fail(MBB_ERR_ARG, "bad arguments");
+    if ((rc = good_check_ctx(c, c->nsrc))) return rc;
+    if (n % c->nsrc != 0) return fail(MBB_ERR_ARG, "in multi-source mode the rows must be nsources equal blocks");
+    const size_t chunk = std::min<size_t>((size_t)n, (size_t)kSumChunkRows);
+    if ((rc = grow(c, c->good.mf, chunk * c->nb * sizeof(double)))) return rc;
+    if ((rc = grow(c, *outbuf, chunk * (c->nb * sizeof(double) + extra_bytes)))) return rc;
+    if ((rc = ensure_sed(c, chunk, 0))) return rc;
+    mbbq::FluxArgs fa;
+    if ((rc = good_upload_bands(c, fa))) return rc;
+    for (size_t off = 0; off < (size_t)n; off += chunk) {
+        const int m = (int)std::min(chunk, (size_t)n - off);
+        if ((rc = run_prologue(c, pars + off * 5, m, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+        if ((rc = eval(fa, off, m, chunk))) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return MBB_OK;
 }
 
 extern "C" int mbb_goodness_rows(mbb_ctx *c, const double *pars, int n, double *chisq, double *q, int32_t *status,
                                  double *model_flux)
 {
     using namespace mbbq;
-    int rc = use(c);
-    if (rc) return rc;
-    if (!pars || n <= 0 || !chisq || !q || !status) return fail(MBB_ERR_ARG, "bad arguments");
-    if ((rc = good_check_ctx(c, c->nsrc))) return rc;
-    if (n % c->nsrc != 0) return fail(MBB_ERR_ARG, "in multi-source mode the rows must be nsources equal blocks");
-    const int nb = c->nb;
-    const size_t chunk = std::min<size_t>((size_t)n, (size_t)kSumChunkRows);
-    mbb_ctx::GoodWork &w = c->good;
-    const size_t out_bytes = chunk * (2 + (size_t)nb) * sizeof(double) + chunk * sizeof(int);
-    if ((rc = grow(c, w.mf, chunk * nb * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
-    if ((rc = ensure_sed(c, chunk, 0))) return rc;
-    FluxArgs fa;
-    if ((rc = good_upload_bands(c, fa))) return rc;
-    Carve ob{(char *)w.outbuf.p};
-    double *const d_chisq = ob.take<double>(chunk), *const d_q = ob.take<double>(chunk), *const d_mf = ob.take<double>(chunk * nb);
-    int *const d_status = ob.take<int>(chunk);
-    for (size_t off = 0; off < (size_t)n; off += chunk) {
-        const int m = (int)std::min(chunk, (size_t)n - off);
-        if ((rc = run_prologue(c, pars + off * 5, m, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+    return eval_rows(c, pars, n, chisq && q && status, c ? &c->good.outbuf : nullptr, 2 * sizeof(double) + sizeof(int),
+                     [&](FluxArgs &fa, size_t off, int m, size_t chunk) -> int {
+        const int nb = c->nb;
+        Carve ob{(char *)c->good.outbuf.p};
+        double *const d_chisq = ob.take<double>(chunk), *const d_q = ob.take<double>(chunk), *const d_mf = ob.take<double>(chunk * nb);
+        int *const d_status = ob.take<int>(chunk);
         ChiArgs ca;
         memset(&ca, 0, sizeof ca);
         ca.off = (long long)off; ca.rows_per_src = n / c->nsrc;
         ca.chisq = d_chisq; ca.q = d_q; ca.row_status = d_status; ca.mf_rows = model_flux ? d_mf : nullptr;
-        if ((rc = good_eval(c, fa, ca, m))) return rc;
+        if (const int rc = good_eval(c, fa, ca, m)) return rc;
         HIPCHK(hipMemcpyAsync(chisq + off, d_chisq, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(q + off, d_q, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(status + off, d_status, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         if (model_flux)
             HIPCHK(hipMemcpyAsync(model_flux + off * nb, d_mf, (size_t)m * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return MBB_OK;
+        return MBB_OK;
+    });
 }
 
 // ---- out-of-sample fit of a chain (mbb_pointwise.hip.h) -----------------------
@@ -3386,42 +3411,18 @@ static int pw_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_po
     if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
     int rc;
     if ((rc = good_check_ctx(c, nsrc))) return rc;
-    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
-    const long long kept = ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
+    if ((rc = check_burn_thin(sp->burn, sp->thin, nsteps))) return rc;
+    const long long kept = kept_steps(sp->burn, sp->thin, nsteps);
     if ((long long)nw * kept > MBB_PW_MAX_WINDOW || mbbps::ps_tail_len((long long)nw * kept) > mbbps::kTailMax)
         return fail(MBB_ERR_ARG, "the window's tail would be longer than one workgroup sorts (MBB_PW_MAX_WINDOW entries per source)");
     if ((size_t)nsrc * c->nb > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
     return MBB_OK;
 }
 
-// k_good_flux on the n rows whose records launch_prologue has just made, as good_eval launches it
-static int pw_flux(mbb_ctx *c, mbbq::FluxArgs &fa, int n)
-{
-    using namespace mbbq;
-    fa.wk = c->sed.wk.d(); fa.status = c->sed.status.d();
-    fa.n = n; fa.mf = (double *)c->good.mf.p;
-    const bool stage = fa.nmany > 0 && fa.nsamples <= kLdsSamples;
-    const size_t lds = stage ? (size_t)fa.nsamples * 3 * sizeof(double) : 0;
-    const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
-    dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
-        if (stage)
-            hipLaunchKernelGGL((k_good_flux<decltype(OT)::value, decltype(NA)::value, true>), grid, dim3(kThreads), lds, c->stream, fa);
-        else
-            hipLaunchKernelGGL((k_good_flux<decltype(OT)::value, decltype(NA)::value, false>), grid, dim3(kThreads), 0, c->stream, fa);
-    });
-    HIPCHK(hipGetLastError());
-    return MBB_OK;
-}
-
-// ... and k_pw_g on their band fluxes.  ga carries where the results go and the group.
+// k_pw_g on the band fluxes good_flux has just made of n rows.  ga carries where the results go and the group.
 static int pw_g(mbb_ctx *c, const mbbq::FluxArgs &fa, mbbpw::GArgs &ga, int n)
 {
-    ga.mf = fa.mf; ga.status = fa.status; ga.n = n; ga.nb = c->nb;
-    ga.nsrc_data = c->nsrc;
-    ga.flux = c->data.flux.d(); ga.ivar = c->data.ivar.d();
-    ga.invcov = c->has_cov ? c->data.invcov.d() : nullptr;
-    ga.cov_in_lds = c->has_cov && c->nb <= mbbq::kLdsCov;
-    const size_t clds = ga.cov_in_lds ? (size_t)c->nb * c->nb * sizeof(double) : 0;
+    const size_t clds = bind_data(c, fa, ga, n);
     hipLaunchKernelGGL(mbbpw::k_pw_g, dim3((unsigned)((n + mbbq::kThreads - 1) / mbbq::kThreads)), dim3(mbbq::kThreads), clds,
                        c->stream, ga);
     HIPCHK(hipGetLastError());
@@ -3442,12 +3443,7 @@ static int pw_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nstep
     const int group = (int)std::max<long long>(1, std::min<long long>(nb, budget / (long long)(2 * cells * sizeof(double))));
     PwArgs a;
     memset(&a, 0, sizeof a);
-    a.chain = d_chain;
-    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
-    a.nkept = (int)(((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin);
-    a.n = (long long)nw * a.nkept;
-    a.splits = nsrc >= 256 ? 1 : (int)std::min<long long>(mbbc::kMaxSplits, (a.n + 16383) / 16384);
-    a.per_split = (a.n + a.splits - 1) / a.splits;
+    fill_window_fixed(a, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
     a.nb = nb; a.cells = (long long)cells;
     a.ivar = c->data.ivar.d(); a.invcov = c->has_cov ? c->data.invcov.d() : nullptr; a.nsrc_data = c->nsrc;
     mbb_ctx::PwWork &w = c->pw;
@@ -3483,7 +3479,7 @@ static int pw_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nstep
         for (size_t off = 0; off < cells; off += chunk) {
             const int n = (int)std::min(chunk, cells - off);
             if ((rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
-            if ((rc = pw_flux(c, fa, n))) return rc;
+            if ((rc = good_flux(c, fa, n))) return rc;
             GArgs ga;
             memset(&ga, 0, sizeof ga);
             ga.off = (long long)off; ga.rows_per_src = (long long)nw * nsteps;
@@ -3531,45 +3527,27 @@ static int pw_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nstep
 extern "C" int mbb_chain_pointwise(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
                                    const mbb_pointwise_spec *spec, const mbb_pointwise_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if ((rc = pw_check(c, nsrc, nw, nsteps, spec, out))) return rc;        // (before the chain is read or uploaded)
-    if (!chain) return fail(MBB_ERR_ARG, "bad arguments");
-    const size_t cells = (size_t)nsrc * nw * nsteps;
-    return with_uploaded_chain(c, chain, nullptr, cells, [&](const double *d) {
-        return pw_run(c, d, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, nullptr, nsrc, nw, nsteps, [&] { return pw_check(c, nsrc, nw, nsteps, spec, out); },
+                         [&](const double *d, const double *) { return pw_run(c, d, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_pointwise(mbb_ctx *c, void *sp, const mbb_pointwise_spec *spec, const mbb_pointwise_out *out)
 {
-    mbb_sampler_state *s;
-    int rc;
-    if ((rc = analysed_sampler(c, sp, spec && out, "cross-validated", s)) || (rc = resident_chain(s))) return rc;
-    return pw_run(c, s->d_chain_out.d(), s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return analyse_sampler(c, sp, spec && out, "cross-validated", false, [&](const double *d, const double *, int nsrc, int nw, int nsteps) {
+        return pw_run(c, d, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 extern "C" int mbb_pointwise_rows(mbb_ctx *c, const double *pars, int n, double *ll, int32_t *status)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!pars || n <= 0 || !ll || !status) return fail(MBB_ERR_ARG, "bad arguments");
-    if ((rc = good_check_ctx(c, c->nsrc))) return rc;
-    if (n % c->nsrc != 0) return fail(MBB_ERR_ARG, "in multi-source mode the rows must be nsources equal blocks");
-    const int nb = c->nb;
-    const size_t chunk = std::min<size_t>((size_t)n, (size_t)kSumChunkRows);
-    if ((rc = grow(c, c->good.mf, chunk * nb * sizeof(double)))) return rc;
-    if ((rc = grow(c, c->pw.outbuf, chunk * nb * sizeof(double) + chunk * sizeof(int)))) return rc;
-    if ((rc = ensure_sed(c, chunk, 0))) return rc;
-    mbbq::FluxArgs fa;
-    if ((rc = good_upload_bands(c, fa))) return rc;
-    Carve ob{(char *)c->pw.outbuf.p};
-    double *const d_ll = ob.take<double>(chunk * nb);
-    int *const d_status = ob.take<int>(chunk);
-    for (size_t off = 0; off < (size_t)n; off += chunk) {
-        const int m = (int)std::min(chunk, (size_t)n - off);
-        if ((rc = run_prologue(c, pars + off * 5, m, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
-        if ((rc = pw_flux(c, fa, m))) return rc;
+    return eval_rows(c, pars, n, ll && status, c ? &c->pw.outbuf : nullptr, sizeof(int),
+                     [&](mbbq::FluxArgs &fa, size_t off, int m, size_t chunk) -> int {
+        const int nb = c->nb;
+        Carve ob{(char *)c->pw.outbuf.p};
+        double *const d_ll = ob.take<double>(chunk * nb);
+        int *const d_status = ob.take<int>(chunk);
+        int rc;
+        if ((rc = good_flux(c, fa, m))) return rc;
         mbbpw::GArgs ga;
         memset(&ga, 0, sizeof ga);
         ga.off = (long long)off; ga.rows_per_src = n / c->nsrc;
@@ -3577,9 +3555,8 @@ extern "C" int mbb_pointwise_rows(mbb_ctx *c, const double *pars, int n, double 
         if ((rc = pw_g(c, fa, ga, m))) return rc;
         HIPCHK(hipMemcpyAsync(ll + off * nb, d_ll, (size_t)m * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(status + off, d_status, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return MBB_OK;
+        return MBB_OK;
+    });
 }
 
 // ---- the maximum of the posterior (mbb_map.hip.h) ------------------------------
@@ -3710,11 +3687,6 @@ static_assert(mbbev::kConverged == MBB_EV_CONVERGED && mbbev::kMaxIterHit == MBB
               mbbev::kCovSingular == MBB_EV_COV_SINGULAR && mbbev::kPostLeftOut == MBB_EV_POST_LEFT_OUT &&
               mbbev::kNoOverlap == MBB_EV_NO_OVERLAP && mbbev::kAllHeld == MBB_EV_ALL_HELD &&
               mbbev::kHeldShift == MBB_EV_HELD_SHIFT, "the header's status bits are the kernels'");
-static long long ev_kept_steps(const mbb_evidence_spec *sp, int nsteps)
-{
-    return ((long long)nsteps - sp->burn + sp->thin - 1) / sp->thin;
-}
-
 // The argument checks of an evidence call: before anything is allocated, uploaded or launched.
 static int ev_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_evidence_spec *sp, const mbb_evidence_out *o)
 {
@@ -3726,8 +3698,8 @@ static int ev_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_ev
     if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
     int rc;
     if ((rc = good_check_ctx(c, nsrc))) return rc;
-    if (sp->burn < 0 || sp->burn >= nsteps || sp->thin < 1) return fail(MBB_ERR_ARG, "bad burn / thin");
-    const long long nkept = ev_kept_steps(sp, nsteps);
+    if ((rc = check_burn_thin(sp->burn, sp->thin, nsteps))) return rc;
+    const long long nkept = kept_steps(sp->burn, sp->thin, nsteps);
     if (nkept < 2) return fail(MBB_ERR_ARG, "an evidence needs two kept steps at least: one half fits the proposal, the other is bridged to");
     if (sp->n2 < 0 || sp->n2 > MBB_EV_MAX_N2) return fail(MBB_ERR_ARG, "0 to 2^22 proposal draws per source");
     if ((long long)nw * nkept > 0x7fffffffll) return fail(MBB_ERR_ARG, "more than 2^31 - 1 samples per source");
@@ -3755,10 +3727,8 @@ static int evidence_run(mbb_ctx *c, const double *d_chain, const double *d_lnpro
     if (!d_lnprob) return fail(MBB_ERR_ARG, "an evidence needs the chain's lnprob");
     EvArgs a;
     memset(&a, 0, sizeof a);
-    a.chain = d_chain; a.lnprob = d_lnprob;
-    a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.thin = sp->thin;
-    a.nkept = (int)ev_kept_steps(sp, nsteps);
-    a.n = (long long)nw * a.nkept;
+    fill_window(a, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
+    a.lnprob = d_lnprob;
     a.nfit = a.nkept / 2; a.n1k = a.nkept - a.nfit;
     a.n1max = (long long)nw * a.n1k;
     a.n2 = sp->n2 ? sp->n2 : (int)a.n1max;
@@ -3848,23 +3818,18 @@ static int evidence_run(mbb_ctx *c, const double *d_chain, const double *d_lnpro
 extern "C" int mbb_chain_evidence(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
                                   const mbb_evidence_spec *spec, const mbb_evidence_out *out)
 {
-    int rc = use(c);
-    if (rc) return rc;
-    if (!chain || !lnprob) return fail(MBB_ERR_ARG, "bad arguments: an evidence needs the chain and its lnprob");
-    if ((rc = ev_check(c, nsrc, nw, nsteps, spec, out))) return rc;        // (before the chain is uploaded)
-    const size_t cells = (size_t)nsrc * nw * nsteps;
-    return with_uploaded_chain(c, chain, lnprob, cells, [&](const double *d) {
-        return evidence_run(c, d, d + cells * 5, nsrc, nw, nsteps, spec, out);
-    });
+    return analyse_chain(c, chain, lnprob, nsrc, nw, nsteps, [&] {
+        if (!chain || !lnprob) return fail(MBB_ERR_ARG, "bad arguments: an evidence needs the chain and its lnprob");
+        return ev_check(c, nsrc, nw, nsteps, spec, out);
+    }, [&](const double *d, const double *dl) { return evidence_run(c, d, dl, nsrc, nw, nsteps, spec, out); });
 }
 
 extern "C" int mbb_sampler_evidence(mbb_ctx *c, void *sp, const mbb_evidence_spec *spec, const mbb_evidence_out *out)
 {
-    mbb_sampler_state *s;
-    int rc;
-    if ((rc = analysed_sampler(c, sp, spec && out, "bridged to an evidence", s)) || (rc = resident_chain(s))) return rc;
-    const size_t cells = (size_t)s->rows() * s->resident_nsteps;
-    return evidence_run(c, s->d_chain_out.d(), s->d_chain_out.d() + cells * 5, s->nsrc, s->nw, s->resident_nsteps, spec, out);
+    return analyse_sampler(c, sp, spec && out, "bridged to an evidence", true,
+                           [&](const double *d, const double *dl, int nsrc, int nw, int nsteps) {
+        return evidence_run(c, d, dl, nsrc, nw, nsteps, spec, out);
+    });
 }
 
 // Measurement helper: the empirical roof of the sample arithmetic (k_roof).

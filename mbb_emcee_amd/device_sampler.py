@@ -9,11 +9,12 @@ of N steps is 2N dependent launches enqueued back to back; the host only sees
 the chain at the end.  emcee itself is not part of the reference tree, so parity
 with it is statistical.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 from .ensemble import integrated_time
 
 __all__ = ["DeviceEnsembleSampler", "accepted_by_step"]
@@ -51,6 +52,95 @@ class _OpenSample(object):
     """What a suspended sample() generator has to leave behind when it ends or is retired."""
     __slots__ = ("live", "it_prev", "n_prev", "made", "acc_made", "storechain", "big_c", "big_l", "kept_c", "kept_l",
                  "single")
+
+
+def _request_predict(s, kw):
+    from . import predict
+    return predict._Request(s.lnprobfn, kw["specs"], _analysis.quantiles(kw.get("percentile", 68.3), kw.get("percentiles", ()))[1],
+                            kw.get("burn", 0), kw.get("thin", 1), kw.get("clip"), kw.get("wavenorm"))
+
+
+def _request_loo(s, kw):
+    from . import loo
+    return loo._Request(s.lnprobfn, kw.get("burn", 0), kw.get("thin", 1))
+
+
+def _request_goodness(s, kw):
+    from . import goodness
+    return goodness._Request(s.lnprobfn, _analysis.quantiles(kw.get("percentile", 68.3), kw.get("percentiles", ()))[1],
+                             kw.get("burn", 0), kw.get("thin", 1))
+
+
+def _request_evidence(s, kw):
+    from . import evidence
+    return evidence._Request(s.lnprobfn, kw.get("n2"), kw.get("fixed"), kw.get("seed", s.seed), kw.get("burn", 0),
+                             kw.get("thin", 1), kw.get("tol", evidence.TOL), kw.get("maxiter", evidence.MAXITER))
+
+
+def _request_marginals(s, kw):
+    from . import marginals
+    return marginals._Request(nsources=s.nsources, **kw)
+
+
+def _request_draws(s, kw):
+    from . import draws
+    kw.setdefault("seed", s.seed)
+    return draws._Request(nsources=s.nsources, **kw)
+
+
+def _request_convergence(s, kw):
+    from . import diagnostics
+    return diagnostics._Request(**kw)
+
+
+def _check_steps(s, req, kw, nsteps):
+    req.check_steps(nsteps)
+
+
+def _check_loo(s, req, kw, nsteps):
+    req.check_steps(nsteps, s.k)
+
+
+def _check_evidence(s, req, kw, nsteps):
+    req.check_steps(nsteps)
+    if not isinstance(kw.get("neff", "auto"), str):
+        req.set_neff(kw["neff"], s.nsources)
+    elif kw.get("neff", "auto") != "auto":
+        raise ValueError("neff must be 'auto', None, a number or one number per source")
+
+
+# One analysis of the chain a run leaves on the device, as run_mcmc's keyword of that name is read:
+#   first    -- the argument a value that is no dict stands for (None: True stands for no keywords);
+#   needs    -- the refusal when ``first`` is missing, where it has to be there;
+#   inherits -- the keys of summary= that are the defaults of its own;
+#   allowed  -- its keywords, where run_mcmc names the unknown ones itself (None: the request's constructor does);
+#   request  -- (sampler, keywords) -> the module's _Request, which checks all it can before a device is touched;
+#   check    -- (sampler, request, keywords, nsteps): what the number of steps of the run decides;
+#   verb     -- what a sharded run cannot be;
+#   attr, method -- the attribute the result goes to, and the method that makes it from the resident chain.
+_Analysis = collections.namedtuple("_Analysis", "first needs inherits allowed request check verb attr method")
+_WINDOW = ("burn", "thin")
+_DERIVED = _WINDOW + ("derived", "redshift", "lumdist_mpc", "kappa", "kappa_wave", "lir_range", "peak_model")
+_ANALYSES = {
+    "predict": _Analysis("specs", "predict= needs specs: wavelengths in um and / or passband names", _WINDOW,
+                         {"specs", "percentile", "percentiles", "burn", "thin", "clip", "wavenorm", "keep"},
+                         _request_predict, _check_steps, "predicted from", "predictions_", "predictions"),
+    "loo": _Analysis(None, None, _WINDOW, {"burn", "thin"}, _request_loo, _check_loo, "cross-validated", "loo_", "loo"),
+    "goodness": _Analysis(None, None, _WINDOW, {"percentile", "percentiles", "burn", "thin"}, _request_goodness,
+                          _check_steps, "tested for goodness of fit", "goodness_", "goodness"),
+    "evidence": _Analysis(None, None, _WINDOW, {"n2", "fixed", "neff", "seed", "burn", "thin", "tol", "maxiter", "keep"},
+                          _request_evidence, _check_evidence, "bridged to an evidence", "evidence_", "evidence"),
+    "marginals": _Analysis(None, None, _DERIVED, None, _request_marginals, _check_steps, "binned", "marginals_",
+                           "marginals"),
+    "draws": _Analysis("n", None, _DERIVED, None, _request_draws, _check_steps, "drawn from", "draws_", "draws"),
+    "convergence": _Analysis(None, None, (), None, _request_convergence, _check_steps, "diagnosed", "convergence_",
+                             "convergence"),
+}
+# three orders, each as run_mcmc has always had it: requests are made and checked, a sharded run is refused, and the
+# results are made after the run
+_REQUEST_ORDER = ("predict", "loo", "goodness", "evidence", "marginals", "draws", "convergence")
+_SHARDED_ORDER = ("convergence", "marginals", "predict", "loo", "goodness", "evidence", "draws")
+_RESULT_ORDER = ("convergence", "marginals", "predict", "draws", "goodness", "evidence", "loo")
 
 
 class DeviceEnsembleSampler(object):
@@ -116,13 +206,9 @@ class DeviceEnsembleSampler(object):
         if getattr(self, "summary", None) is not None:
             self.summary.drop_chain()
         self.summary = None
-        self.convergence_ = None
-        self.marginals_ = None
-        self.draws_ = None
-        self.goodness_ = None
-        self.loo_ = None
-        self.evidence_ = None
         self._drop_predictions()
+        for an in _ANALYSES.values():
+            setattr(self, an.attr, None)
         self._resident = 0                    # steps of the last run's chain that are resident on the device
         if self._h is not None:
             _native._check(self._ctx.lib.mbb_sampler_reset(self._ctx.h, self._h))
@@ -163,20 +249,28 @@ class DeviceEnsembleSampler(object):
     def random_state(self):
         return self.seed
 
+    def _resident_steps(self, name):
+        """The steps of the last run's chain that are resident on the device, for the method ``name``."""
+        if not getattr(self, "_resident", 0):
+            raise ValueError("no chain of this sampler is resident on the device: {}() needs a run with "
+                             "storechain=True or summary= (and not a sharded one) since the last reset".format(name))
+        return self._resident
+
+    def _analyse(self, entry, req, raw):
+        """``mbb_sampler_<entry>`` of the resident chain, asked for what ``req`` says, into the arrays of ``raw``."""
+        ctx, h = self._handle()
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(getattr(ctx.lib, "mbb_sampler_" + entry)(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return raw
+
     def convergence(self, burn=0, c=5.0, tol=50.0, method="mean", nacf=0):
         """``diagnostics.ChainDiagnostics`` (autocorrelation time, ESS, split R-hat per parameter and source) of the
         chain the last run left on the device -- a run with storechain=True or with summary= -- over its steps from
         ``burn`` on; the keywords are ``diagnostics.chain_diagnostics``'s.  No chain crosses the bus."""
         from . import diagnostics
         req = diagnostics._Request(burn, c, tol, method, nacf)
-        if not getattr(self, "_resident", 0):
-            raise ValueError("no chain of this sampler is resident on the device: convergence() needs a run with "
-                             "storechain=True or summary= (and not a sharded one) since the last reset")
-        n = req.check_steps(self._resident)
-        ctx, h = self._handle()
-        raw = diagnostics._Raw(self.nsources, req.nacf)
-        spec, out = req.spec(), raw.out()
-        _native.check_arg(ctx.lib.mbb_sampler_diagnostics(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        n = req.check_steps(self._resident_steps("convergence"))
+        raw = self._analyse("diagnostics", req, diagnostics._Raw(self.nsources, req.nacf))
         return diagnostics.ChainDiagnostics(req, raw, self.nsources > 1, self.k, n)
 
     def marginals(self, **kw):
@@ -185,14 +279,8 @@ class DeviceEnsembleSampler(object):
         No chain crosses the bus."""
         from . import marginals
         req = marginals._Request(nsources=self.nsources, **kw)
-        if not getattr(self, "_resident", 0):
-            raise ValueError("no chain of this sampler is resident on the device: marginals() needs a run with "
-                             "storechain=True or summary= (and not a sharded one) since the last reset")
-        nkept = req.check_steps(self._resident)
-        ctx, h = self._handle()
-        raw = marginals._Raw(self.nsources, req.bins, req.bins2d, len(req.pairs))
-        spec, out = req.spec(), raw.out()
-        _native.check_arg(ctx.lib.mbb_sampler_marginals(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        nkept = req.check_steps(self._resident_steps("marginals"))
+        raw = self._analyse("marginals", req, marginals._Raw(self.nsources, req.bins, req.bins2d, len(req.pairs)))
         return marginals.ChainMarginals(req, raw, self.nsources > 1, self.k, nkept)
 
     def draws(self, n=1, **kw):
@@ -203,14 +291,8 @@ class DeviceEnsembleSampler(object):
         from . import draws
         kw.setdefault("seed", self.seed)
         req = draws._Request(n, nsources=self.nsources, **kw)
-        if not getattr(self, "_resident", 0):
-            raise ValueError("no chain of this sampler is resident on the device: draws() needs a run with "
-                             "storechain=True or summary= (and not a sharded one) since the last reset")
-        nkept = req.check_steps(self._resident)
-        ctx, h = self._handle()
-        raw = draws._Raw(self.nsources, req.n, req.derived)
-        spec, out = req.spec(), raw.out()
-        _native.check_arg(ctx.lib.mbb_sampler_draws(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        nkept = req.check_steps(self._resident_steps("draws"))
+        raw = self._analyse("draws", req, draws._Raw(self.nsources, req.n, req.derived))
         return draws.ChainDraws(self.lnprobfn, req, raw, self.nsources > 1, self.k, nkept)
 
     def goodness(self, percentile=68.3, percentiles=(), burn=0, thin=1):
@@ -219,16 +301,10 @@ class DeviceEnsembleSampler(object):
         the last run left on the device -- a run with storechain=True or with summary= --; the keywords are
         ``goodness.chain_goodness``'s.  No chain crosses the bus."""
         from . import goodness
-        cens, qs = goodness._quantiles(percentile, percentiles)
+        cens, qs = _analysis.quantiles(percentile, percentiles)
         req = goodness._Request(self.lnprobfn, qs, burn, thin)
-        if not getattr(self, "_resident", 0):
-            raise ValueError("no chain of this sampler is resident on the device: goodness() needs a run with "
-                             "storechain=True or summary= (and not a sharded one) since the last reset")
-        nkept = req.check_steps(self._resident)
-        ctx, h = self._handle()
-        raw = goodness._Raw(self.nsources, req.ndata, len(req.qs))
-        spec, out = req.spec(), raw.out()
-        _native.check_arg(ctx.lib.mbb_sampler_goodness(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        nkept = req.check_steps(self._resident_steps("goodness"))
+        raw = self._analyse("goodness", req, goodness._Raw(self.nsources, req.ndata, len(req.qs)))
         return goodness.ChainGoodness(req, raw, self.nsources > 1, cens[0], self.k, nkept)
 
     def loo(self, burn=0, thin=1):
@@ -237,14 +313,8 @@ class DeviceEnsembleSampler(object):
         summary= --; the keywords are ``loo.chain_loo``'s.  No chain crosses the bus."""
         from . import loo
         req = loo._Request(self.lnprobfn, burn, thin)
-        if not getattr(self, "_resident", 0):
-            raise ValueError("no chain of this sampler is resident on the device: loo() needs a run with "
-                             "storechain=True or summary= (and not a sharded one) since the last reset")
-        nkept = req.check_steps(self._resident, self.k)
-        ctx, h = self._handle()
-        raw = loo._Raw(self.nsources, req.ndata)
-        spec, out = req.spec(), raw.out()
-        _native.check_arg(ctx.lib.mbb_sampler_pointwise(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        nkept = req.check_steps(self._resident_steps("loo"), self.k)
+        raw = self._analyse("pointwise", req, loo._Raw(self.nsources, req.ndata))
         return loo.ChainLoo(req, raw, self.nsources > 1, self.k, nkept)
 
     def evidence(self, n2=None, fixed=None, neff="auto", seed=None, burn=0, thin=1, tol=None, maxiter=None, keep=False):
@@ -257,10 +327,7 @@ class DeviceEnsembleSampler(object):
         req = evidence._Request(self.lnprobfn, n2, fixed, self.seed if seed is None else seed, burn, thin,
                                 evidence.TOL if tol is None else tol, evidence.MAXITER if maxiter is None else maxiter,
                                 0, keep)
-        if not getattr(self, "_resident", 0):
-            raise ValueError("no chain of this sampler is resident on the device: evidence() needs a run with "
-                             "storechain=True or summary= (and not a sharded one) since the last reset")
-        nkept, nfit = req.check_steps(self._resident)
+        nkept, nfit = req.check_steps(self._resident_steps("evidence"))
         n1 = self.k * (nkept - nfit)
         if isinstance(neff, str):
             if neff != "auto":
@@ -269,10 +336,7 @@ class DeviceEnsembleSampler(object):
             req.set_neff(req.neff_from_ess(dg.ess, dg.status, n1), self.nsources)
         else:
             req.set_neff(neff, self.nsources)
-        ctx, h = self._handle()
-        raw = evidence._Raw(self.nsources, n1, req.n2 or n1, req.keep)
-        spec, out = req.spec(), raw.out()
-        _native.check_arg(ctx.lib.mbb_sampler_evidence(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        raw = self._analyse("evidence", req, evidence._Raw(self.nsources, n1, req.n2 or n1, req.keep))
         return evidence.ChainEvidence(req, raw, self.nsources > 1, self.k, nkept)
 
     def predictions(self, specs, percentile=68.3, percentiles=(), burn=0, thin=1, clip=None, wavenorm=None, keep=True):
@@ -280,12 +344,9 @@ class DeviceEnsembleSampler(object):
         chain the last run left on the device -- a run with storechain=True or with summary= --; the arguments are
         ``predict.chain_predictions``'s.  No chain crosses the bus."""
         from . import predict
-        cens, qs = predict._quantiles(percentile, percentiles)
+        cens, qs = _analysis.quantiles(percentile, percentiles)
         req = predict._Request(self.lnprobfn, specs, qs, burn, thin, clip, wavenorm)
-        if not getattr(self, "_resident", 0):
-            raise ValueError("no chain of this sampler is resident on the device: predictions() needs a run with "
-                             "storechain=True or summary= (and not a sharded one) since the last reset")
-        nkept = req.check_steps(self._resident)
+        nkept = req.check_steps(self._resident_steps("predictions"))
         res = predict.ChainPredictions(req, self._predict_again(req), self.nsources > 1,
                                        self._predict_again if keep else None, cens[0], self.k, nkept)
         if keep:
@@ -310,11 +371,7 @@ class DeviceEnsembleSampler(object):
     def _predict_again(self, req):
         """A prediction from the chain the last run left on the device (mbb_sampler_predict)."""
         from . import predict
-        ctx, h = self._handle()
-        raw = predict._Raw(self.nsources, len(req.keys), len(req.qs))
-        spec, out = req.spec(), raw.out()
-        _native.check_arg(ctx.lib.mbb_sampler_predict(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
-        return raw
+        return self._analyse("predict", req, predict._Raw(self.nsources, len(req.keys), len(req.qs)))
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
                  marginals=None, predict=None, draws=None, goodness=None, evidence=None, loo=None, **unused):
@@ -377,7 +434,8 @@ class DeviceEnsembleSampler(object):
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
         with summary=."""
         self._retire()
-        return self._run(pos0, N, lnprob0, storechain, summary, convergence, marginals, predict, draws, goodness, evidence, loo)
+        return self._run(pos0, N, lnprob0, storechain, summary, convergence=convergence, marginals=marginals,
+                         predict=predict, draws=draws, goodness=goodness, evidence=evidence, loo=loo)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""
@@ -396,149 +454,40 @@ class DeviceEnsembleSampler(object):
         if not st.single:
             self._resident = 0                # (what is resident is the last chunk: a part)
 
-    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, convergence=None, marginals=None, predict=None,
-             draws=None, goodness=None, evidence=None, loo=None):
-        creq = mkw = pkw = dkw = gkw = ekw = lkw = None
-        self.loo_ = None
-        self.evidence_ = None
-        self.convergence_ = None
-        self.marginals_ = None
-        self.draws_ = None
-        self.goodness_ = None
+    def _run(self, pos0, N, lnprob0=None, storechain=True, summary=None, **asked):
         self._drop_predictions()                    # (the chain they could go back to is about to be overwritten)
-        if predict is not None and predict is not False:
-            from . import predict as _predict
-            pkw = dict(predict) if isinstance(predict, dict) else dict(specs=predict)
-            if "specs" not in pkw:
-                raise ValueError("predict= needs specs: wavelengths in um and / or passband names")
-            if summary is not None and summary is not False and summary is not True:
-                for key in ("burn", "thin"):
-                    if key in summary:
-                        pkw.setdefault(key, summary[key])
-            unknown = set(pkw) - {"specs", "percentile", "percentiles", "burn", "thin", "clip", "wavenorm", "keep"}
-            if unknown:
-                raise TypeError("predict= got unexpected keyword(s) {}".format(sorted(unknown)))
-            preq = _predict._Request(self.lnprobfn, pkw["specs"],
-                                     _predict._quantiles(pkw.get("percentile", 68.3), pkw.get("percentiles", ()))[1],
-                                     pkw.get("burn", 0), pkw.get("thin", 1), pkw.get("clip"), pkw.get("wavenorm"))
-            if not storechain and (summary is None or summary is False):
-                raise ValueError("predict= with storechain=False needs summary= too: a run that neither stores "
-                                 "nor summarises its chain keeps none on the device")
-            preq.check_steps(int(N))
-        if loo is not None and loo is not False:
-            from . import loo as _loo
-            lkw = {} if loo is True else dict(loo)
-            if summary is not None and summary is not False and summary is not True:
-                for key in ("burn", "thin"):
-                    if key in summary:
-                        lkw.setdefault(key, summary[key])
-            unknown = set(lkw) - {"burn", "thin"}
-            if unknown:
-                raise TypeError("loo= got unexpected keyword(s) {}".format(sorted(unknown)))
-            lreq = _loo._Request(self.lnprobfn, lkw.get("burn", 0), lkw.get("thin", 1))
-            if not storechain and (summary is None or summary is False):
-                raise ValueError("loo= with storechain=False needs summary= too: a run that neither stores "
-                                 "nor summarises its chain keeps none on the device")
-            lreq.check_steps(int(N), self.k)
-        if goodness is not None and goodness is not False:
-            from . import goodness as _goodness
-            gkw = {} if goodness is True else dict(goodness)
-            if summary is not None and summary is not False and summary is not True:
-                for key in ("burn", "thin"):
-                    if key in summary:
-                        gkw.setdefault(key, summary[key])
-            unknown = set(gkw) - {"percentile", "percentiles", "burn", "thin"}
-            if unknown:
-                raise TypeError("goodness= got unexpected keyword(s) {}".format(sorted(unknown)))
-            greq = _goodness._Request(self.lnprobfn, _goodness._quantiles(gkw.get("percentile", 68.3),
-                                                                          gkw.get("percentiles", ()))[1],
-                                      gkw.get("burn", 0), gkw.get("thin", 1))
-            if not storechain and (summary is None or summary is False):
-                raise ValueError("goodness= with storechain=False needs summary= too: a run that neither stores "
-                                 "nor summarises its chain keeps none on the device")
-            greq.check_steps(int(N))
-        if evidence is not None and evidence is not False:
-            from . import evidence as _evidence
-            ekw = {} if evidence is True else dict(evidence)
-            if summary is not None and summary is not False and summary is not True:
-                for key in ("burn", "thin"):
-                    if key in summary:
-                        ekw.setdefault(key, summary[key])
-            unknown = set(ekw) - {"n2", "fixed", "neff", "seed", "burn", "thin", "tol", "maxiter", "keep"}
-            if unknown:
-                raise TypeError("evidence= got unexpected keyword(s) {}".format(sorted(unknown)))
-            ereq = _evidence._Request(self.lnprobfn, ekw.get("n2"), ekw.get("fixed"), ekw.get("seed", self.seed),
-                                      ekw.get("burn", 0), ekw.get("thin", 1), ekw.get("tol", _evidence.TOL),
-                                      ekw.get("maxiter", _evidence.MAXITER))
-            if not storechain and (summary is None or summary is False):
-                raise ValueError("evidence= with storechain=False needs summary= too: a run that neither stores "
-                                 "nor summarises its chain keeps none on the device")
-            ereq.check_steps(int(N))
-            if not isinstance(ekw.get("neff", "auto"), str):
-                ereq.set_neff(ekw["neff"], self.nsources)
-            elif ekw.get("neff", "auto") != "auto":
-                raise ValueError("neff must be 'auto', None, a number or one number per source")
-        if marginals is not None and marginals is not False:
-            from . import marginals as _marginals
-            mkw = {} if marginals is True else dict(marginals)
-            if summary is not None and summary is not False and summary is not True:
-                for key in _marginals._SUMMARY_KEYS:
-                    if key in summary:
-                        mkw.setdefault(key, summary[key])
-            mreq = _marginals._Request(nsources=self.nsources, **mkw)
-            if not storechain and (summary is None or summary is False):
-                raise ValueError("marginals= with storechain=False needs summary= too: a run that neither stores "
-                                 "nor summarises its chain keeps none on the device")
-            mreq.check_steps(int(N))
-        if draws is not None and draws is not False:
-            from . import draws as _draws
-            dkw = dict(draws) if isinstance(draws, dict) else dict(n=draws)
-            if summary is not None and summary is not False and summary is not True:
-                for key in _draws._SUMMARY_KEYS:
-                    if key in summary:
-                        dkw.setdefault(key, summary[key])
-            dkw.setdefault("seed", self.seed)
-            dreq = _draws._Request(nsources=self.nsources, **dkw)
-            if not storechain and (summary is None or summary is False):
-                raise ValueError("draws= with storechain=False needs summary= too: a run that neither stores "
-                                 "nor summarises its chain keeps none on the device")
-            dreq.check_steps(int(N))
-        if convergence is not None and convergence is not False:
-            from . import diagnostics
-            ckw = {} if convergence is True else dict(convergence)
-            creq = diagnostics._Request(**ckw)
-            if not storechain and (summary is None or summary is False):
-                raise ValueError("convergence= with storechain=False needs summary= too: a run that neither stores "
-                                 "nor summarises its chain keeps none on the device")
-            creq.check_steps(int(N))
+        for an in _ANALYSES.values():
+            setattr(self, an.attr, None)
+        summarised = summary is not None and summary is not False
+        kws = {}
+        for key in _REQUEST_ORDER:
+            value, an = asked.get(key), _ANALYSES[key]
+            if value is None or value is False:
+                continue
+            if isinstance(value, dict):
+                kw = dict(value)
+            else:
+                kw = {} if an.first is None else {an.first: value}
+            if an.needs and an.first not in kw:
+                raise ValueError(an.needs)
+            if summarised and summary is not True:
+                for k in an.inherits:
+                    if k in summary:
+                        kw.setdefault(k, summary[k])
+            if an.allowed is not None and set(kw) - an.allowed:
+                raise TypeError("{}= got unexpected keyword(s) {}".format(key, sorted(set(kw) - an.allowed)))
+            req = an.request(self, kw)
+            if not storechain and not summarised:
+                raise ValueError("{}= with storechain=False needs summary= too: a run that neither stores "
+                                 "nor summarises its chain keeps none on the device".format(key))
+            an.check(self, req, kw, int(N))
+            kws[key] = kw
         ctx, h = self._handle()
-        if creq is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
-            raise ValueError("a sharded sampler run cannot be diagnosed on the device: a rank holds only its own "
-                             "walkers' chain")
-        if mkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
-            raise ValueError("a sharded sampler run cannot be binned on the device: a rank holds only its own "
-                             "walkers' chain")
-        if pkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
-            raise ValueError("a sharded sampler run cannot be predicted from on the device: a rank holds only its own "
-                             "walkers' chain")
-        if lkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
-            raise ValueError("a sharded sampler run cannot be cross-validated on the device: a rank holds only its own "
-                             "walkers' chain")
-        if gkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
-            raise ValueError("a sharded sampler run cannot be tested for goodness of fit on the device: a rank holds "
-                             "only its own walkers' chain")
-        if ekw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
-            raise ValueError("a sharded sampler run cannot be bridged to an evidence on the device: a rank holds only "
-                             "its own walkers' chain")
-        if dkw is not None and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
-            raise ValueError("a sharded sampler run cannot be drawn from on the device: a rank holds only its own "
-                             "walkers' chain")
-        req = None
-        if summary is not None and summary is not False:
-            if ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None):
-                raise ValueError("a sharded sampler run cannot be summarised on the device: a rank holds only its "
-                                 "own walkers' chain")
-            req = self._summary_request({} if summary is True else dict(summary), int(N))
+        verbs = [_ANALYSES[key].verb for key in _SHARDED_ORDER if key in kws] + ["summarised"] * summarised
+        if verbs and (ctx.info("nranks") > 1 or getattr(ctx, "xchg_barrier", None)):
+            raise ValueError("a sharded sampler run cannot be {} on the device: a rank holds only its own walkers' "
+                             "chain".format(verbs[0]))
+        req = self._summary_request({} if summary is True else dict(summary), int(N)) if summarised else None
         # sharded with the one-hop exchange (parallel.ipc_exchange_setup): the ranks are
         # held together around set_state, because a peer's kernel writes into this rank's
         # copy of the ensemble
@@ -623,33 +572,18 @@ class DeviceEnsembleSampler(object):
         if req is not None:
             self.summary = results.ChainSummary(self.lnprobfn, req, raw, self.nsources > 1, self._summarise_again,
                                                 self._summary_percentile)
-        if creq is not None:
-            self.convergence_ = self.convergence(creq.burn, creq.c, creq.tol, creq.method, creq.nacf)
-        if mkw is not None:
-            self.marginals_ = self.marginals(**mkw)
-        if pkw is not None:
-            self.predictions_ = self.predictions(**pkw)
-        if dkw is not None:
-            self.draws_ = self.draws(**dkw)
-        if gkw is not None:
-            self.goodness_ = self.goodness(**gkw)
-        if ekw is not None:
-            self.evidence_ = self.evidence(**ekw)
-        if lkw is not None:
-            self.loo_ = self.loo(**lkw)
+        for key in _RESULT_ORDER:
+            if key in kws:
+                an = _ANALYSES[key]
+                setattr(self, an.attr, getattr(self, an.method)(**kws[key]))
         return pos, lnprob, self.seed
 
     def _summary_request(self, kw, nsteps):
         from . import results
-        cens = [float(p) for p in np.atleast_1d(kw.pop("percentile", 68.3))]
-        qs = []
-        for q in [q for p in cens for q in results._pval(p)] + [float(q) for q in kw.pop("percentiles", ())]:
-            if q not in qs:
-                qs.append(q)
+        cens, qs = _analysis.quantiles(kw.pop("percentile", 68.3), kw.pop("percentiles", ()))
         self._summary_percentile = cens[0]
         req = results._Request(qs, nsources=self.nsources, **kw)
-        if nsteps < 1 or req.burn >= nsteps:
-            raise ValueError("burn leaves no step of the chain")
+        req.check_steps(nsteps)
         return req
 
     def _summarise_again(self, req):

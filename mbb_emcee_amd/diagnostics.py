@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 
 __all__ = ["chain_diagnostics", "ChainDiagnostics"]
 
@@ -17,7 +17,7 @@ METHODS = {"mean": _native.DIAG_MEAN, "walkers": _native.DIAG_WALKERS}
 PARAM_NAMES = ("T", "beta", "lambda0", "alpha", "fnorm")
 
 
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native diagnostics call is asked for (mbb_diag_spec); everything is checked here, before the
     device is touched."""
 
@@ -37,9 +37,7 @@ class _Request(object):
             raise ValueError("nacf must not be negative")
 
     def check_steps(self, nsteps):
-        n = int(nsteps) - self.burn
-        if n < 1:
-            raise ValueError("burn leaves no step of the chain")
+        n = _analysis.Window.check_steps(self, nsteps)        # (no thin: every step from burn on)
         if n > _native.DIAG_MAX_STEPS:
             raise ValueError("more than %d kept steps per series: raise burn" % _native.DIAG_MAX_STEPS)
         if self.nacf > n:

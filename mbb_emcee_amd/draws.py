@@ -13,13 +13,12 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 from . import results
 
 __all__ = ["chain_draws", "draw_indices", "ChainDraws"]
 
 _HOW = {"random": _native.DRAWS_RANDOM, "even": _native.DRAWS_EVEN}
-_SUMMARY_KEYS = ("burn", "thin", "derived", "redshift", "lumdist_mpc", "kappa", "kappa_wave", "lir_range", "peak_model")
 _DERIVED_ORDER = ("peaklambda", "lir", "dustmass")
 # the reference's messages (results.py:840-845)
 _NOT_COMPUTED = {"peaklambda": "Peak lambda not computed", "lir": "LIR not computed", "dustmass": "Dustmass not computed"}
@@ -42,7 +41,7 @@ def _check_picks(n, how, seed, nsources):
     return n, how, seed
 
 
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native draws call is asked for (mbb_draws_spec); everything is checked here, before the device is
     touched."""
 
@@ -53,12 +52,6 @@ class _Request(object):
                                         lir_range, peak_model, nsources=nsources)
         self.burn, self.thin, self.derived = self.summary.burn, self.summary.thin, self.summary.derived
         self.n, self.how, self.seed = _check_picks(n, how, seed, nsources)
-
-    def check_steps(self, nsteps):
-        """The number of kept steps per walker."""
-        if int(nsteps) < 1 or self.burn >= int(nsteps):
-            raise ValueError("burn leaves no step of the chain")
-        return (int(nsteps) - self.burn + self.thin - 1) // self.thin
 
     def spec(self):
         s = _native.DrawsSpec()
@@ -89,7 +82,7 @@ class _Raw(object):
         return o
 
 
-class ChainDraws(object):
+class ChainDraws(_analysis.Result):
     """Draws from a chain (a leading source axis for a multi-source chain).
 
     params [n, 5], lnprob [n] (NaN when the chain came without one), index [n, 2] (walker, step) : the drawn cells,
@@ -105,11 +98,8 @@ class ChainDraws(object):
 
     def __init__(self, like, request, raw, multi, nwalkers, nkept):
         self._like, self._req, self._raw, self._multi = like, request, raw, multi
-        self.n, self.how, self.seed, self.burn, self.thin = request.n, request.how, request.seed, request.burn, request.thin
-        self.nwalkers, self.nsteps_used = int(nwalkers), int(nkept)
-
-    def _squeeze(self, a):
-        return a if self._multi else a[0]
+        self.n, self.how, self.seed = request.n, request.how, request.seed
+        self._set_window(request, nwalkers, nkept)
 
     def _derived(self, name):
         if name not in self._raw.derived:
@@ -197,12 +187,7 @@ def chain_draws(like, chain, lnprob=None, n=1, how="random", seed=0, burn=0, thi
     nsrc, nw, nsteps = c4.shape[:3]
     if nsrc < 1 or nw < 1 or nsteps < 1:
         raise ValueError("the chain is empty")
-    l3 = None
-    if lnprob is not None:
-        l3 = np.ascontiguousarray(lnprob, dtype=np.float64)
-        l3 = l3 if multi else l3[None]
-        if l3.shape != c4.shape[:3]:
-            raise ValueError("lnprob must have the chain's shape without its last axis")
+    l3 = None if lnprob is None else _analysis.lnprob_like(lnprob, c4, multi)
     req = _Request(n, how, seed, burn, thin, derived, redshift, lumdist_mpc, kappa, kappa_wave, lir_range, peak_model,
                    nsources=nsrc)
     nkept = req.check_steps(nsteps)

@@ -16,7 +16,7 @@ import math
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 
 __all__ = ["chain_evidence", "ChainEvidence", "ln_prior_norm"]
 
@@ -80,7 +80,7 @@ def ln_prior_norm(like, fixed=None):
     return total, improper, bool(like._has_uplim[5] or like._has_gprior[5])
 
 
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native evidence call is asked for (mbb_evidence_spec); everything is checked here, before the device is
     touched."""
 
@@ -93,9 +93,7 @@ class _Request(object):
         if not 0 <= self.n2 <= MAX_N2:
             raise ValueError("n2 must be 0 (as many draws as posterior samples) to {:d}".format(MAX_N2))
         self.seed = int(seed) & 0xffffffffffffffff
-        self.burn, self.thin = int(burn), int(thin)
-        if self.burn < 0 or self.thin < 1:
-            raise ValueError("burn must be >= 0 and thin >= 1")
+        self.set_window(burn, thin)
         self.tol = float(tol)
         if not (np.isfinite(self.tol) and self.tol >= 0):
             raise ValueError("tol must be finite and not negative")
@@ -112,18 +110,11 @@ class _Request(object):
 
     def check_steps(self, nsteps):
         """(kept steps per walker, those that fit the proposal)"""
-        if int(nsteps) < 1 or self.burn >= int(nsteps):
-            raise ValueError("burn leaves no step of the chain")
-        nkept = (int(nsteps) - self.burn + self.thin - 1) // self.thin
+        nkept = _analysis.Window.check_steps(self, nsteps)
         if nkept < 2:
             raise ValueError("an evidence needs two kept steps at least: one half fits the proposal, the other is "
                              "bridged to")
         return nkept, nkept // 2
-
-    def check_sources(self, like_nsources, chain_nsources):
-        if chain_nsources != like_nsources and like_nsources != 1:
-            raise ValueError("the chain has {:d} sources, the likelihood {:d}: they must agree, or the likelihood hold "
-                             "one source for all".format(chain_nsources, like_nsources))
 
     def set_neff(self, neff, nsrc):
         if neff is None:
@@ -201,12 +192,10 @@ def chain_evidence(like, chain, lnprob, n2=None, fixed=None, neff="auto", seed=D
         raise ValueError("the chain is empty")
     req = _Request(like, n2, fixed, seed, burn, thin, tol, maxiter, first_source, keep)
     nkept, nfit = req.check_steps(nsteps)
-    req.check_sources(like.nsources, nsrc)
+    _analysis.check_sources(like.nsources, nsrc)
     if lnprob is None:
         raise ValueError("an evidence needs the chain's lnprob")
-    lp = np.ascontiguousarray(lnprob, dtype=np.float64)
-    if lp.shape != c4.shape[0 if multi else 1:3]:
-        raise ValueError("lnprob must have the chain's shape without its last axis")
+    lp = _analysis.lnprob_like(lnprob, c4, multi)
     n1 = nw * (nkept - nfit)
     if isinstance(neff, str):
         if neff != "auto":
@@ -225,7 +214,7 @@ def chain_evidence(like, chain, lnprob, n2=None, fixed=None, neff="auto", seed=D
     return ChainEvidence(req, raw, multi, nw, nkept)
 
 
-class ChainEvidence(object):
+class ChainEvidence(_analysis.Result):
     """The evidence of a chain from the device (a leading source axis for a multi-source result).
 
     lnz, lnz_err : ln of the integral of the unnormalised posterior over the free parameters, and its standard error
@@ -244,11 +233,7 @@ class ChainEvidence(object):
 
     def __init__(self, request, raw, multi, nwalkers=0, nkept=0):
         self._req, self._raw, self._multi = request, raw, bool(multi)
-        self.burn, self.thin = request.burn, request.thin
-        self.nwalkers, self.nsteps_used = int(nwalkers), int(nkept)
-
-    def _squeeze(self, a):
-        return a if self._multi else a[0]
+        self._set_window(request, nwalkers, nkept)
 
     lnz = property(lambda self: self._squeeze(self._raw.lnz).copy())
     lnz_err = property(lambda self: self._squeeze(self._raw.lnz_err).copy())

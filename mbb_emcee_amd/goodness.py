@@ -13,8 +13,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 from . import results
+from ._analysis import quantiles as _quantiles
 
 __all__ = ["chain_goodness", "ChainGoodness"]
 
@@ -22,23 +23,13 @@ MAX_BANDS = 256
 CHISQ, Q = 0, 1            # the two columns
 
 
-def _quantiles(percentile, percentiles):
-    cens = [float(p) for p in np.atleast_1d(percentile)]
-    qs = []
-    for q in [q for p in cens for q in results._pval(p)] + [float(q) for q in percentiles]:
-        if q not in qs:
-            qs.append(q)
-    return cens, qs
-
-
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native goodness call is asked for (mbb_goodness_spec); everything is checked here, before the device
     is touched."""
 
     def __init__(self, like, qs, burn=0, thin=1):
-        if not like.data_read:
-            raise Exception("Data not read: goodness of fit needs the likelihood's photometry")
-        self.ndata = int(like._ndata)
+        # the data the pulls are formed with: [nsources, ndata]
+        self.ndata, self.flux, self.sigma = _analysis.photometry(like, "goodness of fit")
         if self.ndata > MAX_BANDS:
             raise ValueError("at most {:d} bands per goodness call".format(MAX_BANDS))
         self.qs = [float(q) for q in qs]
@@ -47,27 +38,7 @@ class _Request(object):
         for q in self.qs:
             if not (0 <= q <= 100):
                 raise ValueError("Invalid percentile {:f}".format(q))
-        self.burn, self.thin = int(burn), int(thin)
-        if self.burn < 0 or self.thin < 1:
-            raise ValueError("burn must be >= 0 and thin >= 1")
-        # the data the pulls are formed with: [nsources, ndata]
-        if like.nsources > 1:
-            self.flux = np.array(like._flux_multi, dtype=np.float64)
-            self.sigma = 1.0 / np.sqrt(np.asarray(like._ivar_multi, dtype=np.float64))
-        else:
-            self.flux = np.array(like._flux, dtype=np.float64)[None]
-            self.sigma = np.array(like.data_flux_unc, dtype=np.float64)[None]
-
-    def check_steps(self, nsteps):
-        """The number of kept steps per walker."""
-        if int(nsteps) < 1 or self.burn >= int(nsteps):
-            raise ValueError("burn leaves no step of the chain")
-        return (int(nsteps) - self.burn + self.thin - 1) // self.thin
-
-    def check_sources(self, like_nsources, chain_nsources):
-        if chain_nsources != like_nsources and like_nsources != 1:
-            raise ValueError("the chain has {:d} sources, the likelihood {:d}: they must agree, or the likelihood hold "
-                             "one source for all".format(chain_nsources, like_nsources))
+        self.set_window(burn, thin)
 
     def spec(self):
         s = _native.GoodnessSpec()
@@ -107,15 +78,12 @@ def goodness_rows(like, pars, want_flux=False):
     """(chisq [n], q [n], row status [n]) of parameter rows [n, 5] -- and their band fluxes [n, ndata] with want_flux --
     by the device function the chain's entries go through (mbb_goodness_rows).  In multi-source mode the rows are
     nsources equal blocks, as for ``like(pars)``."""
-    p = np.ascontiguousarray(np.atleast_2d(np.asarray(pars, dtype=np.float64)))
-    if p.ndim != 2 or p.shape[1] != 5 or p.shape[0] < 1:
-        raise ValueError("pars must be [n, 5]")
-    if not like.data_read:
-        raise Exception("Data not read: goodness of fit needs the likelihood's photometry")
+    p = _analysis.rows5(pars)
+    ndata = _analysis.photometry(like, "goodness of fit")[0]
     ctx = _native.analysis_context(like)
     n = p.shape[0]
     chisq, q, st = np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)
-    fl = np.empty((n, int(like._ndata))) if want_flux else None
+    fl = np.empty((n, ndata)) if want_flux else None
     _native.check_arg(ctx.lib.mbb_goodness_rows(ctx.h, _native._d(p), n, _native._d(chisq), _native._d(q), _native._i(st),
                                                 _native._d(fl) if want_flux else None), ctx)
     return (chisq, q, st, fl) if want_flux else (chisq, q, st)
@@ -138,12 +106,8 @@ def chain_goodness(like, chain, lnprob=None, percentile=68.3, percentiles=(), bu
     cens, qs = _quantiles(percentile, percentiles)
     req = _Request(like, qs, burn, thin)
     nkept = req.check_steps(nsteps)
-    req.check_sources(like.nsources, nsrc)
-    lp = None
-    if lnprob is not None:
-        lp = np.ascontiguousarray(lnprob, dtype=np.float64)
-        if lp.shape != c4.shape[0 if multi else 1:3]:
-            raise ValueError("lnprob must have the chain's shape without its last axis")
+    _analysis.check_sources(like.nsources, nsrc)
+    lp = None if lnprob is None else _analysis.lnprob_like(lnprob, c4, multi)
     ctx = _native.analysis_context(like)
     raw = _Raw(nsrc, req.ndata, len(req.qs))
     spec, out = req.spec(), raw.out()
@@ -152,7 +116,7 @@ def chain_goodness(like, chain, lnprob=None, percentile=68.3, percentiles=(), bu
     return ChainGoodness(req, raw, multi, cens[0], nw, nkept)
 
 
-class ChainGoodness(object):
+class ChainGoodness(_analysis.Result):
     """Goodness of fit of a chain from the device (a leading source axis for a multi-source result).
 
     chisq_cen() : [mean, upper - mean, mean - lower] of chisq over the window;
@@ -174,11 +138,7 @@ class ChainGoodness(object):
     def __init__(self, request, raw, multi, percentile=68.3, nwalkers=0, nkept=0):
         self._req, self._raw, self._multi = request, raw, bool(multi)
         self._percentile = float(percentile)
-        self.burn, self.thin = request.burn, request.thin
-        self.nwalkers, self.nsteps_used = int(nwalkers), int(nkept)
-
-    def _squeeze(self, a):
-        return a if self._multi else a[0]
+        self._set_window(request, nwalkers, nkept)
 
     ndata = property(lambda self: self._req.ndata)
     n_used = property(lambda self: self._squeeze(self._raw.n_used[:, CHISQ]).copy())

@@ -20,7 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 
 __all__ = ["chain_loo", "loo_rows", "ChainLoo"]
 
@@ -29,41 +29,24 @@ MAX_WINDOW = _native.PW_MAX_WINDOW
 _TABLES = ("lppd", "p_waic", "elpd_waic", "elpd_loo", "p_loo", "khat", "loo_pit")
 
 
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native pointwise call is asked for (mbb_pointwise_spec); everything is checked here, before the device
     is touched."""
 
     def __init__(self, like, burn=0, thin=1):
-        if not like.data_read:
-            raise Exception("Data not read: cross-validation needs the likelihood's photometry")
-        self.ndata = int(like._ndata)
+        # what the fit was held against, for compare(): [nsources, ndata]
+        self.ndata, self.flux, self.sigma = _analysis.photometry(like, "cross-validation")
         if self.ndata > MAX_BANDS:
             raise ValueError("at most {:d} bands per pointwise call".format(MAX_BANDS))
-        self.burn, self.thin = int(burn), int(thin)
-        if self.burn < 0 or self.thin < 1:
-            raise ValueError("burn must be >= 0 and thin >= 1")
-        # what the fit was held against, for compare(): [nsources, ndata]
-        if like.nsources > 1:
-            self.flux = np.array(like._flux_multi, dtype=np.float64)
-            self.sigma = 1.0 / np.sqrt(np.asarray(like._ivar_multi, dtype=np.float64))
-        else:
-            self.flux = np.array(like._flux, dtype=np.float64)[None]
-            self.sigma = np.array(like.data_flux_unc, dtype=np.float64)[None]
+        self.set_window(burn, thin)
 
     def check_steps(self, nsteps, nwalkers=1):
         """The number of kept steps per walker."""
-        if int(nsteps) < 1 or self.burn >= int(nsteps):
-            raise ValueError("burn leaves no step of the chain")
-        nkept = (int(nsteps) - self.burn + self.thin - 1) // self.thin
+        nkept = _analysis.Window.check_steps(self, nsteps)
         if int(nwalkers) * nkept > MAX_WINDOW:
             raise ValueError("a window of {:d} entries per source needs a longer tail than the device sorts: at most "
                              "{:d} (thin the window)".format(int(nwalkers) * nkept, MAX_WINDOW))
         return nkept
-
-    def check_sources(self, like_nsources, chain_nsources):
-        if chain_nsources != like_nsources and like_nsources != 1:
-            raise ValueError("the chain has {:d} sources, the likelihood {:d}: they must agree, or the likelihood hold "
-                             "one source for all".format(chain_nsources, like_nsources))
 
     def spec(self):
         s = _native.PointwiseSpec()
@@ -93,14 +76,11 @@ class _Raw(object):
 def loo_rows(like, pars):
     """(ll [n, ndata], row status [n]) of parameter rows [n, 5] by the device function the chain's entries go through
     (mbb_pointwise_rows).  In multi-source mode the rows are nsources equal blocks, as for ``like(pars)``."""
-    p = np.ascontiguousarray(np.atleast_2d(np.asarray(pars, dtype=np.float64)))
-    if p.ndim != 2 or p.shape[1] != 5 or p.shape[0] < 1:
-        raise ValueError("pars must be [n, 5]")
-    if not like.data_read:
-        raise Exception("Data not read: cross-validation needs the likelihood's photometry")
+    p = _analysis.rows5(pars)
+    ndata = _analysis.photometry(like, "cross-validation")[0]
     ctx = _native.analysis_context(like)
     n = p.shape[0]
-    ll, st = np.empty((n, int(like._ndata))), np.empty(n, dtype=np.int32)
+    ll, st = np.empty((n, ndata)), np.empty(n, dtype=np.int32)
     _native.check_arg(ctx.lib.mbb_pointwise_rows(ctx.h, _native._d(p), n, _native._d(ll), _native._i(st)), ctx)
     return ll, st
 
@@ -116,7 +96,7 @@ def chain_loo(like, chain, burn=0, thin=1):
         raise ValueError("the chain is empty")
     req = _Request(like, burn, thin)
     nkept = req.check_steps(nsteps, nw)
-    req.check_sources(like.nsources, nsrc)
+    _analysis.check_sources(like.nsources, nsrc)
     ctx = _native.analysis_context(like)
     raw = _Raw(nsrc, req.ndata)
     spec, out = req.spec(), raw.out()
@@ -136,7 +116,7 @@ def _band_se(t):
     return np.sqrt(nb * np.var(t, axis=1, ddof=1))
 
 
-class ChainLoo(object):
+class ChainLoo(_analysis.Result):
     """WAIC and PSIS-LOO of a chain from the device (a leading source axis for a multi-source result).
 
     Per band [..., ndata]: ``lppd_band``, ``p_waic_band``, ``elpd_waic_band``, ``elpd_loo_band``, ``p_loo_band``,
@@ -158,11 +138,7 @@ class ChainLoo(object):
 
     def __init__(self, request, raw, multi, nwalkers=0, nkept=0):
         self._req, self._raw, self._multi = request, raw, bool(multi)
-        self.burn, self.thin = request.burn, request.thin
-        self.nwalkers, self.nsteps_used = int(nwalkers), int(nkept)
-
-    def _squeeze(self, a):
-        return a if self._multi else a[0]
+        self._set_window(request, nwalkers, nkept)
 
     ndata = property(lambda self: self._req.ndata)
     n_used = property(lambda self: self._squeeze(self._raw.n_used).copy())

@@ -11,14 +11,13 @@ import itertools
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 from . import results
 
 __all__ = ["chain_marginals", "ChainMarginals"]
 
 COLUMN_NAMES = ("T", "beta", "lambda0", "alpha", "fnorm", "peaklambda", "lir", "dustmass")
 _range = range                # (``range`` is a keyword of the public calls, as it is of numpy.histogram)
-_SUMMARY_KEYS = ("burn", "thin", "derived", "redshift", "lumdist_mpc", "kappa", "kappa_wave", "lir_range", "peak_model")
 
 
 def _slot(name):
@@ -28,7 +27,7 @@ def _slot(name):
     return results._paridx(name)
 
 
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native marginals call is asked for (mbb_marginals_spec); everything is checked here, before the
     device is touched."""
 
@@ -76,12 +75,6 @@ class _Request(object):
             if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi and np.isfinite(hi - lo)):
                 raise ValueError("the range of {} must be finite with lo < hi".format(COLUMN_NAMES[slot]))
             self.range[slot] = (lo, hi)
-
-    def check_steps(self, nsteps):
-        """The number of kept steps per walker."""
-        if int(nsteps) < 1 or self.burn >= int(nsteps):
-            raise ValueError("burn leaves no step of the chain")
-        return (int(nsteps) - self.burn + self.thin - 1) // self.thin
 
     def spec(self):
         s = _native.MarginalsSpec()
@@ -141,7 +134,7 @@ def levels_of(H, fractions=(0.683, 0.954)):
     return out
 
 
-class ChainMarginals(object):
+class ChainMarginals(_analysis.Result):
     """Binned marginals of a chain (a leading source axis for a multi-source chain).  Column names are
     ``results``' (a parameter name or index, "peaklambda", "lir", "dustmass").
 
@@ -159,12 +152,9 @@ class ChainMarginals(object):
 
     def __init__(self, request, raw, multi, nwalkers, nkept):
         self._req, self._raw, self._multi = request, raw, multi
-        self.bins, self.bins2d, self.burn, self.thin = request.bins, request.bins2d, request.burn, request.thin
+        self.bins, self.bins2d = request.bins, request.bins2d
         self.pairs = [(COLUMN_NAMES[a], COLUMN_NAMES[b]) for a, b in request.pairs]
-        self.nwalkers, self.nsteps_used = int(nwalkers), int(nkept)
-
-    def _squeeze(self, a):
-        return a if self._multi else a[0]
+        self._set_window(request, nwalkers, nkept)
 
     def _column(self, name):
         slot = _slot(name)

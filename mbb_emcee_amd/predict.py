@@ -14,8 +14,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 from . import results
+from ._analysis import quantiles as _quantiles
 from .modified_blackbody import um_to_GHz
 
 __all__ = ["chain_predictions", "ChainPredictions"]
@@ -66,7 +67,7 @@ def sample_lists(like, keys):
     return np.array(off, dtype=np.int32), np.concatenate(freq), np.concatenate(weight)
 
 
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native prediction call is asked for (mbb_predict_spec); everything is checked here, before the
     device is touched."""
 
@@ -85,9 +86,7 @@ class _Request(object):
         for q in self.qs:
             if not (0 <= q <= 100):
                 raise ValueError("Invalid percentile {:f}".format(q))
-        self.burn, self.thin = int(burn), int(thin)
-        if self.burn < 0 or self.thin < 1:
-            raise ValueError("burn must be >= 0 and thin >= 1")
+        self.set_window(burn, thin)
         self.wavenorm = 0.0 if wavenorm is None else float(wavenorm)
         if wavenorm is not None and not (0 < self.wavenorm < np.inf):
             raise ValueError("wavenorm must be positive")
@@ -100,12 +99,6 @@ class _Request(object):
         if k not in self.keys:
             raise ValueError("{} was not asked for when the predictions were made".format(spec))
         return self.keys.index(k)
-
-    def check_steps(self, nsteps):
-        """The number of kept steps per walker."""
-        if int(nsteps) < 1 or self.burn >= int(nsteps):
-            raise ValueError("burn leaves no step of the chain")
-        return (int(nsteps) - self.burn + self.thin - 1) // self.thin
 
     def only(self, i, qs, lo, hi):
         """The same request for spec i alone, other percentiles and another clipping."""
@@ -161,15 +154,6 @@ class _Raw(object):
         return o
 
 
-def _quantiles(percentile, percentiles):
-    cens = [float(p) for p in np.atleast_1d(percentile)]
-    qs = []
-    for q in [q for p in cens for q in results._pval(p)] + [float(q) for q in percentiles]:
-        if q not in qs:
-            qs.append(q)
-    return cens, qs
-
-
 def _predict_host(like, c4, req):
     """mbb_chain_predict on a host chain [nsrc, nw, nsteps, 5]."""
     ctx = _native.analysis_context(like)
@@ -204,7 +188,7 @@ def chain_predictions(like, chain, specs, percentile=68.3, percentiles=(), burn=
     return ChainPredictions(req, raw, multi, again, cens[0], nw, nkept)
 
 
-class ChainPredictions(object):
+class ChainPredictions(_analysis.Result):
     """What ``mbb_results.predflux_cen`` reports of a chain, from the device's prediction (a leading source axis for
     a multi-source chain).  A spec is named as it was asked for: the band's name, or the wavelength.
 
@@ -220,11 +204,7 @@ class ChainPredictions(object):
         self._req, self._raw, self._multi, self._again = request, raw, multi, again
         self._percentile = float(percentile)
         self._cache = {}
-        self.burn, self.thin = request.burn, request.thin
-        self.nwalkers, self.nsteps_used = int(nwalkers), int(nkept)
-
-    def _squeeze(self, a):
-        return a if self._multi else a[0]
+        self._set_window(request, nwalkers, nkept)
 
     def drop_chain(self):
         """Forget how to compute more from the chain (a sampler's next run overwrites it on the device)."""

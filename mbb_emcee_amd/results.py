@@ -19,7 +19,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 from .modified_blackbody import modified_blackbody
 
 __all__ = ["chain_summary", "ChainSummary"]
@@ -57,7 +57,7 @@ def _paridx(param):
     return paridx
 
 
-class _Request(object):
+class _Request(_analysis.Window):
     """What one native summary call is asked for (mbb_summary_spec)."""
 
     def __init__(self, qs, burn=0, thin=1, clip=None, derived=(), redshift=None, lumdist_mpc=None, kappa=2.64,
@@ -68,9 +68,7 @@ class _Request(object):
         for q in self.qs:
             if not (0 <= q <= 100):
                 raise ValueError("Invalid percentile {:f}".format(q))
-        self.burn, self.thin = int(burn), int(thin)
-        if self.burn < 0 or self.thin < 1:
-            raise ValueError("burn must be >= 0 and thin >= 1")
+        self.set_window(burn, thin)
         self.clip = {}
         for key, (lo, hi) in (clip or {}).items():
             slot = _DERIVED[key] if key in _DERIVED else _paridx(key)
@@ -197,22 +195,11 @@ def chain_summary(like, chain, lnprob, percentile=68.3, burn=0, thin=1, derived=
     unknown: its L_IR and dust mass are NaN (status ``SUM_HAS_NAN``), everything else is unaffected.
     clip : ``{param or derived name: (lowlim, uplim)}`` applied as ``_parcen_internal`` does (either may be None).
     keep : keep the chain with the result, so that other percentiles and clip bounds can be computed on demand."""
-    lnprob = np.ascontiguousarray(lnprob, dtype=np.float64)
     c4, multi = _native.chain4(chain)
-    if lnprob.shape != c4.shape[0 if multi else 1:3]:
-        raise ValueError("lnprob must have the chain's shape without its last axis")
-    l3 = lnprob if multi else lnprob[None]
+    l3 = _analysis.lnprob_like(lnprob, c4, multi)
     if int(burn) >= c4.shape[2]:
         raise ValueError("burn leaves no step of the chain")
-    cens = [float(p) for p in np.atleast_1d(percentile)]
-    qs = []
-    for p in cens:
-        for q in _pval(p):
-            if q not in qs:
-                qs.append(q)
-    for q in percentiles:
-        if float(q) not in qs:
-            qs.append(float(q))
+    cens, qs = _analysis.quantiles(percentile, percentiles)
     req = _Request(qs, burn, thin, clip, derived, redshift, lumdist_mpc, kappa, kappa_wave, lir_range, peak_model,
                    nsources=c4.shape[0])
     raw = _summarise_host(like, c4, l3, req)
@@ -220,7 +207,7 @@ def chain_summary(like, chain, lnprob, percentile=68.3, burn=0, thin=1, derived=
     return ChainSummary(like, req, raw, multi, again, cens[0])
 
 
-class ChainSummary(object):
+class ChainSummary(_analysis.Result):
     """What ``mbb_results`` reports of a chain (results.py), from the device's summary of it.  Results of a
     multi-source chain carry a leading source axis."""
 
@@ -232,9 +219,6 @@ class ChainSummary(object):
         self._ndata = int(like.ndata) if like.data_read and like.nsources == 1 else None
 
     # ---- plumbing ---------------------------------------------------------------------------
-    def _squeeze(self, a):
-        return a if self._multi else a[0]
-
     def drop_chain(self):
         """Forget how to compute more from the chain (a sampler's next run overwrites it on the device)."""
         self._again = None
