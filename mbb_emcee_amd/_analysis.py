@@ -3,7 +3,46 @@ evidence, WAIC / PSIS-LOO): the burn / thin window of a request, the percentiles
 likelihood's photometry, the coercion of the arrays handed in, and the plumbing of a result class.  An analysis adds
 what is its own.
 """
+import ctypes as C
+
 import numpy as np
+
+
+_POINTEE = {}        # a ctypes pointer type -> the dtype of what it points at
+
+
+def bind_out(struct, arrays):
+    """An output struct of ``_native`` (``SummaryOut``, ``DiagOut``, ...) whose pointer fields point at ``arrays``, a
+    mapping from field names to the arrays the library is to fill (a field of several pointers: a sequence of as
+    many arrays or ``None``s).  Each address is cast to the field's own declared pointer type: an array of another dtype is a
+    ``TypeError``, one that is not C-contiguous a ``ValueError``.  A missing or ``None`` entry leaves its field null
+    (an optional output); entries that name no field are ignored, so that a result object's ``vars()`` will do."""
+    def pointer(ptype, a, name):
+        if a is None:
+            return ptype()
+        want = _POINTEE.get(ptype)
+        if want is None:
+            want = _POINTEE[ptype] = np.dtype(ptype._type_)
+        if not isinstance(a, np.ndarray) or a.dtype != want:
+            raise TypeError("{}.{} takes an array of {}, not {}".format(
+                struct.__name__, name, want, getattr(a, "dtype", type(a).__name__)))
+        if not a.flags.c_contiguous:
+            raise ValueError("{}.{} takes a C-contiguous array".format(struct.__name__, name))
+        return a.ctypes.data_as(ptype)
+
+    o = struct()
+    for name, ctype in struct._fields_:
+        a = arrays.get(name)
+        if a is None:
+            continue
+        if issubclass(ctype, C.Array):
+            if len(a) != ctype._length_:
+                raise ValueError("{}.{} takes {:d} arrays, not {:d}".format(struct.__name__, name, ctype._length_, len(a)))
+            for k, item in enumerate(a):
+                getattr(o, name)[k] = pointer(ctype._type_, item, "{}[{:d}]".format(name, k))
+        else:
+            setattr(o, name, pointer(ctype, a, name))
+    return o
 
 
 def quantiles(percentile, percentiles):

@@ -191,6 +191,7 @@ static int load_rccl()
 using mbbo::DevBuf;
 using mbbo::Dev;
 using mbbo::Pin;
+using mbbo::ResultBlock;
 int mbbo::dev_alloc(void **p, size_t bytes, DevKind kind)
 {
     if (kind == kDevFine) HIPCHK(hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained));
@@ -336,21 +337,23 @@ struct mbb_ctx {
         std::vector<mbbs::SrcConst> h_src;    // the per-source constants as uploaded (kept until the next call's)
         bool src_in_flight = false;           // ... and whether that upload may still be reading them
     } der;
-    struct SumWork { DevBuf part, state, hist, covpart, outbuf; } sum;          // ... the chain summary (summary_run)
+    // ... the column statistics and the select behind them (grow_stats, grow_select), shared: the analyses are synchronous, one at a time
+    struct StatWork { DevBuf part, state, hist; } stat;
+    struct SumWork { DevBuf covpart, outbuf; } sum;                             // ... the chain summary (summary_run)
     struct DiagWork {                                                           // ... the chain diagnostics (diag_run)
         DevBuf mean, seq, outbuf;
         size_t lds_granted = 0;               // dynamic-LDS ceiling already requested for k_diag_acf
     } diag;
     struct MargWork { DevBuf extent, range, part1, part2, outbuf; } marg;       // ... the chain marginals (marg_run)
-    struct PredWork { DevBuf samples, part, state, hist, status, outbuf; } pred;   // ... the predicted fluxes (pred_run)
+    struct PredWork { DevBuf samples, status, outbuf; } pred;                   // ... the predicted fluxes (pred_run)
     struct DrawWork { DevBuf rows, aux; } draw;     // ... the posterior draws (draws_run): the compact block, its lnprob and index
-    struct GoodWork { DevBuf samples, band, mf, rows, part, state, hist, best, status, outbuf; } good;   // ... and the goodness of fit (good_run)
+    struct GoodWork { DevBuf samples, band, mf, rows, best, status, outbuf; } good;   // ... and the goodness of fit (good_run)
     struct MapWork {                                                            // the posterior's maximum (mbb_map_fit)
         DevBuf start, outbuf;
         size_t lds_granted[8] = {};           // whether this context has asked for the dynamic-LDS ceiling, by instantiation of k_map_lm
     } map;
     struct EvWork { DevBuf mom, ints, slab, l1, l2, postq, neff, outbuf; } ev;  // the evidence of a chain (evidence_run)
-    struct PwWork { DevBuf cols, part, state, sel, hist, status, outbuf; } pw;  // the out-of-sample fit of a chain (pw_run)
+    struct PwWork { DevBuf cols, part, state, sel, status, outbuf; } pw;        // the out-of-sample fit of a chain (pw_run)
     long opt_pw_budget_mb = 16384;   // ... its two columns per band of a group may take this much; at least one band a group
     // options
     long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
@@ -2202,13 +2205,48 @@ extern "C" int mbb_sed_integrate_batch(mbb_ctx *c, const double *pars, int n, in
 }
 
 // ---- analyses of a resident chain: what the summary, the diagnostics and the marginals share ------------------------
-// A result block handed out array by array: take<T>(n) is its next n values of T, put(dst, n) copies them out of a
-// host image of the block.  (The callers list their arrays by falling alignment, the same list on either side.)
+// A work block cut up array by array, by falling alignment: take<T>(n) is its next n values of T.  (A block whose
+// arrays go home to the caller is a ResultBlock, mbb_owned.h.)
 struct Carve {
     char *p;
     template <typename T> T *take(size_t n) { T *r = (T *)p; p += n * sizeof(T); return r; }
-    template <typename T> void put(T *dst, size_t n) { memcpy(dst, take<T>(n), n * sizeof(T)); }
 };
+
+// The result list rb of an analysis on the device: its block made big enough, then every array's address handed out.
+static int place(mbb_ctx *c, DevBuf &block, ResultBlock &rb) { return rb.place(block, [c] { return sync_stream(c); }); }
+
+// ... and on its way home as one image, behind everything the stream holds: the caller waits, then rb.scatter().
+static int fetch_image(mbb_ctx *c, const DevBuf &block, ResultBlock &rb)
+{
+    HIPCHK(hipMemcpyAsync(rb.image(), block.p, rb.bytes(), hipMemcpyDeviceToHost, c->stream));
+    return MBB_OK;
+}
+
+// ... for a caller with nothing else to wait for: the image, the wait and the scatter.
+static int fetch_home(mbb_ctx *c, const DevBuf &block, ResultBlock &rb)
+{
+    if (const int rc = fetch_image(c, block, rb)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rb.scatter();
+    return MBB_OK;
+}
+
+// A launch grid of n blocks, or of a block per `per` of n items, fits in 31 bits.
+static int check_grid(size_t n, size_t per = 64) { return n > 0x7fffffffull / per ? fail(MBB_ERR_ARG, "too many sources") : MBB_OK; }
+
+// Whether the context is one rank of several: such a rank holds only its own walkers.
+static bool sharded_context(const mbb_ctx *c) { return (c->comm != nullptr && c->nranks > 1) || (c->x.connected && c->x.n > 1); }
+
+// The parameters a fit holds fixed (mbblm::lm_fixed_mask, a device function in this build): the caller's, lambda0 of an
+// optically thin model, alpha of a model without one.
+static uint32_t fixed_mask(const mbb_ctx *c, const int32_t fixed[5])
+{
+    uint32_t m = 0;
+    for (int i = 0; i < 5; ++i) if (fixed[i]) m |= 1u << i;
+    if (c->opthin) m |= 1u << 2;
+    if (c->noalpha) m |= 1u << 3;
+    return m;
+}
 
 // A host chain [cells][5], its lnprob [cells] behind it where given, on the device for as long as run(d_chain) takes.
 template <typename F>
@@ -2299,11 +2337,14 @@ static int check_window(const mbb_summary_spec *sp, int nsteps)
     return MBB_OK;
 }
 
+// A column's samples are counted in 32 bits (what: the refusal, which differs between the analyses).
+static int check_sample_cap(int burn, int thin, int nw, int nsteps, const char *what)
+{
+    return (long long)nw * kept_steps(burn, thin, nsteps) > 0xffffffffll ? fail(MBB_ERR_ARG, what) : MBB_OK;
+}
 static int check_sample_cap(const mbb_summary_spec *sp, int nw, int nsteps)
 {
-    if ((long long)nw * kept_steps(sp->burn, sp->thin, nsteps) > 0xffffffffll)
-        return fail(MBB_ERR_ARG, "more than 2^32 samples per column");
-    return MBB_OK;
+    return check_sample_cap(sp->burn, sp->thin, nw, nsteps, "more than 2^32 samples per column");
 }
 
 // A checked window of a chain as the kernels read it (the columns and their splits are the caller's).
@@ -2531,6 +2572,69 @@ static int derived_sync(mbb_ctx *c)
     return MBB_OK;
 }
 
+// ---- the column statistics of a chain (mbb_summary.hip.h), for every analysis that reduces columns ------------------
+// The percentiles of a call (what: the refusal of a wrong number of them, which names the call) ...
+static int check_percentiles(int npct, const double *pct, const char *what)
+{
+    if (npct < 1 || npct > mbbs::kMaxPct) return fail(MBB_ERR_ARG, what);
+    for (int k = 0; k < npct; ++k)
+        if (!(pct[k] >= 0.0 && pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
+    return MBB_OK;
+}
+
+// ... as the kernels read them.
+static void set_percentiles(mbbs::SumArgs &a, int npct, const double *pct)
+{
+    a.npct = npct;
+    for (int k = 0; k < npct; ++k) a.pct[k] = pct[k];
+}
+
+// The context's work buffers for the statistics of ncolumns columns in splits (part, state), and for their select
+// (hist).  An analysis with two views grows for both before it takes a pointer.
+static int grow_stats(mbb_ctx *c, size_t ncolumns, int splits)
+{
+    if (const int rc = grow(c, c->stat.part, ncolumns * splits * mbbs::kStatWords * sizeof(double))) return rc;
+    return grow(c, c->stat.state, ncolumns * sizeof(mbbs::ColState));
+}
+static int grow_select(mbb_ctx *c, size_t ncolumns, int splits)
+{
+    return grow(c, c->stat.hist, ncolumns * splits * mbbs::kMaxRanks * 256 * sizeof(unsigned int));
+}
+
+// The statistics of a's ncolumns columns, and the select's start from them.  (Launches only: the caller asks
+// hipGetLastError with its own.)
+static void launch_stats(mbb_ctx *c, const mbbs::SumArgs &a, size_t ncolumns)
+{
+    const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
+    hipLaunchKernelGGL(mbbs::k_sum_stats, gcol, dim3(mbbs::kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(mbbs::k_sum_begin, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a);
+}
+
+// ... and the select of their percentiles, a byte of the key per pass.
+static void launch_select(mbb_ctx *c, const mbbs::SumArgs &a, size_t ncolumns)
+{
+    const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
+    for (int pass = 0; pass < 8; ++pass) {
+        hipLaunchKernelGGL(mbbs::k_sum_hist, gcol, dim3(mbbs::kThreads), 0, c->stream, a, pass);
+        hipLaunchKernelGGL(mbbs::k_sum_pick, dim3((unsigned)ncolumns), dim3(mbbs::kThreads), 0, c->stream, a);
+    }
+}
+
+// The chain's rows a chunk at a time: their records by launch_prologue (the fit's model), then fill(off, n) on rows
+// [off, off + n).
+static size_t chunk_rows(size_t cells) { return std::min<size_t>(cells, (size_t)kSumChunkRows); }
+template <typename Fill>
+static int for_row_chunks(mbb_ctx *c, const double *d_chain, size_t cells, double wavenorm, Fill &&fill)
+{
+    const size_t chunk = chunk_rows(cells);
+    for (size_t off = 0; off < cells; off += chunk) {
+        const int n = (int)std::min(chunk, cells - off);
+        if (const int rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, wavenorm, 0, nullptr)) return rc;
+        if (const int rc = fill(off, n)) return rc;
+    }
+    return MBB_OK;
+}
+
 // ---- posterior summaries of a chain (mbb_summary.hip.h) ------------------------
 // Summarise a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
 static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
@@ -2544,10 +2648,8 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
         !o->best_index)
         return fail(MBB_ERR_ARG, "null summary argument");
     if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
-    if (sp->npct < 1 || sp->npct > kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per summary");
-    for (int k = 0; k < sp->npct; ++k)
-        if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
     int rc;
+    if ((rc = check_percentiles(sp->npct, sp->pct, "1 to 8 percentiles per summary"))) return rc;
     if ((rc = check_window(sp, nsteps)) || (rc = check_derived_settings(sp, nsrc)) ||
         (rc = check_sample_cap(sp, nw, nsteps)))
         return rc;
@@ -2555,8 +2657,7 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
     memset(&a, 0, sizeof a);
     fill_chain_view(a, d_chain, nsrc, nw, nsteps, sp, 16384);            // (splits of 64 samples per thread)
     a.lnprob = d_lnprob;
-    a.npct = sp->npct;
-    for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
+    set_percentiles(a, sp->npct, sp->pct);
     for (int k = 0; k < kCols; ++k) {
         a.has_lo[k] = sp->has_lo[k] != 0; a.has_hi[k] = sp->has_hi[k] != 0;
         a.lo[k] = sp->lo[k]; a.hi[k] = sp->hi[k];
@@ -2564,43 +2665,26 @@ static int summary_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob
     const size_t ncolumns = (size_t)nsrc * a.ncol, sc = (size_t)nsrc * kCols, ns = (size_t)nsrc;
     mbb_ctx::SumWork &w = c->sum;
     const size_t np = (size_t)sp->npct;
-    // the result block: 64-bit counts, doubles, 32-bit words
-    const size_t out_bytes = sc * sizeof(long long) + (sc * (3 + np) + ns * (25 + 6)) * sizeof(double) +
-                             (sc + ns * 2) * sizeof(int);
-    if ((rc = grow(c, w.part, ncolumns * a.splits * kStatWords * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.state, ncolumns * sizeof(ColState)))) return rc;
-    if ((rc = grow(c, w.hist, ncolumns * a.splits * kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    ResultBlock rb;                              // 64-bit counts, doubles, 32-bit words
+    rb.add(&a.o_nused, sc, o->n_used);
+    rb.add(&a.o_mean, sc, o->mean); rb.add(&a.o_min, sc, o->min); rb.add(&a.o_max, sc, o->max);
+    rb.add(&a.o_pct, sc * np, o->pct);
+    rb.add(&a.o_cov, ns * 25, o->cov); rb.add(&a.o_best, ns * 6, o->best);
+    rb.add(&a.o_status, sc, o->status); rb.add(&a.o_bestidx, ns * 2, o->best_index);
+    if ((rc = grow_stats(c, ncolumns, a.splits)) || (rc = grow_select(c, ncolumns, a.splits))) return rc;
     if ((rc = grow(c, w.covpart, ns * a.splits * kCovWords * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
-    a.part = (double *)w.part.p; a.state = (ColState *)w.state.p; a.hist = (unsigned int *)w.hist.p;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
+    a.part = (double *)c->stat.part.p; a.state = (ColState *)c->stat.state.p; a.hist = (unsigned int *)c->stat.hist.p;
     a.covpart = (double *)w.covpart.p;
-    Carve ob{(char *)w.outbuf.p};
-    a.o_nused = ob.take<long long>(sc);
-    a.o_mean = ob.take<double>(sc); a.o_min = ob.take<double>(sc); a.o_max = ob.take<double>(sc);
-    a.o_pct = ob.take<double>(sc * np);
-    a.o_cov = ob.take<double>(ns * 25); a.o_best = ob.take<double>(ns * 6);
-    a.o_status = ob.take<int>(sc); a.o_bestidx = ob.take<int>(ns * 2);
     if ((rc = summary_fill_derived(c, sp, a))) return rc;
     a.colstatus = (int *)c->der.colstatus.p;
-    const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits), gsrc((unsigned)nsrc, (unsigned)a.splits);
-    hipLaunchKernelGGL(k_sum_stats, gcol, dim3(kThreads), 0, c->stream, a);
-    hipLaunchKernelGGL(k_sum_begin, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a);
-    for (int pass = 0; pass < 8; ++pass) {
-        hipLaunchKernelGGL(k_sum_hist, gcol, dim3(kThreads), 0, c->stream, a, pass);
-        hipLaunchKernelGGL(k_sum_pick, dim3((unsigned)ncolumns), dim3(kThreads), 0, c->stream, a);
-    }
-    hipLaunchKernelGGL(k_sum_cov, gsrc, dim3(kThreads), 0, c->stream, a);
+    launch_stats(c, a, ncolumns);
+    launch_select(c, a, ncolumns);
+    hipLaunchKernelGGL(k_sum_cov, dim3((unsigned)nsrc, (unsigned)a.splits), dim3(kThreads), 0, c->stream, a);
     hipLaunchKernelGGL(k_sum_finish, dim3((unsigned)(((size_t)nsrc * kCols + 63) / 64)), dim3(64), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = derived_sync(c))) return rc;
-    Carve hb{host.data()};
-    hb.put(o->n_used, sc);
-    hb.put(o->mean, sc); hb.put(o->min, sc); hb.put(o->max, sc);
-    hb.put(o->pct, sc * np);
-    hb.put(o->cov, ns * 25); hb.put(o->best, ns * 6);
-    hb.put(o->status, sc); hb.put(o->best_index, ns * 2);
+    if ((rc = fetch_image(c, w.outbuf, rb)) || (rc = derived_sync(c))) return rc;
+    rb.scatter();
     return MBB_OK;
 }
 
@@ -2646,8 +2730,7 @@ static int diag_check(int nsrc, int nw, int nsteps, const mbb_diag_spec *sp, con
     const int n = nsteps - sp->burn;
     if (n > mbbg::kMaxSteps) return fail(MBB_ERR_ARG, "more than 16384 kept steps per series: raise burn");
     if (sp->nacf < 0 || sp->nacf > n) return fail(MBB_ERR_ARG, "nacf must be between 0 and the number of kept steps");
-    if ((size_t)nsrc * 5 > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
-    return MBB_OK;
+    return check_grid((size_t)nsrc * 5);
 }
 
 // Diagnose a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
@@ -2667,15 +2750,14 @@ static int diag_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     a.nsrc = nsrc; a.nw = nw; a.nsteps = nsteps; a.burn = sp->burn; a.n = n;
     a.method = sp->method; a.nacf = (int)nacf; a.c = sp->c; a.tol = sp->tol;
     mbb_ctx::DiagWork &w = c->diag;
-    const size_t out_bytes = ncol * (3 + nacf) * sizeof(double) + ncol * 2 * sizeof(int);   // the result block
+    ResultBlock rb;
+    rb.add(&a.o_tau, ncol, o->tau); rb.add(&a.o_ess, ncol, o->ess); rb.add(&a.o_rhat, ncol, o->rhat);
+    rb.add(&a.o_acf, ncol * nacf, o->acf);                   // (empty, and null to the kernels, when not asked for)
+    rb.add(&a.o_window, ncol, o->window); rb.add(&a.o_status, ncol, o->status);
     if (sp->method == MBB_DIAG_MEAN && (rc = grow(c, w.mean, ncol * n * sizeof(double)))) return rc;
     if ((rc = grow(c, w.seq, ncol * nw * 4 * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
     a.mean = (double *)w.mean.p; a.seq = (double *)w.seq.p;
-    Carve ob{(char *)w.outbuf.p};
-    a.o_tau = ob.take<double>(ncol); a.o_ess = ob.take<double>(ncol); a.o_rhat = ob.take<double>(ncol);
-    a.o_acf = nacf ? ob.take<double>(ncol * nacf) : nullptr;
-    a.o_window = ob.take<int>(ncol); a.o_status = ob.take<int>(ncol);
     const size_t lds = acf_lds_bytes(n);
     if (lds > 60 * 1024 && lds > w.lds_granted) {
         // (beyond 64 KB of LDS per workgroup, the kernel's 2.3 KB of static LDS included, its dynamic-LDS ceiling has
@@ -2686,7 +2768,7 @@ static int diag_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     }
     if (sp->method == MBB_DIAG_MEAN) {
         const size_t per = ((size_t)n * 5 + kThreads - 1) / kThreads;
-        if (per * nsrc > 0x7fffffffull) return fail(MBB_ERR_ARG, "too many sources");
+        if ((rc = check_grid(per * nsrc, 1))) return rc;
         hipLaunchKernelGGL(k_diag_mean, dim3((unsigned)(per * nsrc)), dim3(kThreads), 0, c->stream, a);
     }
     hipLaunchKernelGGL(k_diag_acf, dim3((unsigned)ncol), dim3(kThreads), lds, c->stream, a);
@@ -2696,14 +2778,7 @@ static int diag_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     hipLaunchKernelGGL(k_diag_seq, dim3((unsigned)ncol, (unsigned)gy), dim3(kThreads), 0, c->stream, a);
     hipLaunchKernelGGL(k_diag_rhat, dim3((unsigned)ncol), dim3(kThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    Carve hb{host.data()};
-    hb.put(o->tau, ncol); hb.put(o->ess, ncol); hb.put(o->rhat, ncol);
-    if (nacf) hb.put(o->acf, ncol * nacf);
-    hb.put(o->window, ncol); hb.put(o->status, ncol);
-    return MBB_OK;
+    return fetch_home(c, w.outbuf, rb);
 }
 
 extern "C" int mbb_chain_diagnostics(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
@@ -2756,8 +2831,7 @@ static int marg_check(int nsrc, int nw, int nsteps, const mbb_marginals_spec *sp
             return fail(MBB_ERR_ARG, "a range must be finite with lo < hi");
     }
     if ((rc = check_derived_settings(ss, nsrc)) || (rc = check_sample_cap(ss, nw, nsteps))) return rc;
-    if ((size_t)nsrc * (kCols + kMaxPairs) > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
-    return MBB_OK;
+    return check_grid((size_t)nsrc * (kCols + kMaxPairs));
 }
 
 // Bin a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
@@ -2779,24 +2853,23 @@ static int marg_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     for (int k = 0; k < kCols; ++k) { a.has_range[k] = sp->has_range[k] != 0; a.lo[k] = sp->lo[k]; a.hi[k] = sp->hi[k]; }
     const size_t ncolumns = (size_t)nsrc * a.ncol, npairs = (size_t)nsrc * a.npairs;
     const size_t sc = (size_t)nsrc * kCols, nb = (size_t)a.nbins, nb2 = (size_t)a.nbins2;
-    // the result block: doubles, 64-bit counts, 32-bit words
     const size_t n_e1 = sc * (nb + 1), n_e2 = nb2 ? sc * (nb2 + 1) : 0, n_c1 = sc * nb, n_c2 = npairs * nb2 * nb2;
-    const size_t out_bytes = (n_e1 + n_e2) * sizeof(double) + 4 * sc * sizeof(long long) +
-                             (n_c1 + n_c2) * sizeof(unsigned int) + sc * sizeof(int);
+    ResultBlock rb;                              // doubles, 64-bit counts, 32-bit words
+    // (edges2 and counts2 are empty, and null to the kernels, without 2-d tables: k_marg_edges writes edges2 only with
+    // nbins2 > 0, k_marg_hist2 is not launched and k_marg_merge has no pair block without pairs)
+    rb.add(&a.o_edges1, n_e1, o->edges1); rb.add(&a.o_edges2, n_e2, o->edges2);
+    rb.add(&a.o_used, sc, o->n_used); rb.add(&a.o_below, sc, o->n_below);
+    rb.add(&a.o_above, sc, o->n_above); rb.add(&a.o_nonfinite, sc, o->n_nonfinite);
+    rb.add(&a.o_counts1, n_c1, o->counts1); rb.add(&a.o_counts2, n_c2, o->counts2);
+    rb.add(&a.o_status, sc, o->status);
     mbb_ctx::MargWork &w = c->marg;
     if ((rc = grow(c, w.extent, ncolumns * a.splits * 2 * sizeof(double)))) return rc;
     if ((rc = grow(c, w.range, sc * sizeof(Range)))) return rc;
     if ((rc = grow(c, w.part1, ncolumns * a.splits * (nb + kTail) * sizeof(unsigned int)))) return rc;
     if (npairs && (rc = grow(c, w.part2, npairs * a.splits * nb2 * nb2 * sizeof(unsigned int)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
     a.extent = (double *)w.extent.p; a.range = (Range *)w.range.p;
     a.part1 = (unsigned int *)w.part1.p; a.part2 = (unsigned int *)w.part2.p;
-    Carve ob{(char *)w.outbuf.p};
-    a.o_edges1 = ob.take<double>(n_e1); a.o_edges2 = ob.take<double>(n_e2);
-    a.o_used = ob.take<long long>(sc); a.o_below = ob.take<long long>(sc);
-    a.o_above = ob.take<long long>(sc); a.o_nonfinite = ob.take<long long>(sc);
-    a.o_counts1 = ob.take<unsigned int>(n_c1); a.o_counts2 = ob.take<unsigned int>(n_c2);
-    a.o_status = ob.take<int>(sc);
     if ((rc = summary_fill_derived(c, sp->summary, a))) return rc;
     a.colstatus = (const int *)c->der.colstatus.p;
     const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
@@ -2807,15 +2880,12 @@ static int marg_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
         hipLaunchKernelGGL(k_marg_hist2, dim3((unsigned)npairs, (unsigned)a.splits), dim3(kThreads), 0, c->stream, a);
     hipLaunchKernelGGL(k_marg_merge, dim3((unsigned)(sc + npairs)), dim3(kThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(o->edges1, a.o_edges1, n_e1 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (n_e2) HIPCHK(hipMemcpyAsync(o->edges2, a.o_edges2, n_e2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(o->n_used, a.o_used, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(o->n_below, a.o_below, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(o->n_above, a.o_above, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(o->n_nonfinite, a.o_nonfinite, sc * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(o->counts1, a.o_counts1, n_c1 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-    if (n_c2) HIPCHK(hipMemcpyAsync(o->counts2, a.o_counts2, n_c2 * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(o->status, a.o_status, sc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    // (the tables are large: each array straight into the caller's, no image in between)
+    if ((rc = rb.each([&](void *dst, size_t off, size_t bytes) -> int {
+            HIPCHK(hipMemcpyAsync(dst, (const char *)w.outbuf.p + off, bytes, hipMemcpyDeviceToHost, c->stream));
+            return MBB_OK;
+        })))
+        return rc;
     return derived_sync(c);
 }
 
@@ -2858,14 +2928,12 @@ static int pred_check(int nsrc, int nw, int nsteps, const mbb_predict_spec *sp, 
         if (!(sp->freq[i] > 0.0 && sp->freq[i] < INFINITY)) return fail(MBB_ERR_ARG, "a frequency must be finite and positive");
         if (!(sp->weight[i] - sp->weight[i] == 0.0)) return fail(MBB_ERR_ARG, "a weight must be finite");
     }
-    if (sp->npct < 1 || sp->npct > mbbs::kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per prediction call");
-    for (int k = 0; k < sp->npct; ++k)
-        if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
-    if (const int rc = check_burn_thin(sp->burn, sp->thin, nsteps)) return rc;
+    int rc;
+    if ((rc = check_percentiles(sp->npct, sp->pct, "1 to 8 percentiles per prediction call"))) return rc;
+    if ((rc = check_burn_thin(sp->burn, sp->thin, nsteps))) return rc;
     if (!(sp->wavenorm >= 0.0 && sp->wavenorm < INFINITY)) return fail(MBB_ERR_ARG, "wavenorm must be positive (0: the context's)");
-    if ((long long)nw * kept_steps(sp->burn, sp->thin, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
-    if ((size_t)nsrc * mbbp::kGroup > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
-    return MBB_OK;
+    if ((rc = check_sample_cap(sp->burn, sp->thin, nw, nsteps, "more than 2^32 - 1 samples per column"))) return rc;
+    return check_grid((size_t)nsrc * mbbp::kGroup);
 }
 
 // Predict from a chain that is on the device in emcee's layout.  Synchronous; the results land in the caller's arrays.
@@ -2881,31 +2949,24 @@ static int pred_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
     mbbs::SumArgs a;
     memset(&a, 0, sizeof a);
     fill_window_fixed(a, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
-    a.npct = sp->npct;
-    for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
+    set_percentiles(a, sp->npct, sp->pct);
     const int ngmax = std::min(nspec, kGroup);
-    const size_t ncolmax = (size_t)nsrc * ngmax;
     mbb_ctx::PredWork &w = c->pred;
-    // the result block: 64-bit counts, doubles, 32-bit words
-    const size_t out_bytes = sn * sizeof(long long) + sn * (3 + np) * sizeof(double) + sn * sizeof(int);
-    if ((rc = grow(c, w.samples, (size_t)ns * 3 * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.part, ncolmax * a.splits * mbbs::kStatWords * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.state, ncolmax * sizeof(mbbs::ColState)))) return rc;
-    if ((rc = grow(c, w.hist, ncolmax * a.splits * mbbs::kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
-    if ((rc = grow(c, w.status, sn * sizeof(int)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
-    if ((rc = grow(c, c->der.der, (size_t)ngmax * cells * sizeof(double)))) return rc;
-    const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
-    if ((rc = ensure_sed(c, chunk, 0))) return rc;
-    a.part = (double *)w.part.p; a.state = (mbbs::ColState *)w.state.p; a.hist = (unsigned int *)w.hist.p;
     FinishArgs f;
     f.nspec = nspec;
+    ResultBlock rb;                              // 64-bit counts, doubles, 32-bit words
+    rb.add(&f.o_nused, sn, o->n_used);
+    rb.add(&f.o_mean, sn, o->mean); rb.add(&f.o_min, sn, o->min); rb.add(&f.o_max, sn, o->max);
+    rb.add(&f.o_pct, sn * np, o->pct);
+    rb.add(&f.o_status, sn, o->status);
+    if ((rc = grow(c, w.samples, (size_t)ns * 3 * sizeof(double)))) return rc;
+    if ((rc = grow_stats(c, (size_t)nsrc * ngmax, a.splits)) || (rc = grow_select(c, (size_t)nsrc * ngmax, a.splits))) return rc;
+    if ((rc = grow(c, w.status, sn * sizeof(int)))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
+    if ((rc = grow(c, c->der.der, (size_t)ngmax * cells * sizeof(double)))) return rc;
+    if ((rc = ensure_sed(c, chunk_rows(cells), 0))) return rc;
+    a.part = (double *)c->stat.part.p; a.state = (mbbs::ColState *)c->stat.state.p; a.hist = (unsigned int *)c->stat.hist.p;
     f.pstatus = (const int *)w.status.p;
-    Carve ob{(char *)w.outbuf.p};
-    f.o_nused = ob.take<long long>(sn);
-    f.o_mean = ob.take<double>(sn); f.o_min = ob.take<double>(sn); f.o_max = ob.take<double>(sn);
-    f.o_pct = ob.take<double>(sn * np);
-    f.o_status = ob.take<int>(sn);
     double *const d_nu = (double *)w.samples.p, *const d_ln = d_nu + ns, *const d_wt = d_ln + ns;
     // (the caller's arrays are pageable: the copies below have read them when they return)
     HIPCHK(hipMemcpyAsync(d_nu, sp->freq, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -2937,9 +2998,7 @@ static int pred_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
         const bool stage = staged > 0 && staged <= kLdsSamples;
         fa.nstaged = stage ? staged : 0;
         const size_t lds = (size_t)fa.nstaged * 3 * sizeof(double);
-        for (size_t off = 0; off < cells; off += chunk) {
-            const int n = (int)std::min(chunk, cells - off);
-            if ((rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, wavenorm, 0, nullptr))) return rc;
+        if ((rc = for_row_chunks(c, d_chain, cells, wavenorm, [&](size_t off, int n) -> int {
             fa.n = n; fa.off = (long long)off;
             const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
             dispatch_variant(c->opthin, c->noalpha, [&](auto OT, auto NA) {
@@ -2951,28 +3010,17 @@ static int pred_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nst
                                        c->stream, fa);
             });
             HIPCHK(hipGetLastError());
-        }
+            return MBB_OK;
+        })))
+            return rc;
         const size_t ncolumns = (size_t)nsrc * ng;
-        const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
-        hipLaunchKernelGGL(mbbs::k_sum_stats, gcol, dim3(mbbs::kThreads), 0, c->stream, a);
-        hipLaunchKernelGGL(mbbs::k_sum_begin, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a);
-        for (int pass = 0; pass < 8; ++pass) {
-            hipLaunchKernelGGL(mbbs::k_sum_hist, gcol, dim3(mbbs::kThreads), 0, c->stream, a, pass);
-            hipLaunchKernelGGL(mbbs::k_sum_pick, dim3((unsigned)ncolumns), dim3(mbbs::kThreads), 0, c->stream, a);
-        }
+        launch_stats(c, a, ncolumns);
+        launch_select(c, a, ncolumns);
         f.spec0 = spec0;
         hipLaunchKernelGGL(k_pred_finish, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a, f);
         HIPCHK(hipGetLastError());
     }
-    std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    Carve hb{host.data()};
-    hb.put(o->n_used, sn);
-    hb.put(o->mean, sn); hb.put(o->min, sn); hb.put(o->max, sn);
-    hb.put(o->pct, sn * np);
-    hb.put(o->status, sn);
-    return MBB_OK;
+    return fetch_home(c, w.outbuf, rb);
 }
 
 extern "C" int mbb_chain_predict(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
@@ -3130,13 +3178,10 @@ static int good_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_
     if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
     int rc;
     if ((rc = good_check_ctx(c, nsrc))) return rc;
-    if (sp->npct < 1 || sp->npct > mbbs::kMaxPct) return fail(MBB_ERR_ARG, "1 to 8 percentiles per goodness call");
-    for (int k = 0; k < sp->npct; ++k)
-        if (!(sp->pct[k] >= 0.0 && sp->pct[k] <= 100.0)) return fail(MBB_ERR_ARG, "percentiles must be in [0, 100]");
+    if ((rc = check_percentiles(sp->npct, sp->pct, "1 to 8 percentiles per goodness call"))) return rc;
     if ((rc = check_burn_thin(sp->burn, sp->thin, nsteps))) return rc;
-    if ((long long)nw * kept_steps(sp->burn, sp->thin, nsteps) > 0xffffffffll) return fail(MBB_ERR_ARG, "more than 2^32 - 1 samples per column");
-    if ((size_t)nsrc * 5 > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
-    return MBB_OK;
+    if ((rc = check_sample_cap(sp->burn, sp->thin, nw, nsteps, "more than 2^32 - 1 samples per column"))) return rc;
+    return check_grid((size_t)nsrc * 5);
 }
 
 // The context's bands on the device as the goodness kernels read them: samples, their logarithms, weights, the band table.
@@ -3234,42 +3279,41 @@ static int good_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, i
     memset(&a, 0, sizeof a);
     fill_window_fixed(a, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
     a.lnprob = d_lnprob;
-    a.npct = sp->npct;
-    for (int k = 0; k < sp->npct; ++k) a.pct[k] = sp->pct[k];
+    set_percentiles(a, sp->npct, sp->pct);
     a.ncol = 2; a.col[0] = 5; a.col[1] = 6;
     mbb_ctx::GoodWork &w = c->good;
-    const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
     const size_t nev = 2 * ns;                              // rows evaluated at the end: theta-bar and the ML entry of every source
-    const size_t rows_max = std::max(chunk, nev);
-    // the result block: 64-bit counts, doubles, 32-bit words
-    const size_t out_doubles = s2 * (3 + np) + ns * 7 * 2 + ns * 2 + nev * 2 + nev * nb;
-    const size_t out_bytes = s2 * sizeof(long long) + out_doubles * sizeof(double) + (s2 + ns * 4 + nev) * sizeof(int);
-    if ((rc = grow(c, w.part, std::max(ns * 5 * a5.splits, s2 * a.splits) * mbbs::kStatWords * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.state, ns * 5 * sizeof(mbbs::ColState)))) return rc;
-    if ((rc = grow(c, w.hist, s2 * a.splits * mbbs::kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    const size_t rows_max = std::max(chunk_rows(cells), nev);
+    FinishArgs f;
+    PickArgs pk;
+    double *ev_chisq, *ev_q, *ev_mf;                        // those rows' chisq, q and band fluxes [nev][nb], their status
+    int *ev_status;
+    ResultBlock rb;                              // 64-bit counts, doubles, 32-bit words
+    rb.add(&f.o_nused, s2, o->n_used);
+    rb.add(&f.o_mean, s2, o->mean); rb.add(&f.o_min, s2, o->min); rb.add(&f.o_max, s2, o->max);
+    rb.add(&f.o_pct, s2 * np, o->pct);
+    rb.add(&f.o_atmean, ns * 7, o->at_mean); rb.add(&f.o_ml, ns * 7, o->ml);
+    rb.add(&pk.o_best, ns * 2, o->best);
+    rb.add(&ev_chisq, nev); rb.add(&ev_q, nev);             // (the rows' chisq and q go home in at_mean and ml)
+    rb.add(&ev_mf, nev * nb, o->ml_model, ns * nb);         // (theta-bar's band fluxes stay; the ML entries' go home)
+    rb.add(&f.o_status, s2, o->status);
+    rb.add(&pk.o_mlidx, ns * 2, o->ml_index); rb.add(&pk.o_bestidx, ns * 2, o->best_index);
+    rb.add(&ev_status, nev);
+    // (two views, theta-bar's five columns and the two columns, through the same part and state in stream order)
+    if ((rc = grow_stats(c, ns * 5, a5.splits)) || (rc = grow_stats(c, s2, a.splits)) || (rc = grow_select(c, s2, a.splits))) return rc;
     if ((rc = grow(c, w.best, ns * a.splits * kBestWords * sizeof(double)))) return rc;
     if ((rc = grow(c, w.status, s2 * sizeof(int)))) return rc;
     if ((rc = grow(c, w.rows, nev * 5 * sizeof(double)))) return rc;
     if ((rc = grow(c, w.mf, rows_max * nb * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
     if ((rc = grow(c, c->der.der, 2 * cells * sizeof(double)))) return rc;
     if ((rc = ensure_sed(c, rows_max, 0))) return rc;
     double *const col0 = (double *)c->der.der.p, *const col1 = col0 + cells;
     a.der[0] = col0; a.der[1] = col1;
-    a5.part = a.part = (double *)w.part.p; a5.state = a.state = (mbbs::ColState *)w.state.p; a.hist = (unsigned int *)w.hist.p;
+    a5.part = a.part = (double *)c->stat.part.p; a5.state = a.state = (mbbs::ColState *)c->stat.state.p;
+    a.hist = (unsigned int *)c->stat.hist.p;
     double *const d_rows = (double *)w.rows.p;
-    FinishArgs f;
-    PickArgs pk;
-    Carve ob{(char *)w.outbuf.p};
-    f.o_nused = ob.take<long long>(s2);
-    f.o_mean = ob.take<double>(s2); f.o_min = ob.take<double>(s2); f.o_max = ob.take<double>(s2);
-    f.o_pct = ob.take<double>(s2 * np);
-    f.o_atmean = ob.take<double>(ns * 7); f.o_ml = pk.o_ml = ob.take<double>(ns * 7);
-    pk.o_best = ob.take<double>(ns * 2);
-    double *const ev_chisq = ob.take<double>(nev), *const ev_q = ob.take<double>(nev), *const ev_mf = ob.take<double>(nev * nb);
-    f.o_status = ob.take<int>(s2);
-    pk.o_mlidx = ob.take<int>(ns * 2); pk.o_bestidx = ob.take<int>(ns * 2);
-    int *const ev_status = ob.take<int>(nev);
+    pk.o_ml = f.o_ml;
     f.gstatus = (const int *)w.status.p;
     f.tbar = d_rows; f.ev_chisq = ev_chisq; f.ev_q = ev_q;
     pk.part = (const double *)w.best.p; pk.ml_row = d_rows + ns * 5;
@@ -3277,32 +3321,22 @@ static int good_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, i
     if ((rc = good_upload_bands(c, fa))) return rc;
     HIPCHK(hipMemsetAsync(w.status.p, 0, s2 * sizeof(int), c->stream));
     // theta-bar
-    {
-        const size_t ncol5 = ns * 5;
-        hipLaunchKernelGGL(mbbs::k_sum_stats, dim3((unsigned)ncol5, (unsigned)a5.splits), dim3(mbbs::kThreads), 0, c->stream, a5);
-        hipLaunchKernelGGL(mbbs::k_sum_begin, dim3((unsigned)((ncol5 + 63) / 64)), dim3(64), 0, c->stream, a5);
-        hipLaunchKernelGGL(k_good_mean, dim3((unsigned)((ncol5 + 63) / 64)), dim3(64), 0, c->stream, a5, d_rows);
-        HIPCHK(hipGetLastError());
-    }
+    launch_stats(c, a5, ns * 5);
+    hipLaunchKernelGGL(k_good_mean, dim3((unsigned)((ns * 5 + 63) / 64)), dim3(64), 0, c->stream, a5, d_rows);
+    HIPCHK(hipGetLastError());
     // the columns, a chunk of rows at a time
-    for (size_t off = 0; off < cells; off += chunk) {
-        const int n = (int)std::min(chunk, cells - off);
-        if ((rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
+    rc = for_row_chunks(c, d_chain, cells, c->wavenorm, [&](size_t off, int n) {
         ChiArgs ca;
         memset(&ca, 0, sizeof ca);
         ca.off = ca.out = (long long)off; ca.rows_per_src = (long long)nw * nsteps;
         ca.chisq = col0; ca.q = col1;
         ca.gstatus = (int *)w.status.p; ca.nw = nw; ca.nsteps = nsteps; ca.burn = sp->burn; ca.thin = sp->thin;
-        if ((rc = good_eval(c, fa, ca, n))) return rc;
-    }
+        return good_eval(c, fa, ca, n);
+    });
+    if (rc) return rc;
     // their statistics, by the summary's kernels
-    const dim3 gcol((unsigned)s2, (unsigned)a.splits);
-    hipLaunchKernelGGL(mbbs::k_sum_stats, gcol, dim3(mbbs::kThreads), 0, c->stream, a);
-    hipLaunchKernelGGL(mbbs::k_sum_begin, dim3((unsigned)((s2 + 63) / 64)), dim3(64), 0, c->stream, a);
-    for (int pass = 0; pass < 8; ++pass) {
-        hipLaunchKernelGGL(mbbs::k_sum_hist, gcol, dim3(mbbs::kThreads), 0, c->stream, a, pass);
-        hipLaunchKernelGGL(mbbs::k_sum_pick, dim3((unsigned)s2), dim3(mbbs::kThreads), 0, c->stream, a);
-    }
+    launch_stats(c, a, s2);
+    launch_select(c, a, s2);
     // the maximum-likelihood and the maximum-lnprob entries
     hipLaunchKernelGGL(k_good_best, dim3((unsigned)nsrc, (unsigned)a.splits), dim3(kThreads), 0, c->stream, a, (double *)w.best.p);
     hipLaunchKernelGGL(k_good_pick, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, c->stream, a, pk);
@@ -3318,21 +3352,7 @@ static int good_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, i
     }
     hipLaunchKernelGGL(k_good_finish, dim3((unsigned)((s2 + 63) / 64)), dim3(64), 0, c->stream, a, f);
     HIPCHK(hipGetLastError());
-    std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    Carve hb{host.data()};
-    hb.put(o->n_used, s2);
-    hb.put(o->mean, s2); hb.put(o->min, s2); hb.put(o->max, s2);
-    hb.put(o->pct, s2 * np);
-    hb.put(o->at_mean, ns * 7); hb.put(o->ml, ns * 7);
-    hb.put(o->best, ns * 2);
-    hb.take<double>(nev * 2);                                // (the rows' chisq and q: in at_mean and ml already)
-    hb.take<double>(ns * nb);                                // (theta-bar's band fluxes)
-    hb.put(o->ml_model, ns * nb);
-    hb.put(o->status, s2);
-    hb.put(o->ml_index, ns * 2); hb.put(o->best_index, ns * 2);
-    return MBB_OK;
+    return fetch_home(c, w.outbuf, rb);
 }
 
 extern "C" int mbb_chain_goodness(mbb_ctx *c, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
@@ -3415,8 +3435,7 @@ static int pw_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_po
     const long long kept = kept_steps(sp->burn, sp->thin, nsteps);
     if ((long long)nw * kept > MBB_PW_MAX_WINDOW || mbbps::ps_tail_len((long long)nw * kept) > mbbps::kTailMax)
         return fail(MBB_ERR_ARG, "the window's tail would be longer than one workgroup sorts (MBB_PW_MAX_WINDOW entries per source)");
-    if ((size_t)nsrc * c->nb > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
-    return MBB_OK;
+    return check_grid((size_t)nsrc * c->nb);
 }
 
 // k_pw_g on the band fluxes good_flux has just made of n rows.  ga carries where the results go and the group.
@@ -3448,46 +3467,44 @@ static int pw_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nstep
     a.ivar = c->data.ivar.d(); a.invcov = c->has_cov ? c->data.invcov.d() : nullptr; a.nsrc_data = c->nsrc;
     mbb_ctx::PwWork &w = c->pw;
     mbb_ctx::GoodWork &gw = c->good;
-    const size_t chunk = std::min<size_t>(cells, (size_t)kSumChunkRows);
+    const size_t chunk = chunk_rows(cells);
     const size_t nsel = (size_t)((group + kSelCols - 1) / kSelCols) * ns * kSelCols;
-    const size_t out_bytes = tab * sizeof(long long) + tab * 7 * sizeof(double) + tab * 2 * sizeof(int);
+    ResultBlock rb;                              // 64-bit counts, doubles, 32-bit words
+    rb.add(&a.o_nused, tab, o->n_used);
+    rb.add(&a.o_lppd, tab, o->lppd); rb.add(&a.o_pwaic, tab, o->p_waic); rb.add(&a.o_elpdwaic, tab, o->elpd_waic);
+    rb.add(&a.o_elpdloo, tab, o->elpd_loo); rb.add(&a.o_ploo, tab, o->p_loo); rb.add(&a.o_khat, tab, o->khat);
+    rb.add(&a.o_pit, tab, o->loo_pit);
+    rb.add(&a.o_tail, tab, o->tail_len); rb.add(&a.o_status, tab, o->status);
     if ((rc = grow(c, w.cols, (size_t)group * 2 * cells * sizeof(double)))) return rc;
     if ((rc = grow(c, w.part, ns * group * a.splits * (kPartWords + 1) * sizeof(double)))) return rc;
     if ((rc = grow(c, w.state, ns * group * sizeof(PwState)))) return rc;
     if ((rc = grow(c, w.sel, nsel * sizeof(mbbs::ColState)))) return rc;
-    if ((rc = grow(c, w.hist, ns * kSelCols * a.splits * mbbs::kMaxRanks * 256 * sizeof(unsigned int)))) return rc;
+    if ((rc = grow_select(c, ns * kSelCols, a.splits))) return rc;
     if ((rc = grow(c, w.status, ns * sizeof(int)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
     if ((rc = grow(c, gw.mf, chunk * nb * sizeof(double)))) return rc;
     if ((rc = ensure_sed(c, chunk, 0))) return rc;
     a.gcol = (double *)w.cols.p; a.lwcol = a.gcol + (size_t)group * cells;
     a.part = (double *)w.part.p; a.part2 = a.part + ns * group * a.splits * kPartWords;
     a.state = (PwState *)w.state.p; a.sel = (mbbs::ColState *)w.sel.p;
     a.gstatus = (const int *)w.status.p;
-    Carve ob{(char *)w.outbuf.p};
-    a.o_nused = ob.take<long long>(tab);
-    a.o_lppd = ob.take<double>(tab); a.o_pwaic = ob.take<double>(tab); a.o_elpdwaic = ob.take<double>(tab);
-    a.o_elpdloo = ob.take<double>(tab); a.o_ploo = ob.take<double>(tab); a.o_khat = ob.take<double>(tab);
-    a.o_pit = ob.take<double>(tab);
-    a.o_tail = ob.take<int>(tab); a.o_status = ob.take<int>(tab);
     mbbq::FluxArgs fa;
     if ((rc = good_upload_bands(c, fa))) return rc;
     HIPCHK(hipMemsetAsync(w.status.p, 0, ns * sizeof(int), c->stream));
     for (int b0 = 0; b0 < nb; b0 += group) {
         a.b0 = b0; a.ng = std::min(group, nb - b0);
         // g of the group's bands, a chunk of rows at a time: one band-flux fill per group
-        for (size_t off = 0; off < cells; off += chunk) {
-            const int n = (int)std::min(chunk, cells - off);
-            if ((rc = launch_prologue(c, d_chain + off * 5, n, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
-            if ((rc = good_flux(c, fa, n))) return rc;
+        rc = for_row_chunks(c, d_chain, cells, c->wavenorm, [&](size_t off, int n) -> int {
+            if (const int rf = good_flux(c, fa, n)) return rf;
             GArgs ga;
             memset(&ga, 0, sizeof ga);
             ga.off = (long long)off; ga.rows_per_src = (long long)nw * nsteps;
             ga.b0 = b0; ga.ng = a.ng; ga.gcol = a.gcol; ga.cells = (long long)cells;
             ga.gstatus = b0 == 0 ? (int *)w.status.p : nullptr;
             ga.nw = nw; ga.nsteps = nsteps; ga.burn = sp->burn; ga.thin = sp->thin;
-            if ((rc = pw_g(c, fa, ga, n))) return rc;
-        }
+            return pw_g(c, fa, ga, n);
+        });
+        if (rc) return rc;
         const size_t ncid = ns * a.ng;
         const dim3 gcol((unsigned)ncid, (unsigned)a.splits);
         hipLaunchKernelGGL(k_pw_stat1, gcol, dim3(kThreads), 0, c->stream, a);
@@ -3502,26 +3519,14 @@ static int pw_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nstep
             s.ncol = std::min(kSelCols, a.ng - q * kSelCols);
             for (int k = 0; k < s.ncol; ++k) { s.col[k] = 5 + k; s.der[k] = a.lwcol + (size_t)(q * kSelCols + k) * cells; }
             s.state = a.sel + (size_t)q * ns * kSelCols;
-            s.hist = (unsigned int *)w.hist.p;
-            const dim3 gsel((unsigned)(ns * s.ncol), (unsigned)a.splits);
-            for (int pass = 0; pass < 8; ++pass) {
-                hipLaunchKernelGGL(mbbs::k_sum_hist, gsel, dim3(mbbs::kThreads), 0, c->stream, s, pass);
-                hipLaunchKernelGGL(mbbs::k_sum_pick, dim3((unsigned)(ns * s.ncol)), dim3(mbbs::kThreads), 0, c->stream, s);
-            }
+            s.hist = (unsigned int *)c->stat.hist.p;
+            launch_select(c, s, ns * s.ncol);
             HIPCHK(hipGetLastError());
         }
         hipLaunchKernelGGL(k_pw_tail, dim3((unsigned)ncid), dim3(kThreads), 0, c->stream, a);
         HIPCHK(hipGetLastError());
     }
-    std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    Carve hb{host.data()};
-    hb.put(o->n_used, tab);
-    hb.put(o->lppd, tab); hb.put(o->p_waic, tab); hb.put(o->elpd_waic, tab); hb.put(o->elpd_loo, tab);
-    hb.put(o->p_loo, tab); hb.put(o->khat, tab); hb.put(o->loo_pit, tab);
-    hb.put(o->tail_len, tab); hb.put(o->status, tab);
-    return MBB_OK;
+    return fetch_home(c, w.outbuf, rb);
 }
 
 extern "C" int mbb_chain_pointwise(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
@@ -3567,7 +3572,7 @@ static int map_check(const mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out
     if (!sp->start || !o->params || !o->lnprob || !o->chisq || !o->q || !o->cov || !o->niter || !o->nfev ||
         !o->start_index || !o->status)
         return fail(MBB_ERR_ARG, "null map argument");
-    if ((c->comm != nullptr && c->nranks > 1) || (c->x.connected && c->x.n > 1))
+    if (sharded_context(c))
         return fail(MBB_ERR_STATE, "a sharded context cannot run a map fit: every rank would repeat the whole search");
     if (sp->nsrc < 1) return fail(MBB_ERR_ARG, "a map fit needs a source at least");
     if (c->nb > mbbmap::kMaxBands) return fail(MBB_ERR_ARG, "more than 256 bands in a map fit");
@@ -3579,7 +3584,7 @@ static int map_check(const mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out
     if (sp->maxiter < 1 || sp->maxiter > MBB_MAP_MAX_ITER) return fail(MBB_ERR_ARG, "1 to 1000 iterations per map fit");
     if (!(sp->ftol >= 0.0 && sp->ftol <= 1.7976931348623157e308) || !(sp->xtol >= 0.0 && sp->xtol <= 1.7976931348623157e308))
         return fail(MBB_ERR_ARG, "ftol and xtol must be finite and not negative");
-    if ((size_t)sp->nsrc * sp->nstart > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    if ((rc = check_grid((size_t)sp->nsrc * sp->nstart))) return rc;
     const size_t nval = (size_t)sp->nsrc * sp->nstart * 5;
     for (size_t i = 0; i < nval; ++i)
         if (!(fabs(sp->start[i]) <= 1.7976931348623157e308)) {
@@ -3599,14 +3604,15 @@ extern "C" int mbb_map_fit(mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out
     const int nb = c->nb, nsrc = sp->nsrc, nstart = sp->nstart;
     const size_t n = (size_t)nsrc * nstart;
     mbb_ctx::MapWork &w = c->map;
-    const size_t out_bytes = n * (kOutDoubles * sizeof(double) + kOutInts * sizeof(int32_t));
+    MapArgs a;
+    memset(&a, 0, sizeof a);
+    ResultBlock rb;                              // (the host reads both in place from the image: nothing is scattered)
+    const size_t at_d = rb.add(&a.outd, n * kOutDoubles), at_i = rb.add(&a.outi, n * kOutInts);
     if ((rc = grow(c, w.start, n * 5 * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
     mbbq::FluxArgs fa;
     if ((rc = good_upload_bands(c, fa))) return rc;
     HIPCHK(hipMemcpyAsync(w.start.p, sp->start, n * 5 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    MapArgs a;
-    memset(&a, 0, sizeof a);
     a.start = (const double *)w.start.p; a.nstart = nstart; a.nsrc_data = c->nsrc;
     a.nu = fa.nu; a.lnnu = fa.lnnu; a.wt = fa.wt; a.band = fa.band; a.nb = nb; a.nsamples = fa.nsamples;
     a.flux = c->data.flux.d(); a.ivar = c->data.ivar.d();
@@ -3616,13 +3622,8 @@ extern "C" int mbb_map_fit(mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out
     for (int i = 0; i < 5; ++i) a.lowlim[i] = c->lowlim[i];
     for (int i = 0; i < 6; ++i) { a.uplim[i] = c->uplim[i]; a.gmean[i] = c->gmean[i]; a.givar[i] = c->givar[i]; }
     a.has_uplim = c->has_uplim; a.has_gprior = c->has_gprior;
-    // (mbblm::lm_fixed_mask: the caller's, lambda0 of an optically thin model, alpha of a model without one)
-    for (int i = 0; i < 5; ++i) if (sp->fixed[i]) a.fixed |= 1u << i;
-    if (c->opthin) a.fixed |= 1u << 2;
-    if (c->noalpha) a.fixed |= 1u << 3;
+    a.fixed = fixed_mask(c, sp->fixed);
     a.maxiter = sp->maxiter; a.ftol = sp->ftol; a.xtol = sp->xtol;
-    Carve ob{(char *)w.outbuf.p};
-    a.outd = ob.take<double>(n * kOutDoubles); a.outi = ob.take<int32_t>(n * kOutInts);
     const bool stage = fa.nmany > 0 && fa.nsamples <= kLdsSamples;
     const size_t lds = lds_doubles(nb, fa.nsamples, stage, c->has_cov != 0, a.cov_in_lds != 0) * sizeof(double);
     const int inst = model_of(c) * 2 + (stage ? 1 : 0);
@@ -3645,11 +3646,9 @@ extern "C" int mbb_map_fit(mbb_ctx *c, const mbb_map_spec *sp, const mbb_map_out
     });
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-    std::vector<char> host(out_bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const double *hd = (const double *)host.data();
-    const int32_t *hi = (const int32_t *)(host.data() + n * kOutDoubles * sizeof(double));
+    if ((rc = fetch_home(c, w.outbuf, rb))) return rc;
+    const double *hd = (const double *)(rb.image() + at_d);
+    const int32_t *hi = (const int32_t *)(rb.image() + at_i);
     // the final points of every (source, start) through the likelihood's own batch path: [nsrc][nstart][5] is its
     // multi-source layout, and the reported lnprob is what like(params) gives, bit for bit
     std::vector<double> pall(n * 5), lall(n);
@@ -3693,7 +3692,7 @@ static int ev_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_ev
     if (!sp || !o || !o->lnz || !o->lnz_err || !o->niter || !o->status || !o->n1 || !o->n2_inside || !o->prop_mean ||
         !o->prop_cov)
         return fail(MBB_ERR_ARG, "null evidence argument");
-    if ((c->comm != nullptr && c->nranks > 1) || (c->x.connected && c->x.n > 1))
+    if (sharded_context(c))
         return fail(MBB_ERR_STATE, "a sharded context cannot estimate an evidence: a rank holds only its own walkers' chain");
     if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
     int rc;
@@ -3708,7 +3707,7 @@ static int ev_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_ev
     if (!(sp->tol >= 0.0 && sp->tol <= 1.7976931348623157e308)) return fail(MBB_ERR_ARG, "tol must be finite and not negative");
     if (sp->maxiter < 1 || sp->maxiter > MBB_EV_MAX_ITER) return fail(MBB_ERR_ARG, "1 to 100000 iterations per evidence");
     if (sp->first_source < 0) return fail(MBB_ERR_ARG, "first_source must not be negative");
-    if ((size_t)nsrc > 0x7fffffffull / 64) return fail(MBB_ERR_ARG, "too many sources");
+    if ((rc = check_grid((size_t)nsrc))) return rc;
     if (sp->neff)
         for (int s = 0; s < nsrc; ++s)
             if (!(sp->neff[s] > 0.0 && sp->neff[s] <= 1.7976931348623157e308))
@@ -3732,17 +3731,17 @@ static int evidence_run(mbb_ctx *c, const double *d_chain, const double *d_lnpro
     a.nfit = a.nkept / 2; a.n1k = a.nkept - a.nfit;
     a.n1max = (long long)nw * a.n1k;
     a.n2 = sp->n2 ? sp->n2 : (int)a.n1max;
-    // (mbblm::lm_fixed_mask, a device function in this build: the caller's, lambda0 of a thin model, alpha without one)
-    for (int i = 0; i < 5; ++i) if (sp->fixed[i]) a.fixed |= 1u << i;
-    if (c->opthin) a.fixed |= 1u << 2;
-    if (c->noalpha) a.fixed |= 1u << 3;
+    a.fixed = fixed_mask(c, sp->fixed);
     a.first_source = sp->first_source; a.seed = sp->seed; a.tol = sp->tol; a.maxiter = sp->maxiter;
     const size_t ns = (size_t)nsrc, n1 = (size_t)a.n1max, n2 = (size_t)a.n2;
     // a slab: draws [k m, (k + 1) m) of every source, [nsrc][m][5] -- the likelihood's multi-source row grouping
     const size_t m = std::min<size_t>(n2, std::max<size_t>(1, (size_t)kSumChunkRows / ns));
     const size_t srows = ns * m;
     mbb_ctx::EvWork &w = c->ev;
-    const size_t out_bytes = ns * (2 * sizeof(long long) + 2 * sizeof(double) + sizeof(int));
+    ResultBlock rb;                              // 64-bit counts, doubles, 32-bit words
+    rb.add(&a.o_n1, ns, o->n1); rb.add(&a.o_inside, ns, o->n2_inside);
+    rb.add(&a.o_lnz, ns, o->lnz); rb.add(&a.o_err, ns, o->lnz_err);
+    rb.add(&a.o_niter, ns, o->niter);
     if ((rc = grow(c, w.mom, ns * kMomWords * sizeof(double)))) return rc;
     if ((rc = grow(c, w.ints, ns * 2 * sizeof(int)))) return rc;
     if ((rc = grow(c, w.slab, srows * (7 * sizeof(double) + sizeof(int32_t))))) return rc;
@@ -3750,7 +3749,7 @@ static int evidence_run(mbb_ctx *c, const double *d_chain, const double *d_lnpro
     if ((rc = grow(c, w.l2, ns * n2 * sizeof(double)))) return rc;
     if (o->post_lnq && (rc = grow(c, w.postq, ns * n1 * sizeof(double)))) return rc;
     if (sp->neff && (rc = grow(c, w.neff, ns * sizeof(double)))) return rc;
-    if ((rc = grow(c, w.outbuf, out_bytes))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
     a.mom = (double *)w.mom.p;
     a.free_ = (int *)w.ints.p; a.status = a.free_ + ns;
     a.l1 = (double *)w.l1.p; a.l2 = (double *)w.l2.p;
@@ -3760,10 +3759,6 @@ static int evidence_run(mbb_ctx *c, const double *d_chain, const double *d_lnpro
     double *const s_lnl = sb.take<double>(srows);
     int32_t *const s_status = sb.take<int32_t>(srows);
     a.s_lnl = s_lnl;
-    Carve ob{(char *)w.outbuf.p};
-    a.o_n1 = ob.take<long long>(ns); a.o_inside = ob.take<long long>(ns);
-    a.o_lnz = ob.take<double>(ns); a.o_err = ob.take<double>(ns);
-    a.o_niter = ob.take<int>(ns);
     if (sp->neff) {
         // (a pageable source: the copy has read it when it returns)
         HIPCHK(hipMemcpyAsync(w.neff.p, sp->neff, ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -3796,18 +3791,14 @@ static int evidence_run(mbb_ctx *c, const double *d_chain, const double *d_lnpro
     }
     hipLaunchKernelGGL(k_ev_bridge, dim3((unsigned)nsrc), dim3(kThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
-    std::vector<char> host(out_bytes);
     std::vector<double> mom(ns * kMomWords);
-    HIPCHK(hipMemcpyAsync(host.data(), w.outbuf.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = fetch_image(c, w.outbuf, rb))) return rc;
     HIPCHK(hipMemcpyAsync(mom.data(), w.mom.p, mom.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(o->status, a.status, ns * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (o->post_lnq)
         HIPCHK(hipMemcpyAsync(o->post_lnq, w.postq.p, ns * n1 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    Carve hb{host.data()};
-    hb.put((long long *)o->n1, ns); hb.put((long long *)o->n2_inside, ns);
-    hb.put(o->lnz, ns); hb.put(o->lnz_err, ns);
-    hb.put(o->niter, ns);
+    rb.scatter();
     for (size_t s = 0; s < ns; ++s) {
         memcpy(o->prop_mean + s * 5, &mom[s * kMomWords + kMomMean], 5 * sizeof(double));
         memcpy(o->prop_cov + s * 25, &mom[s * kMomWords + kMomCov], 25 * sizeof(double));

@@ -8,6 +8,10 @@
 #ifndef MBB_OWNED_H
 #define MBB_OWNED_H
 #include <stddef.h>
+#include <string.h>
+
+#include <type_traits>
+#include <vector>
 
 namespace mbbo {
 
@@ -82,6 +86,59 @@ template <typename T> struct Pin : PinBuf {
     using PinBuf::PinBuf;
     T *h() const { return static_cast<T *>(p); }
     T *dv() const { return static_cast<T *>(alias); }
+};
+
+// The result arrays of an analysis, one behind the other in one device block.  The analysis names each once --
+// add(&p, n, dst): n values of T that the kernels reach through p and the caller gets in dst -- and the block's size,
+// the device addresses and the way home all follow from that list.  An entry begins at a multiple of alignof(T), so a
+// list in falling alignment has no padding.  dst may be null (the array stays on the device), n may be 0 (p is null then,
+// nothing is copied), and add(&p, n, dst, first) sends home only the values from the first-th on: the ones before stay
+// on the device.  The addresses are handed out by place(), which first grows the device block to the list's size.
+class ResultBlock {
+    struct Entry {
+        void *slot;                              // the T * the kernels are given, written by set
+        void (*set)(void *slot, char *p);
+        size_t off, bytes, skip;                 // in the block; of which the first skip bytes do not go home
+        void *dst;
+    };
+    std::vector<Entry> e_;
+    std::vector<char> image_;
+    size_t bytes_ = 0;
+public:
+    // ... returns where the entry begins in the block
+    // (U: the caller's name for T's values where the two differ, int64_t for long long)
+    template <typename T, typename U = T> size_t add(T **p, size_t n, U *dst = nullptr, size_t first = 0)
+    {
+        static_assert(sizeof(U) == sizeof(T) && std::is_integral<U>::value == std::is_integral<T>::value &&
+                      std::is_signed<U>::value == std::is_signed<T>::value, "a destination holds what the kernels write");
+        bytes_ = (bytes_ + alignof(T) - 1) / alignof(T) * alignof(T);
+        e_.push_back(Entry{p, [](void *slot, char *at) { *static_cast<T **>(slot) = reinterpret_cast<T *>(at); }, bytes_,
+                           n * sizeof(T), (first < n ? first : n) * sizeof(T), dst});
+        bytes_ += n * sizeof(T);
+        return e_.back().off;
+    }
+    size_t bytes() const { return bytes_; }
+    template <typename Idle> int place(DevBuf &block, Idle &&idle)
+    {
+        if (const int rc = block.grow(bytes_, idle)) return rc;
+        for (const Entry &e : e_) e.set(e.slot, e.bytes ? static_cast<char *>(block.p) + e.off : nullptr);
+        return 0;
+    }
+    // Home as an image: the caller copies bytes() of the device block to image(), waits, and scatter() fills every dst.
+    char *image() { image_.resize(bytes_); return image_.data(); }
+    void scatter() const
+    {
+        (void)each([this](void *dst, size_t off, size_t bytes) { memcpy(dst, image_.data() + off, bytes); return 0; });
+    }
+    // Home entry by entry: copy(dst, block offset, bytes) for every entry with a dst and a value to send, in the list's
+    // order; stops at the first status that is not 0 and returns it.
+    template <typename Copy> int each(Copy &&copy) const
+    {
+        for (const Entry &e : e_)
+            if (e.dst && e.bytes > e.skip)
+                if (const int rc = copy(e.dst, e.off + e.skip, e.bytes - e.skip)) return rc;
+        return 0;
+    }
 };
 
 // The memory of a device-resident sampler (mbb_sampler_state, mbb_hip.hip)

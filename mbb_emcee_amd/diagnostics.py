@@ -58,11 +58,7 @@ class _Raw(object):
         self.acf = np.empty((nsrc, 5, nacf)) if nacf else None
 
     def out(self):
-        o = _native.DiagOut()
-        o.tau, o.ess, o.rhat = _native._d(self.tau), _native._d(self.ess), _native._d(self.rhat)
-        o.window, o.status = _native._i(self.window), _native._i(self.status)
-        o.acf = _native._d(self.acf) if self.acf is not None else None
-        return o
+        return _analysis.bind_out(_native.DiagOut, vars(self))          # (acf: None, and a null field, when not asked for)
 
 
 class ChainDiagnostics(object):

@@ -73,13 +73,7 @@ class _Raw(object):
         self.status = np.zeros((nsrc, _native.SUMMARY_COLS), dtype=np.int32)
 
     def out(self):
-        o = _native.DrawsOut()
-        o.rows, o.lnprob, o.index, o.status = (_native._d(self.rows), _native._d(self.lnprob), _native._i(self.index),
-                                               _native._i(self.status))
-        for k, d in enumerate(_DERIVED_ORDER):
-            if d in self.derived:
-                o.derived[k] = _native._d(self.derived[d])
-        return o
+        return _analysis.bind_out(_native.DrawsOut, dict(vars(self), derived=[self.derived.get(d) for d in _DERIVED_ORDER]))
 
 
 class ChainDraws(_analysis.Result):

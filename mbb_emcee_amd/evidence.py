@@ -159,14 +159,8 @@ class _Raw(object):
         self.post_lnq = np.full((nsrc, n1), np.nan) if keep else None
 
     def out(self):
-        o = _native.EvidenceOut()
-        d, i = _native._d, _native._i
-        o.lnz, o.lnz_err, o.niter, o.status = d(self.lnz), d(self.lnz_err), i(self.niter), i(self.status)
-        o.n1, o.n2_inside = self.n1.ctypes.data_as(_native._lp), self.n_inside.ctypes.data_as(_native._lp)
-        o.prop_mean, o.prop_cov = d(self.prop_mean), d(self.prop_cov)
-        if self.prop is not None:
-            o.prop, o.prop_lnprob, o.prop_lnq, o.post_lnq = d(self.prop), d(self.prop_lnprob), d(self.prop_lnq), d(self.post_lnq)
-        return o
+        # (the draws and their terms: None, and null fields, unless kept)
+        return _analysis.bind_out(_native.EvidenceOut, dict(vars(self), n2_inside=self.n_inside))
 
 
 def chain_evidence(like, chain, lnprob, n2=None, fixed=None, neff="auto", seed=DEFAULT_SEED, burn=0, thin=1, tol=TOL,

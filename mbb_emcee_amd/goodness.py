@@ -64,14 +64,7 @@ class _Raw(object):
         self.best_index = np.full((nsrc, 2), -1, dtype=np.int32)
 
     def out(self):
-        o = _native.GoodnessOut()
-        o.n_used = self.n_used.ctypes.data_as(_native._lp)
-        o.mean, o.min, o.max, o.pct = _native._d(self.mean), _native._d(self.min), _native._d(self.max), _native._d(self.pct)
-        o.status = _native._i(self.status)
-        o.at_mean, o.ml, o.ml_model, o.best = (_native._d(self.at_mean), _native._d(self.ml), _native._d(self.ml_model),
-                                               _native._d(self.best))
-        o.ml_index, o.best_index = _native._i(self.ml_index), _native._i(self.best_index)
-        return o
+        return _analysis.bind_out(_native.GoodnessOut, vars(self))
 
 
 def goodness_rows(like, pars, want_flux=False):

@@ -65,12 +65,7 @@ class _Raw(object):
             setattr(self, name, np.full((nsrc, ndata), np.nan))
 
     def out(self):
-        o = _native.PointwiseOut()
-        o.n_used = self.n_used.ctypes.data_as(_native._lp)
-        o.tail_len, o.status = _native._i(self.tail_len), _native._i(self.status)
-        for name in _TABLES:
-            setattr(o, name, _native._d(getattr(self, name)))
-        return o
+        return _analysis.bind_out(_native.PointwiseOut, vars(self))
 
 
 def loo_rows(like, pars):

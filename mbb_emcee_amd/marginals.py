@@ -103,15 +103,7 @@ class _Raw(object):
         self.status = np.zeros((nsrc, nc), dtype=np.int32)
 
     def out(self):
-        o = _native.MarginalsOut()
-        u32 = lambda a: a.ctypes.data_as(_native._up)
-        i64 = lambda a: a.ctypes.data_as(_native._lp)
-        o.counts1, o.edges1, o.counts2, o.edges2 = (u32(self.counts1), _native._d(self.edges1), u32(self.counts2),
-                                                    _native._d(self.edges2))
-        o.n_used, o.n_below, o.n_above, o.n_nonfinite = (i64(self.n_used), i64(self.n_below), i64(self.n_above),
-                                                         i64(self.n_nonfinite))
-        o.status = _native._i(self.status)
-        return o
+        return _analysis.bind_out(_native.MarginalsOut, vars(self))
 
 
 RAW_FIELDS = ("counts1", "edges1", "counts2", "edges2", "n_used", "n_below", "n_above", "n_nonfinite", "status")

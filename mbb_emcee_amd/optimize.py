@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native
+from . import _analysis, _native
 
 __all__ = ["map_fit", "MapFit"]
 
@@ -120,13 +120,7 @@ class _Raw(object):
         self.status_all = np.zeros((nsrc, nstart), dtype=np.int32)
 
     def out(self):
-        o = _native.MapOut()
-        d, i = _native._d, _native._i
-        o.params, o.lnprob, o.chisq, o.q, o.model_flux, o.cov = (d(self.params), d(self.lnprob), d(self.chisq), d(self.q),
-                                                                 d(self.model_flux), d(self.cov))
-        o.niter, o.nfev, o.start_index, o.status = i(self.niter), i(self.nfev), i(self.start_index), i(self.status)
-        o.lnprob_all, o.params_all, o.status_all = d(self.lnprob_all), d(self.params_all), i(self.status_all)
-        return o
+        return _analysis.bind_out(_native.MapOut, vars(self))
 
 
 def map_fit(like, start, nstart=None, fixed=None, maxiter=MAXITER, ftol=FTOL, xtol=XTOL, rng=None, squeeze=False):

@@ -146,12 +146,7 @@ class _Raw(object):
         self.status = np.zeros((nsrc, nspec), dtype=np.int32)
 
     def out(self):
-        o = _native.PredictOut()
-        o.n_used = self.n_used.ctypes.data_as(_native._lp)
-        o.mean, o.min, o.max, o.pct = (_native._d(self.mean), _native._d(self.min), _native._d(self.max),
-                                       _native._d(self.pct))
-        o.status = _native._i(self.status)
-        return o
+        return _analysis.bind_out(_native.PredictOut, vars(self))
 
 
 def _predict_host(like, c4, req):

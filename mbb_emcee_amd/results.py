@@ -158,13 +158,7 @@ class _Raw(object):
         self.best_index = np.zeros((nsrc, 2), dtype=np.int32)
 
     def out(self):
-        o = _native.SummaryOut()
-        o.n_used = self.n_used.ctypes.data_as(C.POINTER(C.c_int64))
-        o.mean, o.min, o.max, o.pct = (_native._d(self.mean), _native._d(self.min), _native._d(self.max),
-                                       _native._d(self.pct))
-        o.status, o.cov, o.best, o.best_index = (_native._i(self.status), _native._d(self.cov), _native._d(self.best),
-                                                 _native._i(self.best_index))
-        return o
+        return _analysis.bind_out(_native.SummaryOut, vars(self))
 
 
 def _summarise_host(like, chain, lnprob, req):

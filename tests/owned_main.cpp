@@ -3,11 +3,13 @@
 // Built by tests/test_host_cpu.py with AddressSanitizer (leak detection on) and UBSan and run directly.  The four runtime
 // functions the header declares are defined here with counters of live blocks and a switch that makes the n-th allocation
 // from now fail; what mbb_hip.hip builds on -- grow, a failed allocation, destruction, a struct of owners, a sampler's
-// state held by a unique_ptr -- is checked against them.  Exit status 0: all held.
+// state held by a unique_ptr, the result list of an analysis -- is checked against them.  Exit status 0: all held.
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <memory>
+#include <vector>
 
 #include "../mbb_emcee_amd/csrc/mbb_owned.h"
 
@@ -173,6 +175,115 @@ static void check_sampler_state()
     }
 }
 
+// A caller's array of n values with a guard of kGuard values on either side: ok() when the guards are untouched and the
+// values are the n * sizeof(T) bytes at src (or untouched too, with a null src)
+constexpr size_t kGuard = 4;
+template <typename T> struct Guarded {
+    std::vector<T> v;
+    size_t n;
+    explicit Guarded(size_t n_) : v(n_ + 2 * kGuard), n(n_) { memset(v.data(), 0xA5, v.size() * sizeof(T)); }
+    T *dst() { return v.data() + kGuard; }
+    bool ok(const void *src) const
+    {
+        const unsigned char *b = reinterpret_cast<const unsigned char *>(v.data());
+        for (size_t i = 0; i < v.size() * sizeof(T); ++i) {
+            const bool inside = i >= kGuard * sizeof(T) && i < (kGuard + n) * sizeof(T);
+            const unsigned char want = inside && src ? static_cast<const unsigned char *>(src)[i - kGuard * sizeof(T)] : 0xA5;
+            if (b[i] != want) return false;
+        }
+        return true;
+    }
+};
+
+// The result list of an analysis (ResultBlock): sizes, offsets and padding; what place() hands out and when; both ways
+// home over a malloc'd "device" block filled with a pattern
+static void check_result_block()
+{
+    auto idle = [] { return 0; };
+    {   // falling alignment: the plain sum, no padding
+        ResultBlock rb;
+        long long *p64; double *pd; int *pi;
+        CHECK(rb.add(&p64, 3) == 0 && rb.add(&pd, 5) == 24 && rb.add(&pi, 7) == 64);
+        CHECK(rb.bytes() == 3 * sizeof(long long) + 5 * sizeof(double) + 7 * sizeof(int) && rb.bytes() == 92);
+    }
+    {   // an int first: the double behind it is padded to 8, and the size says so
+        ResultBlock rb;
+        long long *p64; double *pd; int *pi;
+        CHECK(rb.add(&pi, 7) == 0 && rb.add(&pd, 5) == 32 && rb.add(&p64, 3) == 72 && rb.bytes() == 96);
+    }
+    // the list of an analysis: a destined array, an empty one, device-only scratch, two arrays of one type side by side,
+    // one array of which only the second half goes home, a 64-bit destination under the caller's name for it, 32-bit words
+    long long *d_count; double *d_a, *d_empty, *d_scratch, *d_b, *d_pair; int *d_w; unsigned int *d_u;
+    Guarded<int64_t> h_count(3);
+    Guarded<double> h_a(4), h_empty(0), h_b(1), h_pair(5);
+    Guarded<int> h_w(3);
+    Guarded<unsigned int> h_u(2);
+    ResultBlock rb;
+    const size_t at_count = rb.add(&d_count, 3, h_count.dst());
+    const size_t at_a = rb.add(&d_a, 4, h_a.dst());
+    const size_t at_empty = rb.add(&d_empty, 0, h_empty.dst());
+    const size_t at_scratch = rb.add(&d_scratch, 2);
+    const size_t at_b = rb.add(&d_b, 1, h_b.dst());
+    const size_t at_pair = rb.add(&d_pair, 10, h_pair.dst(), 5);
+    const size_t at_pair2 = at_pair + 5 * sizeof(double);                          // (where what goes home begins)
+    const size_t at_w = rb.add(&d_w, 3, h_w.dst());
+    const size_t at_u = rb.add(&d_u, 2, h_u.dst());
+    CHECK(at_count == 0 && at_a == 24 && at_empty == 56 && at_scratch == 56 && at_b == 72 && at_pair == 80 &&
+          at_w == 160 && at_u == 172 && rb.bytes() == 180);
+    CHECK(at_b == at_scratch + 2 * sizeof(double) && at_pair == at_b + sizeof(double));   // one type side by side: contiguous
+    // place(): the block is grown first (idle() before a block in use is released), then the addresses are the new block's
+    DevBuf block;
+    CHECK(block.grow(16, idle) == 0);
+    void *const small = block.p;
+    int idles = 0;
+    void *p_at_idle = nullptr;
+    CHECK(rb.place(block, [&] { ++idles; p_at_idle = block.p; return 0; }) == 0);
+    CHECK(idles == 1 && p_at_idle == small && block.cap == rb.bytes());
+    char *const base = static_cast<char *>(block.p);
+    CHECK((char *)d_count == base && (char *)d_a == base + at_a && (char *)d_scratch == base + at_scratch &&
+          (char *)d_b == base + at_b && (char *)d_pair == base + at_pair && (char *)d_w == base + at_w && (char *)d_u == base + at_u);
+    CHECK(d_empty == nullptr);                                                     // an empty array has no address
+    CHECK(rb.place(block, [&] { ++idles; return 0; }) == 0 && idles == 1 && (char *)d_u == base + at_u);   // big enough: as it is
+    {   // a block that cannot be grown: the status comes back and nothing is handed out
+        ResultBlock big;
+        double *q = nullptr;
+        big.add(&q, 1000);
+        DevBuf none;
+        g_fail_in = 1;
+        CHECK(big.place(none, idle) == -3 && q == nullptr && none.p == nullptr);
+        CHECK(big.place(none, [] { return -7; }) == -7 && q == nullptr && none.p == nullptr);   // ... nor when idle() fails
+        CHECK(big.place(none, idle) == 0 && q != nullptr && q == none.p);
+    }
+    for (size_t i = 0; i < rb.bytes(); ++i) base[i] = (char)(i * 7 + 1);
+    // home entry by entry: exactly the destined arrays that hold something, in the list's order
+    struct Visit { void *dst; size_t off, bytes; };
+    std::vector<Visit> seen;
+    CHECK(rb.each([&](void *dst, size_t off, size_t bytes) { seen.push_back(Visit{dst, off, bytes}); return 0; }) == 0);
+    const Visit want[] = {{h_count.dst(), at_count, 24}, {h_a.dst(), at_a, 32}, {h_b.dst(), at_b, 8},
+                          {h_pair.dst(), at_pair2, 40}, {h_w.dst(), at_w, 12}, {h_u.dst(), at_u, 8}};
+    CHECK(seen.size() == 6);
+    for (size_t i = 0; i < 6; ++i) CHECK(seen[i].dst == want[i].dst && seen[i].off == want[i].off && seen[i].bytes == want[i].bytes);
+    // ... a copy that fails ends the walk with its status
+    int calls = 0;
+    CHECK(rb.each([&](void *, size_t, size_t) { return ++calls == 2 ? -5 : 0; }) == -5 && calls == 2);
+    CHECK(h_count.ok(nullptr) && h_a.ok(nullptr) && h_b.ok(nullptr) && h_pair.ok(nullptr) && h_w.ok(nullptr) && h_u.ok(nullptr));
+    // home as an image: every destination gets its own slice, nothing else is written
+    {   // an entry whose first value to go home is beyond its last sends nothing
+        ResultBlock none;
+        double *q;
+        Guarded<double> h(3);
+        none.add(&q, 3, h.dst(), 3);
+        none.add(&q, 2, h.dst(), 7);
+        CHECK(none.bytes() == 40 && none.each([](void *, size_t, size_t) { return -1; }) == 0);
+    }
+    char *const image = rb.image();
+    memcpy(image, base, rb.bytes());                                               // (the caller's one copy of the block)
+    CHECK(rb.image() == image);
+    rb.scatter();
+    CHECK(h_count.ok(base + at_count) && h_a.ok(base + at_a) && h_empty.ok(nullptr) && h_b.ok(base + at_b) && h_pair.ok(base + at_pair2) &&
+          h_w.ok(base + at_w) && h_u.ok(base + at_u));
+}
+
 int main()
 {
     check_grow<DevBuf>(g_live_dev);
@@ -180,6 +291,7 @@ int main()
     check_pinned_alias();
     check_group();
     check_sampler_state();
+    check_result_block();
     CHECK(g_live_dev == 0 && g_live_pin == 0 && g_allocs == g_frees);
     printf("OWNED_OK %d checks\n", g_checks);
     return 0;

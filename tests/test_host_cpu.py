@@ -781,7 +781,9 @@ def test_owners_under_sanitizers(tmp_path):
     """The owners of every device and pinned allocation of the host library (mbb_emcee_amd/csrc/mbb_owned.h) over
     malloc / free: tests/owned_main.cpp, a program of its own built with AddressSanitizer (leaks included) and UBSan
     and run directly -- grow within and beyond capacity, a failed allocation, destruction, a struct of owners whose
-    allocations stop midway, a sampler's state held by a unique_ptr whose second allocation fails."""
+    allocations stop midway, a sampler's state held by a unique_ptr whose second allocation fails; and the result list
+    of an analysis (ResultBlock): sizes, offsets and padding, empty and device-only entries, an array half of which goes home,
+    addresses only from a grown block, both ways home against guarded destinations."""
     import shutil
     gxx = shutil.which("g++")
     if not gxx:

@@ -4,7 +4,8 @@ Every device and pinned block of a context or a sampler is an owner that is rema
 (mbb_emcee_amd/csrc/mbb_owned.h).  What a call computes must not depend on what the context's buffers went through
 before it: here one context is driven over every growth seam -- boundary blocks, model fluxes, SED scratch, SED
 outputs, the chain store, the analyses' work buffers, a second sampler -- and every array that comes back is compared,
-bit for bit, with the same call on a context that has done nothing else."""
+bit for bit, with the same call on a context that has done nothing else.  The analyses that reduce columns share one
+set of work buffers (StatWork, mbb_hip.hip): a second test runs them one after the other over one resident chain."""
 import ctypes as C
 
 import numpy as np
@@ -195,3 +196,112 @@ def test_one_context_across_every_growth_seam_equals_fresh_contexts(mbb):
     for life in (1, 2):
         differ = [k for k in sorted(lives[0]) if lives[life][k].tobytes() != lives[0][k].tobytes()]
         assert not differ, (life, differ)
+
+
+# ---- the analyses that share the column-statistics buffers, one after the other on one context
+BANDS3 = ["A_delta_100um", "SPIRE_250um", "B_delta_850um"]        # one sample, a passband of many, one sample
+QS3 = [15.85, 50.0, 84.15]
+NSTEPS = 48
+
+
+def _analysis_calls(like, ctx, h):
+    """name -> a call that runs one analysis of the chain resident with sampler h and returns the arrays the library
+    filled, in the order the shared buffers are to go through them."""
+    from mbb_emcee_amd import _native, evidence, goodness, loo, predict, results
+
+    def analyse(entry, req, raw):
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(getattr(ctx.lib, "mbb_sampler_" + entry)(ctx.h, h, C.byref(spec), C.byref(out)), ctx)
+        return _raw_arrays(raw)
+
+    def summary(**kw):
+        def call():
+            req = results._Request(QS3, **kw)
+            raw = results._Raw(1, len(req.qs))
+            spec, out = req.spec(), raw.out()
+            _native.check_arg(ctx.lib.mbb_sampler_run_summary(ctx.h, h, 0, 2.0, C.byref(spec), C.byref(out), None, None, None,
+                                                              None, None), ctx)
+            return _raw_arrays(raw)
+        return call
+
+    def predicted(specs):
+        def call():
+            req = predict._Request(like, specs, QS3)
+            return analyse("predict", req, predict._Raw(1, len(req.keys), len(req.qs)))
+        return call
+
+    def good():
+        req = goodness._Request(like, QS3)
+        return analyse("goodness", req, goodness._Raw(1, req.ndata, len(req.qs)))
+
+    def pointwise():
+        req = loo._Request(like)
+        return analyse("pointwise", req, loo._Raw(1, req.ndata))
+
+    def bridged():
+        req = evidence._Request(like, 64, seed=SEED)
+        nkept, nfit = req.check_steps(NSTEPS)
+        req.set_neff(None, 1)
+        return analyse("evidence", req, evidence._Raw(1, NW * (nkept - nfit), 64, False))
+
+    return [
+        ("summary_a", summary()),
+        ("predict3", predicted([70.0, "SPIRE_250um", 500.0])),
+        ("goodness_a", good),
+        ("loo", pointwise),
+        ("summary_derived", summary(derived=("peaklambda", "lir", "dustmass"), redshift=1.0, lumdist_mpc=6000.0)),
+        ("goodness_b", good),
+        # (more specs than mbbp::kGroup = 3: two groups, the shared buffers reused within one call)
+        ("predict5", predicted([70.0, "SPIRE_250um", 500.0, "B_delta_850um", 1100.0])),
+        ("evidence", bridged),
+        ("summary_b", summary()),
+    ]
+
+
+def test_analyses_sharing_work_buffers_equal_fresh_contexts(mbb):
+    """Summary, predictions, goodness of fit, WAIC / PSIS-LOO and evidence of one resident chain (8 walkers x 48 steps;
+    3 bands, one of them a passband of many samples), in an order that takes the shared column-statistics buffers from
+    every analysis to every other: each array of each result is the same bytes (NaNs by bit pattern) as from the same
+    call on a context that has run the chain and nothing else, and the first and the last summary are the same bytes."""
+    import bench
+    from mbb_emcee_amd import _native
+    helper = mbb.likelihood(response=True)
+    helper.set_phot(BANDS3, np.ones(3), np.ones(3))
+    flux = helper.model_flux(bench.TRUTH)[0]
+    helper.context.close()
+    p0 = np.ascontiguousarray(bench.walkers(1)[:NW])
+
+    def make():
+        like = mbb.likelihood(response=True)
+        like.set_phot(BANDS3, flux, 0.1 * flux + 1.0)
+        ctx = like._sync_device()
+        h = _sampler(ctx)
+        return like, ctx, h, _run(ctx, h, p0, NSTEPS)["chain"]
+
+    def close(ctx, h):
+        _native._check(ctx.lib.mbb_sampler_destroy(ctx.h, h))
+        ctx.close()
+
+    like, ctx, h, chain = make()
+    calls = _analysis_calls(like, ctx, h)
+    names = [name for name, _ in calls]
+    got = {name: call() for name, call in calls}
+    close(ctx, h)
+    assert all(arrays and all(v.size for v in arrays.values()) for arrays in got.values())
+    assert sum(len(arrays) for arrays in got.values()) >= 70
+
+    def differing(a, b):
+        assert sorted(a) == sorted(b)
+        return [k for k in sorted(a) if a[k].dtype != b[k].dtype or a[k].shape != b[k].shape or a[k].tobytes() != b[k].tobytes()]
+
+    for name in names:
+        like, ctx, h, again = make()
+        assert again.tobytes() == chain.tobytes()                        # the same chain: the runs are seeded
+        fresh = dict(_analysis_calls(like, ctx, h))[name]()
+        close(ctx, h)
+        assert not differing(got[name], fresh), (name, differing(got[name], fresh))
+    assert not differing(got["summary_a"], got["summary_b"])
+    assert not differing(got["goodness_a"], got["goodness_b"])
+    # (the calls did something: every summary saw all the samples, the predictions of one spec agree across the calls)
+    assert np.all(got["summary_a"]["n_used"][:, :5] == NW * NSTEPS)
+    assert got["predict5"]["mean"][0, :3].tobytes() == got["predict3"]["mean"].tobytes()

@@ -6,7 +6,7 @@
   (b) run_mcmc(storechain=False, summary=..., marginals=...).
 
 Two table sets -- "1d": five 1-D tables of 64 bins; "2d": those and the ten 32 x 32 pairs --, in one process, warmed
-up, alternated, nine times each; walls with their spread and the bytes each way brings back, as one JSON object
+up, alternated, nine times each (`--runs N`: N times); walls with their spread and the bytes each way brings back, as one JSON object
 (profiles/r16/marginals.json).  Both ways bin the same chain (same seed) and the counts are compared.  `--single`
 measures the single-source 250 x 250 case the same way; `--only-device` runs (b) twice per set after a warm-up, for a
 kernel trace of its own (rocprofv3 --kernel-trace --stats -- python tools/bench_marginals.py --only-device)."""
@@ -77,15 +77,16 @@ def main():
                                                           "n_above", "n_nonfinite", "status"))
         return t2 - t0, t1 - t0, t2 - t1, (m._raw.counts1[:, :5], m._raw.counts2), nbytes
 
+    runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else RUNS
     if "--only-device" in sys.argv:
         for kw in SETS.values():
             way_b(kw); way_b(kw)
         return
-    out = {"shape": {"sources": ns, "walkers": nw, "steps": nsteps, "bands": 8}, "host_threads": THREADS, "runs": RUNS}
+    out = {"shape": {"sources": ns, "walkers": nw, "steps": nsteps, "bands": 8}, "host_threads": THREADS, "runs": runs}
     for name, kw in SETS.items():
         way_b(kw); way_a(kw)                                     # warm-up of both
         a, b = [], []
-        for _ in range(RUNS):
+        for _ in range(runs):
             ra = way_a(kw); rb = way_b(kw)
             a.append(ra[:3]); b.append(rb[:3])
         same = bool(np.array_equal(ra[3][0], rb[3][0]) and (not kw["bins2d"] or np.array_equal(ra[3][1], rb[3][1])))
