@@ -711,71 +711,168 @@ int mbb_event_record(mbb_ctx *ctx, void *ev);
 int mbb_event_elapsed_ms(mbb_ctx *ctx, void *start, void *stop, float *ms);
 int mbb_event_destroy(mbb_ctx *ctx, void *ev);
 
-/* Tunables: "walkers_per_group" (0 = auto), "block_threads" (0 = auto),
- * "zero_copy" (host path reads/writes pinned host memory from the kernel),
- * "spin_wait" (how mbb_lnlike_batch waits: 0 blocks on the stream, 1 polls it,
- * 2 -- the default -- watches the result slots in pinned memory, which are final
- * before the kernel's completion signal is; "spin_budget" = polls before it falls back
- * to blocking on the stream, 0 forces the fallback), "bar_params" (host path writes the
- * parameter rows into device memory through the PCIe BAR), "serve" (default 1: after "serve_after" (3) boundary calls in a row
- * with nothing else in between -- a sampler's loop -- mbb_lnlike_call hands its rows to a kernel that STAYS on the GPU
- * between the calls and is rung through the BAR (k_serve: no launch per call; same results bit for bit), while a batch
- * is at most two rows per CU (a workgroup of the kernel takes a row; a call of more rows than it has workgroups, two).  One such kernel per device and process: any other entry point on the context, and any entry
- * point of ANOTHER context of the process that comes to the device (which also ends this context's run of calls, and
- * doubles, up to 64, the calls in a row it needs before its next server -- back to "serve_after" once a server has
- * answered 256 requests: likelihoods used in turns do not spend their time starting and stopping kernels), tells it to
- * leave first; it leaves by itself "serve_idle_us" (1000) after the last request; a request
- * whose results do not appear within "serve_budget_us" (400) is evaluated by a launch instead and three such in a row
- * rest the feature for the next 4096 boundary calls (mbb_get_info "serve_rests": how often, "serve_resting": calls left).  A server holds a CU per workgroup, and nothing of another PROCESS fits on those (emcee's pool,
- * mbb_fit.py:80-81 with threads > 1): so it is as wide as the calls have rows (in eights; "serve_grid" > 0: that many
- * workgroups; mbb_get_info "serve_grid": the resident one's) and no wider than this process's share of the device -- the CUs
- * divided (in whole rows of the 8 XCDs) by the processes of this library that are making boundary calls on it right now (a table in POSIX shared memory
- * keyed by the device's PCI address, each process noting its calls: csrc/mbb_registry.h; mbb_get_info "device_peers": registered, "device_busy": calling).  Two
- * workers of 125 rows have their servers side by side; a server narrower than a call has rows takes two rows a workgroup
- * (three workers: 80 CUs each); a call of more than twice the share's rows goes by a launch
- * ("serve_peer_yields"); a server too wide for the share or too narrow for the call leaves and the next starts with the same
- * call ("serve_resizes").  For processes that table cannot show, a server is sent away after "serve_lease_us" (50000;
- * 0: never) in one go -- the rows of that call go by a launch, the next server starts after the next few calls in a row
- * ("serve_lease_yields").
- * "serve" 0: a launch per call; 2: the whole device is this process's share whoever else is there (tests).  "serve_prefetch" (32; 0 to
- * 256): once a request's first record has turned the host asks for that many record lines ahead of its scan.  "prepass" (-1 auto: from
- * 64 rows per CU; 0 never; 1 always): a likelihood launch of given rows is preceded by k_walker_pre, which works out gate, SED
- * constructor and penalties with a LANE per row (k_lnlike: a row of 16 lanes per walker -- right where a constructor is
- * latency, a quarter of all instructions where a launch is bound by their number); same values bit for bit
- * (mbb_get_info "last_prepass").  "serve_overlap" (default 1): that
- * kernel starts a row's passband quadrature beside its SED constructor -- the blackbody-side value of every sample,
- * which needs none of the constructor's merge point, into a buffer in LDS -- and sums the units from the buffer when
- * the constructor is through, when the bands have at least 12 chunks of 64 samples (2: with fewer too); 0: one after
- * the other, as a launch does it; the same results either way.
- * mbb_get_info "serving", "serve_requests", "serve_fallbacks"), "seg_chunks", "pack_tails" (band
- * leftovers share chunks; takes effect at the next mbb_set_bands), "stage_tables",
- * "virtual_ranks", "debug", "roof_threads" / "roof_wgs_per_cu" (measurement only: the geometry of
- * mbb_roof_probe), "xchg_spin_max" (polls before a launch waiting for a peer
- * gives up); the forms of the single-GPU sampler, same chains bit for bit (which one a run takes by default, and
- * what each costs: plan_sampler_run in mbb_hip.hip, profiles/r04/walker_sweep.txt):
- * "lookahead_sampler" (default 1; 0: the plain train of one launch per half-step),
- * "flow_sampler" (default 1: one launch per 4096 steps, every workgroup resident, rows handed over through check
- * words instead of a launch boundary; 0: the plain train as well),
- * "flow_min_steps" (runs shorter than this take the plain train: a one-launch run costs ~14 us
- * beside its steps; default from profiles/r03/flowm_short_runs.txt),
- * "merged_flow_sampler" (default 1: ensembles of up to two walkers per CU take "form 7", k_flowm -- one workgroup per
- * pair of walkers and candidate; the passband quadrature of both proposals a walker can end up making, and the SED
- * constructor for every outcome still open, run ahead of the decisions they depend on; 0: those ensembles take the
- * resident forms below too),
- * "resident_sampler" (default 1: ensembles beyond that run as ONE launch per 4096 steps as well, a workgroup owning
- * W = ceil(half / CUs) walkers of each half, up to 8; 0: off, the plain train; 2: every eligible ensemble takes it),
- * that run -- "form 9", k_flowa -- constructs every walker's proposal a half-step ahead, for both outcomes of its partner's
- * pending move, beside the quadrature of the half-step before,
- * "resident_walkers" (walkers per workgroup and half of the resident forms; 0 = the host's choice),
- * "sharded_flow_sampler" (default 1: a sharded run with the
- * one-hop exchange is one launch per 4096 steps on every rank too; 0: one launch per half-step),
- * "flow_spin_log2" (0 = 22: log2 of the polls before a wait -- 63: no polls, the first miss, for tests --
- * inside the one-launch run gives up; mbb_sampler_run then redoes the run as a launch train and
- * counts it in mbb_get_info "flow_fallbacks"; the next run takes the one-launch form again, and only
- * three give-ups in a row rest it for the next 16 runs -- mbb_get_info "flow_resting" says how many of
- * those are left.  mbb_sampler_advance_async keeps nothing to redo a run from: there a give-up surfaces
- * at the next mbb_sampler_run as MBB_ERR_STATE and the sampler wants mbb_sampler_set_state again).
- * mbb_get_info "last_kernel_form" says which form ran. */
+/* ---- tunables and counters of a context ---------------------------------- */
+/* Options (mbb_set_option).  A value beyond its range is set to the nearer end, never refused; a name that is not here is
+ * MBB_ERR_ARG.  Setting any option sends a resident server (below) away first.  The table in code, which
+ * tests/test_host_cpu.py holds this one to: csrc/mbb_options.h.
+ *
+ *   name                    default   range         meaning
+ *   "walkers_per_group"     0         any           walkers per workgroup of a likelihood launch; 0 = auto
+ *   "block_threads"         0         any           threads per workgroup of a likelihood launch; 0 = auto
+ *   "zero_copy"             1         any           host path: the kernel reads and writes pinned host memory
+ *   "seg_chunks"            4         any           most chunks of 64 samples to a band segment; from the next mbb_set_bands
+ *   "debug"                 0         any           a row's status carries the walker's pad bits too
+ *   "stage_tables"          -1        any           band tables staged in LDS: -1 auto, 0 never, 1 whenever they fit
+ *   "spin_wait"             2         any           how mbb_lnlike_batch waits (Waiting): 0 blocks, 1 polls the stream, 2 watches
+ *   "spin_budget"           20000000  >= 0          polls of the watch before it blocks on the stream; 0 forces that
+ *   "pack_tails"            1         any           band leftovers share chunks; from the next mbb_set_bands
+ *   "bar_params"            1         any           host path: parameter rows written into device memory through the PCIe BAR
+ *   "serve_overlap"         1         any           the served kernel's quadrature beside its constructor (Serve overlap); 0, 1, 2
+ *   "serve"                 1         any           the served boundary: 0 a launch per call, 1 on, 2 whoever else is there (tests)
+ *   "serve_after"           3         >= 1          boundary calls in a row before a server is started
+ *   "serve_idle_us"         1000      any           a server leaves by itself this long after the last request
+ *   "serve_budget_us"       400       >= 1          a served request not answered within this goes by a launch
+ *   "serve_lease_us"        50000     >= 0          a server is sent away after this long in one go; 0 = never
+ *   "serve_grid"            0         0 .. 1048576  workgroups of a server; 0 = as many as the calls have rows, in eights
+ *   "serve_prefetch"        32        0 .. 256      record lines the host asks for ahead of its scan; 0 = none
+ *   "prepass"               -1        any           k_walker_pre before a likelihood launch (Prepass): -1 auto, 0 never, 1 always
+ *   "virtual_ranks"         0         any           testing: a sampler run as this many shards on one GPU
+ *   "xchg_spin_max"         4000000   any           polls before a launch waiting for a peer gives up; default again at mbb_xchg_close
+ *   "lookahead_sampler"     1         any           0: the plain train of one launch per half-step (Sampler forms)
+ *   "flow_sampler"          1         any           one launch per 4096 steps; 0: the plain train as well
+ *   "merged_flow_sampler"   1         any           form 7 (k_flowm) for ensembles of up to two walkers per CU; 0: the resident form
+ *   "resident_sampler"      1         any           form 9 (k_flowa) for larger ensembles; 0: off, 2: every eligible ensemble
+ *   "resident_walkers"      0         any           walkers per workgroup and half of the resident forms; 0 = the host's choice
+ *   "flow_spin_log2"        0         any           log2 of the polls before a wait in a one-launch run gives up; 0 = 22, 63 = none
+ *   "flow_min_steps"        2         any           runs shorter than this take the plain train
+ *   "sharded_flow_sampler"  1         any           a sharded run with the one-hop exchange is one launch per 4096 steps too; 0: not
+ *   "roof_wgs_per_cu"       0         any           measurement only: workgroups per CU of mbb_roof_probe; 0 = 2
+ *   "roof_threads"          0         any           measurement only: threads per workgroup of mbb_roof_probe; 0 = 512
+ *   "pointwise_budget_mb"   16384     >= 0          out-of-sample fit: memory the two columns per band of a group may take
+ *
+ * Info keys (mbb_get_info); any other name is MBB_ERR_ARG.
+ *
+ *   name                     meaning
+ *   "device"                 the context's HIP device
+ *   "cu_count"               its compute units
+ *   "nb"                     bands set by mbb_set_bands
+ *   "nseg"                   ... their segments
+ *   "nunit"                  ... the entries of the unit table
+ *   "nchunk"                 ... its chunks of 64 samples
+ *   "nq"                     ... its quadrature samples
+ *   "simd_chunks_max"        most chunks the unit table deals to one of the four SIMD positions
+ *   "simd_chunks_min"        ... and fewest
+ *   "last_prep_ns"           last mbb_lnlike_batch: time to prepare
+ *   "last_launch_ns"         ... to launch
+ *   "last_wait_ns"           ... to wait
+ *   "last_watch_seen"        ... 1 the watch saw the results, 0 it fell back to the stream, -1 no watch
+ *   "last_prepass"           whether the last likelihood launch was preceded by k_walker_pre
+ *   "last_wpb"               last likelihood launch: walkers per workgroup
+ *   "last_threads"           ... threads per workgroup
+ *   "last_grid"              ... workgroups
+ *   "last_smem"              ... bytes of dynamic LDS
+ *   "last_stage"             ... whether the band tables were staged in LDS
+ *   "last_kernel_form"       which form the last launch ran (Sampler forms; 0: a plain likelihood launch)
+ *   "last_workgroups_ahead"  workgroups of the last sampler launch that worked ahead
+ *   "serving"                1 while a server is resident
+ *   "serve_enabled"          option "serve" as it stands
+ *   "serve_requests"         boundary calls handed to a server
+ *   "serve_fallbacks"        ... of which the answer did not come in time and a launch evaluated them
+ *   "serve_rests"            how often the served boundary has had to rest
+ *   "serve_resting"          boundary calls it still rests for
+ *   "serve_grid"             workgroups of the resident server; 0 without one
+ *   "serve_resizes"          servers that left because they were the wrong width
+ *   "serve_peer_yields"      servers not started, or sent away, because another process is on the device
+ *   "serve_lease_yields"     servers sent away because their lease was up
+ *   "device_peers"           other processes of this library registered on the device
+ *   "device_busy"            ... making boundary calls on it, as the latest boundary call counted them
+ *   "flow_fallbacks"         one-launch sampler runs that gave up and were redone as a launch train
+ *   "flow_resting"           runs the one-launch forms still rest for
+ *   "nranks"                 ranks of the exchange when connected, else of the communicator
+ *   "rank"                   ... and this context's
+ *   "xchg_launches"          launches posted to the one-hop exchange so far
+ *
+ * Waiting.  "spin_wait" says how mbb_lnlike_batch waits: 0 blocks on the stream, 1 polls it, 2
+ * watches the result slots in pinned memory, which are final before the kernel's completion signal
+ * is.  After "spin_budget" polls the watch falls back to blocking on the stream.
+ *
+ * The served boundary.  With "serve" on, after "serve_after" boundary calls in a row with nothing
+ * else in between -- a sampler's loop -- mbb_lnlike_call hands its rows to a kernel that STAYS on
+ * the GPU between the calls and is rung through the BAR (k_serve: no launch per call; same results
+ * bit for bit), while a batch is at most two rows per CU (a workgroup of the kernel takes a row; a
+ * call of more rows than it has workgroups, two).  It leaves by itself "serve_idle_us" after the
+ * last request.  mbb_get_info "serving", "serve_requests", "serve_fallbacks" tell what happened.
+ *
+ * Sharing inside a process.  One such kernel per device and process: any other entry point on the
+ * context, and any entry point of ANOTHER context of the process that comes to the device, tells it
+ * to leave first.  Such a visit also ends this context's run of calls, and doubles, up to 64, the
+ * calls in a row it needs before its next server -- back to "serve_after" once a server has
+ * answered 256 requests: likelihoods used in turns do not spend their time starting and stopping
+ * kernels.
+ *
+ * Sharing between processes.  A server holds a CU per workgroup, and nothing of another PROCESS
+ * fits on those (emcee's pool, mbb_fit.py:80-81 with threads > 1).  So it is as wide as the calls
+ * have rows (in eights; "serve_grid" > 0: that many workgroups; mbb_get_info "serve_grid": the
+ * resident one's) and no wider than this process's share of the device: the CUs divided (in whole
+ * rows of the 8 XCDs) by the processes of this library that are making boundary calls on it right
+ * now.  Those are read from a table in POSIX shared memory keyed by the device's PCI address, each
+ * process noting its calls (csrc/mbb_registry.h; mbb_get_info "device_peers": registered,
+ * "device_busy": calling).  Two workers of 125 rows have their servers side by side; a server
+ * narrower than a call has rows takes two rows a workgroup (three workers: 80 CUs each); a call of
+ * more than twice the share's rows goes by a launch ("serve_peer_yields"); a server too wide for
+ * the share or too narrow for the call leaves and the next starts with the same call
+ * ("serve_resizes").  For processes that table cannot show, a server is sent away after
+ * "serve_lease_us" in one go -- the rows of that call go by a launch, the next server starts after
+ * the next few calls in a row ("serve_lease_yields").  "serve" 2: the whole device is this
+ * process's share whoever else is there (tests).
+ *
+ * Give-up and rest of the served boundary.  A request whose results do not appear within
+ * "serve_budget_us" is evaluated by a launch instead, and three such in a row rest the feature for
+ * the next 4096 boundary calls (mbb_get_info "serve_rests": how often, "serve_resting": calls
+ * left).
+ *
+ * Record prefetch.  Once a request's first record has turned, the host asks for "serve_prefetch"
+ * record lines ahead of its scan.
+ *
+ * Serve overlap.  With "serve_overlap" 1 the served kernel starts a row's passband quadrature
+ * beside its SED constructor -- the blackbody-side value of every sample, which needs none of the
+ * constructor's merge point, into a buffer in LDS -- and sums the units from the buffer when the
+ * constructor is through, when the bands have at least 12 chunks of 64 samples (2: with fewer too);
+ * 0: one after the other, as a launch does it; the same results either way.
+ *
+ * Prepass.  "prepass" -1 (auto: from 64 rows per CU), 0 (never), 1 (always): a likelihood launch of
+ * given rows is preceded by k_walker_pre, which works out gate, SED constructor and penalties with
+ * a LANE per row (k_lnlike: a row of 16 lanes per walker -- right where a constructor is latency, a
+ * quarter of all instructions where a launch is bound by their number); same values bit for bit
+ * (mbb_get_info "last_prepass").
+ *
+ * Sampler forms.  The forms of the single-GPU sampler give the same chains bit for bit (which one a
+ * run takes by default, and what each costs: plan_sampler_run in mbb_hip.hip,
+ * profiles/r04/walker_sweep.txt); mbb_get_info "last_kernel_form" says which form ran.
+ *   - "lookahead_sampler" 0: the plain train of one launch per half-step.
+ *   - "flow_sampler" 1: one launch per 4096 steps, every workgroup resident, rows handed over
+ *     through check words instead of a launch boundary; 0: the plain train as well.
+ *   - "flow_min_steps": runs shorter than this take the plain train: a one-launch run costs ~14 us
+ *     beside its steps (default from profiles/r03/flowm_short_runs.txt).
+ *   - "merged_flow_sampler" 1: ensembles of up to two walkers per CU take "form 7", k_flowm -- one
+ *     workgroup per pair of walkers and candidate; the passband quadrature of both proposals a
+ *     walker can end up making, and the SED constructor for every outcome still open, run ahead of
+ *     the decisions they depend on; 0: those ensembles take the resident forms below too.
+ *   - "resident_sampler" 1: ensembles beyond that run as ONE launch per 4096 steps as well, a
+ *     workgroup owning W = ceil(half / CUs) walkers of each half, up to 8; 0: off, the plain train;
+ *     2: every eligible ensemble takes it.  That run -- "form 9", k_flowa -- constructs every
+ *     walker's proposal a half-step ahead, for both outcomes of its partner's pending move, beside
+ *     the quadrature of the half-step before.  "resident_walkers": W, when not 0.
+ *   - "sharded_flow_sampler" 1: a sharded run with the one-hop exchange is one launch per 4096
+ *     steps on every rank too; 0: one launch per half-step.
+ *
+ * Give-up and rest of the one-launch forms.  "flow_spin_log2" is log2 of the polls before a wait
+ * inside the one-launch run gives up (0 = 22; 63: no polls, the first miss, for tests).
+ * mbb_sampler_run then redoes the run as a launch train and counts it in mbb_get_info
+ * "flow_fallbacks"; the next run takes the one-launch form again, and only three give-ups in a row
+ * rest it for the next 16 runs -- mbb_get_info "flow_resting" says how many of those are left.
+ * mbb_sampler_advance_async keeps nothing to redo a run from: there a give-up surfaces at the next
+ * mbb_sampler_run as MBB_ERR_STATE and the sampler wants mbb_sampler_set_state again. */
 int mbb_set_option(mbb_ctx *ctx, const char *name, long value);
 int mbb_get_info(mbb_ctx *ctx, const char *name, long *value);
 

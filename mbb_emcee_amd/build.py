@@ -26,6 +26,7 @@ FLOW_FLAGS = ["-mllvm", "-sink-insts-to-avoid-spills", "-mllvm", "-disable-machi
 DEPS = [SRC, SRC_HOST, SRC_FLOW, SRC_REG, os.path.join(HERE, "csrc", "mbb_host_tables.h"),
         os.path.join(HERE, "csrc", "mbb_registry.h"),
         os.path.join(HERE, "csrc", "mbb_owned.h"),
+        os.path.join(HERE, "csrc", "mbb_options.h"),
         os.path.join(HERE, "csrc", "mbb_exp2_tab.inc"),
         os.path.join(HERE, "csrc", "mbb_walker_consts.inc"),
         os.path.join(HERE, "csrc", "mbb_walker_penalties.inc"),

@@ -114,6 +114,7 @@ static void (*const g_kernel[kNumSlots])(const LikeArgs) = {MBB_MODELS(MBB_LNLIK
 #undef MBB_FLOWA_V
 #undef MBB_SERVE_V
 #include "mbb_host_tables.h"
+#include "mbb_options.h"
 #include "mbb_owned.h"
 #include "mbb_registry.h"
 
@@ -290,26 +291,18 @@ struct mbb_ctx {
     bool serving = false;
     unsigned long long srv_seq = 0;           // requests so far (the doorbell word is request number << 16 | rows)
     int srv_hot = 0;                          // boundary calls in a row with nothing else in between
-    long srv_need = 0;                        // ... of which a server is started (0: opt_serve_after).  Doubled, up to 64, every
+    long srv_need = 0;                        // ... of which a server is started (0: opt.serve_after).  Doubled, up to 64, every
                                               // time a sibling context's visit sends this context's server away, back to
-                                              // opt_serve_after once a server has answered 256 requests: two likelihoods used
+                                              // opt.serve_after once a server has answered 256 requests: two likelihoods used
                                               // in turns must not spend their time starting and stopping kernels
     long srv_run = 0;                         // requests the present server has answered
     int srv_strikes = 0;                      // servers that had to be given up in a row; three rest the feature
     long srv_rest = 0, srv_rests = 0;         // boundary calls the feature still rests for; how often it has had to
     long srv_requests = 0, srv_fallbacks = 0;
-    long opt_serve = 1;                       // 0: every boundary call is a launch; 2: a server even beside other contexts (tests)
-    long opt_serve_after = 3;                 // boundary calls in a row before a server is started
-    long opt_serve_idle_us = 1000;            // the server leaves after this long without a request (by the clock all CUs share)
-    long opt_serve_budget_us = 400;           // the host gives a served request this long before it falls back to a launch
-    int opt_serve_grid = 0;                   // workgroups of a resident server (0: as many as the calls have rows, in eights)
-    int srv_grid = 0;                         // ... of the one that is resident
+    int srv_grid = 0;                         // workgroups of the server that is resident
     int srv_want = 0;                         // the most rows a call of this context has had (in eights): a server is started that wide
     long srv_resizes = 0;                     // servers that left because they were the wrong width
     int srv_busy = 0;                         // busy processes beside this one, as the latest boundary call counted them
-    int opt_serve_prefetch = 32;              // record lines asked for ahead of the host's scan once the first record has turned (0: none)
-    long opt_serve_lease_us = 50000;          // a server is sent away after this long in one go (0: never): processes this library
-                                              // cannot see (other containers, other programs) get the CUs at least that often
     long srv_t0_ns = 0;                       // when the present server was started
     uint32_t reg_key = 0;                     // the device's name in the cross-process registry (mbb_registry.h): PCI domain:bus:device
     long srv_lease_yields = 0;                // servers sent away because their lease was up
@@ -354,40 +347,16 @@ struct mbb_ctx {
     } map;
     struct EvWork { DevBuf mom, ints, slab, l1, l2, postq, neff, outbuf; } ev;  // the evidence of a chain (evidence_run)
     struct PwWork { DevBuf cols, part, state, sel, status, outbuf; } pw;        // the out-of-sample fit of a chain (pw_run)
-    long opt_pw_budget_mb = 16384;   // ... its two columns per band of a group may take this much; at least one band a group
-    // options
-    long opt_wpb = 0, opt_threads = 0, opt_seg_chunks = 4, opt_debug = 0;
-    long opt_prepass = -1, last_prepass = 0;   // big batches: the constructors by k_walker_pre, a lane per walker (launch_rows)
+    mbbopt::Options opt;                       // what mbb_set_option sets: every field, default and bound in mbb_options.h
+    long last_prepass = 0;                     // whether the last likelihood launch was preceded by k_walker_pre (launch_rows)
     Dev<double> pre;                           // ... its records
-    long opt_zero_copy = 1;   // host path: kernel reads/writes pinned host memory (26 vs 34 us per call)
-    long opt_stage = -1;      // -1 auto, 0 never, 1 whenever the tables fit in LDS
-    long opt_roof_wgs = 0, opt_roof_threads = 0;   // measurement: geometry of mbb_roof_probe
-    long opt_vranks = 0;      // testing: run a sampler as this many shards on one GPU
-    long opt_bar_params = 1;  // host path: write the parameter rows into device memory through the BAR
-    long opt_pack_tails = 1;  // band leftovers share chunks, one row of 16 lanes each (0: a chunk per leftover)
-    long opt_spin_budget = 20000000L;   // polls of the result slots before falling back to the stream
     long last_watch_seen = -1;          // last mbb_lnlike_batch: 1 results seen by the watch, 0 fell back, -1 no watch
-    long opt_spin = 2;        // 0 block on the stream; 1 poll hipStreamQuery (measured: no gain);
-                              // 2 watch the result slots in pinned memory (zero-copy batches <= 8192 rows)
     long last_stage = 0;
-    long opt_lookahead = 1;   // single-GPU sampler runs prepare the next half-step's proposals ahead of the decisions they depend on
-    long opt_serve_overlap = 1;    // the served kernel starts a row's quadrature beside its constructor (0: one after the other)
-    long opt_flow_spin_log2 = 0;   // one-launch run: log2 of the polls before a wait gives up (0: the kernel's 22)
     EventPair ev_timed;            // mbb_sampler_advance_timed
     long flow_fallbacks = 0;       // one-launch runs that timed out and were redone as a launch train
     // A give-up is a property of the moment (a co-tenant holding CUs), not of the context: the next run
     // takes the one-launch form again.  Only kFlowStrikes give-ups in a row rest it, for kFlowRest runs.
     long flow_strikes = 0, flow_rest = 0;
-    long opt_flow_min_steps = 2;   // runs shorter than this take the launch train (a one-launch run costs
-                                   // ~14 us beside its steps: 16.9 us for one step against 15.7)
-    long opt_xflow = 1;       // ... also for a sharded ensemble with the one-hop exchange (SMODE 6)
-    long opt_flow = 1;        // 1: ... as ONE launch per run, the half-steps handing over row by row (forms 6, 7, 9)
-    long opt_flowm = 1;       // 1: ... with the quadrature of both candidates running ahead too (k_flowm, form 7)
-    long opt_flowr = 1;       // 1: ensembles beyond one pair of walkers per CU run as ONE resident launch too, several walkers per
-                              // workgroup, the SED constructor a half-step ahead for both outcomes of each partner's pending move
-                              // (k_flowa, form 9); 0: off; 2: every eligible ensemble takes it
-    long opt_flowr_walkers = 0;   // walkers per workgroup and half of that form (0: the host's choice, ceil(half / CUs))
-                              // (ensembles of 258-512 walkers on 256 CUs); 1, 2 force it (testing)
     size_t lds_granted[kNumSlots] = {};   // dynamic-LDS ceiling already requested, by slot (kernel_slot)
     long last_wpb = 0, last_threads = 0, last_grid = 0, last_smem = 0, last_smode = 0, last_ahead = 0;
     Dev<unsigned long long> stamps;           // diagnostic build only
@@ -403,7 +372,6 @@ struct mbb_ctx {
         unsigned char *peer[16] = {};             // every rank's allocation as mapped here (own = base)
         unsigned long long flow_run = 0;          // one-launch sharded runs so far (the same on every rank)
         unsigned long long seq = 0;               // launches posted so far
-        long long spin_max = 4000000;
     };
     struct Xchg : XchgState {
         Dev<unsigned char> base{mbbo::kDevFine};  // own allocation
@@ -502,7 +470,7 @@ static int yield_server(mbb_ctx *c)
         std::lock_guard<std::mutex> theirs(o->srv_mu, std::adopt_lock);
         if (!o->serving) return MBB_OK;            // (it left by itself, or its owner sent it away, in between)
         o->srv_hot = 0;
-        o->srv_need = std::min<long>(64, 2 * (o->srv_need > 0 ? o->srv_need : o->opt_serve_after));
+        o->srv_need = std::min<long>(64, 2 * (o->srv_need > 0 ? o->srv_need : o->opt.serve_after));
         return serve_stop(o);
     }
 }
@@ -643,7 +611,7 @@ extern "C" int mbb_set_bands(mbb_ctx *c, const double *freq, const double *weigh
     if (rc) return rc;
     mbbh::BandLayout L;
     const char *why = "bad band tables";
-    if (mbbh::build_band_layout(freq, weight, offsets, nb, (int)c->opt_seg_chunks, c->opt_pack_tails != 0, L, &why))
+    if (mbbh::build_band_layout(freq, weight, offsets, nb, (int)c->opt.seg_chunks, c->opt.pack_tails != 0, L, &why))
         return fail(MBB_ERR_ARG, why);
     std::vector<int4> unit_tab(L.unit_tab.size());
     std::vector<int2> band_rng(L.band_rng.size());
@@ -744,7 +712,7 @@ static const int32_t kStatusSentinel = 0x7fffff01;
 
 static int wait_stream(mbb_ctx *c)
 {
-    if (c->opt_spin == 1) {
+    if (c->opt.spin == 1) {
         for (;;) {
             hipError_t e = hipStreamQuery(c->stream);
             if (e == hipSuccess) return MBB_OK;
@@ -840,15 +808,15 @@ static void pick_geometry(const mbb_ctx *c, int n, int &wpb, int &threads, bool 
         // 13-17 % from 500 to 8192 rows, 7 % at 32768, 3 % at 65536; at 250 000 rows it is 3 % behind.
         const long wm = std::min<long>(64, (n + cus - 1) / cus);
         const size_t tables = (size_t)c->nchunk * 64 * 3 * sizeof(double);
-        if (n <= 256 * cus && c->opt_wpb <= 0 && c->opt_threads <= 0 && c->opt_stage != 0 &&
+        if (n <= 256 * cus && c->opt.wpb <= 0 && c->opt.threads <= 0 && c->opt.stage != 0 &&
             lnlike_lds_base(c, (int)wm) + (c->has_cov ? 8 * (size_t)c->nb * c->nb : 0) + tables + 16 <= dynamic_lds_limit(c)) {
             w = wm; t = 1024;
             if (mid_staged) *mid_staged = true;
         }
     }
-    if (c->opt_wpb > 0) w = c->opt_wpb > 64 ? 64 : c->opt_wpb;
+    if (c->opt.wpb > 0) w = c->opt.wpb > 64 ? 64 : c->opt.wpb;
     wpb = (int)w;
-    if (c->opt_threads > 0) t = c->opt_threads;
+    if (c->opt.threads > 0) t = c->opt.threads;
     if (t < 64) t = 64;
     if (t > 1024) t = 1024;
     threads = (int)((t / 64) * 64);
@@ -924,7 +892,7 @@ static void fill_model_args(const mbb_ctx *c, LikeArgs &a)
     for (int i = 0; i < 5; ++i) a.lowlim[i] = c->lowlim[i];
     for (int i = 0; i < 6; ++i) { a.uplim[i] = c->uplim[i]; a.gmean[i] = c->gmean[i]; a.givar[i] = c->givar[i]; }
     a.has_uplim = c->has_uplim; a.has_gprior = c->has_gprior;
-    a.debug = (int)c->opt_debug;
+    a.debug = (int)c->opt.debug;
 #ifdef MBB_STAMPS
     a.stamps = c->stamps.d();
 #endif
@@ -951,8 +919,8 @@ static int lnlike_shape(mbb_ctx *c, int n, LnlikeShape &g, LikeArgs &a)
     // is 4-5 % slower than reading the tables through L2, because 60 KB of LDS per workgroup caps residency at two per CU.
     const size_t table_bytes = (size_t)c->nchunk * 64 * 3 * sizeof(double);
     g.stage = ((g.wpb == 1 && n <= c->cu_count) || mid_staged) && smem + table_bytes + 16 <= dyn_limit;
-    if (c->opt_stage == 0) g.stage = false;
-    if (c->opt_stage == 1) g.stage = smem + table_bytes + 16 <= dyn_limit;
+    if (c->opt.stage == 0) g.stage = false;
+    if (c->opt.stage == 1) g.stage = smem + table_bytes + 16 <= dyn_limit;
     g.smem = smem + (g.stage ? table_bytes + 16 : 0);
     if (c->nsrc > 1 && n % c->nsrc != 0) return fail(MBB_ERR_ARG, "row count must be a multiple of the number of sources");
     memset(&a, 0, sizeof a);
@@ -980,7 +948,7 @@ static int launch_rows(mbb_ctx *c, const double *d_pars, int n, double *d_lnl, i
     // -- where a launch is bound by the number of instructions it issues, a row of 16 lanes per walker spends a quarter of
     // them on the constructors (cfg5's 250 000 rows: 1.31 -> 1.0x ms).  Option "prepass": -1 auto (from 64 walkers per CU),
     // 0 never, 1 always.
-    if (c->opt_prepass > 0 || (c->opt_prepass < 0 && (long)n >= 64L * c->cu_count)) {
+    if (c->opt.prepass > 0 || (c->opt.prepass < 0 && (long)n >= 64L * c->cu_count)) {
         const size_t need = (size_t)n * kPreWords * sizeof(double);
         size_t cap = c->pre.cap ? c->pre.cap : 16384 * (size_t)kPreWords * sizeof(double);
         while (cap < need) cap *= 2;
@@ -1032,7 +1000,7 @@ static int lnlike_zero_copy(mbb_ctx *c, int n, bool push, bool model_flux, long 
     // writes (a NaN with a payload; it produces the canonical NaN), and the host
     // watches them: a walker's results are final the moment they appear, before the
     // end-of-kernel bookkeeping.  status is written after lnl by the same lane.
-    const bool watch = c->opt_spin == 2 && !model_flux && n <= 8192;
+    const bool watch = c->opt.spin == 2 && !model_flux && n <= 8192;
     c->last_watch_seen = -1;
     if (watch) {
         uint64_t *hl = reinterpret_cast<uint64_t *>(c->bnd.h_lnl.h());
@@ -1048,7 +1016,7 @@ static int lnlike_zero_copy(mbb_ctx *c, int n, bool push, bool model_flux, long 
         const uint64_t *hl = reinterpret_cast<const uint64_t *>(c->bnd.h_lnl.h());
         const int32_t *hs = c->bnd.h_status.h();
         int i = 0;
-        for (long spins = 0; spins < c->opt_spin_budget; ++spins) {   // default ~ tens of ms, then give up
+        for (long spins = 0; spins < c->opt.spin_budget; ++spins) {   // default ~ tens of ms, then give up
             while (i < n && __atomic_load_n(&hl[i], __ATOMIC_ACQUIRE) != kLnlSentinel &&
                    __atomic_load_n(&hs[i], __ATOMIC_ACQUIRE) != kStatusSentinel) ++i;
             if (i == n) { seen = true; break; }
@@ -1073,14 +1041,14 @@ extern "C" int mbb_lnlike_batch(mbb_ctx *c, const double *pars, int n, double *l
     const size_t nbytes = (size_t)n * 5 * sizeof(double);
     auto now_ns = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1000000000L + ts.tv_nsec; };
     const long t_a = now_ns();
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
+    const bool push = c->opt.zero_copy && c->opt.bar_params && c->bnd.w_pars.d();
     if (push) {
         memcpy(c->bnd.w_pars.d(), pars, nbytes);           // CPU stores through the BAR ...
         __builtin_ia32_sfence();                   // ... drained before the doorbell is rung
     } else {
         memcpy(c->bnd.h_pars.h(), pars, nbytes);
     }
-    if (c->opt_zero_copy) {
+    if (c->opt.zero_copy) {
         if ((rc = lnlike_zero_copy(c, n, push, model_flux != nullptr, t_a))) return rc;
     } else {
         HIPCHK(hipMemcpyAsync(c->bnd.d_pars.d(), c->bnd.h_pars.h(), nbytes, hipMemcpyHostToDevice, c->stream));
@@ -1119,7 +1087,7 @@ extern "C" int mbb_boundary_buffers(mbb_ctx *c, int nmax, double **in, double **
     if (rc) return rc;
     if (nmax <= 0 || !in || !out) return fail(MBB_ERR_ARG, "bad arguments");
     if ((rc = ensure_capacity(c, (size_t)nmax, false))) return rc;
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
+    const bool push = c->opt.zero_copy && c->opt.bar_params && c->bnd.w_pars.d();
     c->call_in = push ? c->bnd.w_pars.d() : c->bnd.h_pars.h();
     c->call_cap = c->bnd.cap;
     *in = c->call_in; *out = c->bnd.h_lnl.h();
@@ -1153,7 +1121,7 @@ static int serve_stop(mbb_ctx *c)
 // more than this process's share of the device.
 static int serve_grid(const mbb_ctx *c, int n, int share)
 {
-    int g = c->opt_serve_grid > 0 ? c->opt_serve_grid : std::max(c->srv_want, (n + 7) & ~7);
+    int g = c->opt.serve_grid > 0 ? (int)c->opt.serve_grid : std::max(c->srv_want, (n + 7) & ~7);
     return std::min(std::min(g, share), c->cu_count);
 }
 
@@ -1178,22 +1146,22 @@ static int serve_launch(mbb_ctx *c, int n, unsigned long long word, int grid)
     const size_t table_bytes = (size_t)c->nchunk * 64 * 3 * sizeof(double);
     a.cov_in_lds = (c->has_cov && serve_lds(c->nb, c->npart, true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
     const size_t sm = serve_lds(c->nb, c->npart, a.cov_in_lds != 0);
-    const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
+    const bool stg = c->opt.stage != 0 && sm + table_bytes + 16 <= dyn_limit;
     // The quadrature beside the constructor (mbb_serve.hip.h): every wave but the first keeps both candidates of its own
     // unit's samples in registers
     // -- with a chunk of samples at least for each of twelve waves: with fewer the extra barrier costs more than there is to
     // gain (cfg1's one chunk: 8.5-8.7 -> 8.9 us per 25-row call; option "serve_overlap" 2: regardless; 0: never)
     // -- and waves to work ahead with (a workgroup narrowed by option "block_threads" may have none besides the constructor's)
     // -- and units of at most four chunks (option "seg_chunks")
-    const bool ovl = c->opt_serve_overlap != 0 && (c->nchunk >= 12 || c->opt_serve_overlap == 2) && threads >= 256 &&
-                     c->opt_seg_chunks >= 1 && c->opt_seg_chunks <= 4;
+    const bool ovl = c->opt.serve_overlap != 0 && (c->nchunk >= 12 || c->opt.serve_overlap == 2) && threads >= 256 &&
+                     c->opt.seg_chunks >= 1 && c->opt.seg_chunks <= 4;
     a.spec_cfg = ovl ? 1 : 0;
     const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
     if (sm_total > dyn_limit) return 1;
     a.chain6 = reinterpret_cast<double *>(c->srv.h_gone.dv());
     a.pos6 = reinterpret_cast<double *>(c->srv.w_door.d());
     a.seed = word;
-    a.persist = (int)std::min<long>(std::max<long>(c->opt_serve_idle_us, 20), 1000000);
+    a.persist = (int)std::min<long>(std::max<long>(c->opt.serve_idle_us, 20), 1000000);
     *c->srv.h_gone.h() = 0;
     __atomic_store_n(c->srv.w_door.d(), word, __ATOMIC_RELAXED);
     __builtin_ia32_sfence();
@@ -1237,7 +1205,7 @@ static int serve_start(mbb_ctx *c, int n, unsigned long long word, int grid)
 // negative on error.  The parameter rows are in c->bnd.w_pars already.
 static int serve_request(mbb_ctx *c, int n, int grid)
 {
-    const int kPfAhead = c->opt_serve_prefetch;
+    const int kPfAhead = (int)c->opt.serve_prefetch;
     auto now_ns = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1000000000L + ts.tv_nsec; };
     const long t_a = now_ns();
     // (the records exist once a server has been started; before that serve_start makes them)
@@ -1248,7 +1216,7 @@ static int serve_request(mbb_ctx *c, int n, int grid)
     const unsigned long long word = (++c->srv_seq << 16) | (unsigned long long)n;
     __builtin_ia32_sfence();                       // the caller's rows, through the BAR, before the request
     const long t_b = now_ns();
-    long budget_ns = c->opt_serve_budget_us * 1000L;
+    long budget_ns = c->opt.serve_budget_us * 1000L;
     if (!c->serving) {
         int rc = serve_start(c, n, word, grid);
         if (rc) return rc;
@@ -1311,8 +1279,8 @@ extern "C" int mbb_lnlike_call(mbb_ctx *c, int n)
     int rc;
     if (n <= 0) return n == 0 ? MBB_OK : fail(MBB_ERR_ARG, "bad row count");
     if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
-    if (!c->opt_zero_copy || !c->call_in || c->call_cap != c->bnd.cap || (size_t)n > c->bnd.cap ||
+    const bool push = c->opt.zero_copy && c->opt.bar_params && c->bnd.w_pars.d();
+    if (!c->opt.zero_copy || !c->call_in || c->call_cap != c->bnd.cap || (size_t)n > c->bnd.cap ||
         c->call_in != (push ? c->bnd.w_pars.d() : c->bnd.h_pars.h())) {
         if (c->serving && (rc = serve_stop(c))) return rc;
         return fail(MBB_ERR_STATE, "mbb_boundary_buffers first (or again: the buffers or the host-path options changed)");
@@ -1321,7 +1289,7 @@ extern "C" int mbb_lnlike_call(mbb_ctx *c, int n)
     // a kernel that stays on the GPU (k_serve) instead of a launch each: while the batch is at most a row per CU and the
     // host path is the default one.  One server per device and process: whichever context comes to the device tells a
     // sibling's to leave first (use(), and the line below).
-    bool can_serve = c->opt_serve && push && n <= kServePasses * c->cu_count && c->nsrc <= 1 && c->opt_spin == 2 && c->data_nb == c->nb;
+    bool can_serve = c->opt.serve && push && n <= kServePasses * c->cu_count && c->nsrc <= 1 && c->opt.spin == 2 && c->data_nb == c->nb;
     if (c->srv_rest > 0) { --c->srv_rest; can_serve = false; }      // (resting after three lost servers in a row)
     // ... and across PROCESSES (emcee's pool, mbb_fit.py:80-81 threads > 1: the likelihood pickled into workers that share the
     // GPU): a server holds a CU per workgroup, and nothing of another process fits on those -- with round 4's server on every
@@ -1332,11 +1300,11 @@ extern "C" int mbb_lnlike_call(mbb_ctx *c, int n)
     // by a launch; a server that is too wide for the share, or too narrow for the call, leaves and the next starts with this
     // call.  ("serve" 2: the whole device is this process's share -- tests.)
     int share = c->cu_count, grid = 0;
-    const long need_hot = c->srv_need > 0 ? c->srv_need : c->opt_serve_after;
+    const long need_hot = c->srv_need > 0 ? c->srv_need : c->opt.serve_after;
     timespec tb = {0, 0};
     if (can_serve) {
         clock_gettime(CLOCK_MONOTONIC, &tb);                   // (one look at the clock: who is busy, and the lease)
-        if (c->opt_serve != 2) {
+        if (c->opt.serve != 2) {
             const uint64_t now_ms = (uint64_t)tb.tv_sec * 1000u + (uint64_t)(tb.tv_nsec / 1000000);
             // (before a server is there every call looks: a pool's workers begin together, and three servers of 128 do not fit)
             const int busy = mbbh::registry_busy(c->reg_key, now_ms, 250, !c->serving);
@@ -1362,8 +1330,8 @@ extern "C" int mbb_lnlike_call(mbb_ctx *c, int n)
     }
     // ... and not for ever in one go: processes the registry cannot see get the CUs when the lease is up (the rows of this
     // call go by a launch, a new server starts after the next few calls in a row)
-    if (can_serve && c->serving && c->opt_serve_lease_us > 0) {
-        if (tb.tv_sec * 1000000000L + tb.tv_nsec - c->srv_t0_ns > c->opt_serve_lease_us * 1000L) {
+    if (can_serve && c->serving && c->opt.serve_lease_us > 0) {
+        if (tb.tv_sec * 1000000000L + tb.tv_nsec - c->srv_t0_ns > c->opt.serve_lease_us * 1000L) {
             can_serve = false;
             c->srv_hot = 0;
             ++c->srv_lease_yields;
@@ -1582,7 +1550,7 @@ static int shard_plan(const mbb_ctx *c, const mbb_sampler_state *s, ShardPlan &p
     const bool xchg = c->x.connected && !s->pos6_own.p && c->x.n > 1;
     p.collective = xchg || (c->comm != nullptr && c->nranks > 1);
     const int granks = xchg ? c->x.n : c->nranks, grank = xchg ? c->x.rank : c->rank;
-    p.shards = p.collective ? granks : (int)(c->opt_vranks > 1 ? c->opt_vranks : 1);
+    p.shards = p.collective ? granks : (int)(c->opt.vranks > 1 ? c->opt.vranks : 1);
     if (p.shards > 1 && s->nsrc > 1)
         return fail(MBB_ERR_ARG, "a sharded sampler run needs a single source");
     if (half % p.shards != 0)
@@ -1634,17 +1602,17 @@ static int plan_sampler_run(const mbb_ctx *c, const mbb_sampler_state *s, int ns
     int wpb, threads;
     pick_geometry(c, nl, wpb, threads);
     lookahead_plan(c, nl, threads, p.per, rp.rows, rp.aw, rp.n_ahead);
-    const bool flow = one_launch_ok && c->opt_lookahead && c->opt_flow && s->nsrc == 1;
-    if (flow && p.xchg && c->opt_xflow && nsteps > 0 && wpb == 1 && rp.n_ahead + nl <= c->cu_count &&
+    const bool flow = one_launch_ok && c->opt.lookahead && c->opt.flow && s->nsrc == 1;
+    if (flow && p.xchg && c->opt.xflow && nsteps > 0 && wpb == 1 && rp.n_ahead + nl <= c->cu_count &&
         (size_t)s->rows() <= c->x.cap_rows) {
         rp.form = 6;
         return MBB_OK;
     }
-    const bool resident = flow && p.shards == 1 && !p.collective && nsteps >= (int)std::max<long>(1, c->opt_flow_min_steps);
-    rp.res_w = c->opt_flowr_walkers > 0 ? (int)std::min<long>(c->opt_flowr_walkers, kFaMaxW) : (nl + c->cu_count - 1) / c->cu_count;
+    const bool resident = flow && p.shards == 1 && !p.collective && nsteps >= (int)std::max<long>(1, c->opt.flow_min_steps);
+    rp.res_w = c->opt.flowr_walkers > 0 ? (int)std::min<long>(c->opt.flowr_walkers, kFaMaxW) : (nl + c->cu_count - 1) / c->cu_count;
     const bool res_fits = rp.res_w >= 1 && rp.res_w <= kFaMaxW && (nl + rp.res_w - 1) / rp.res_w <= c->cu_count;
-    if (resident && c->opt_flowm && c->opt_flowr != 2 && 2 * nl <= c->cu_count && wpb == 1) rp.form = 7;
-    else if (resident && c->opt_flowr != 0 && res_fits) rp.form = 9;
+    if (resident && c->opt.flowm && c->opt.flowr != 2 && 2 * nl <= c->cu_count && wpb == 1) rp.form = 7;
+    else if (resident && c->opt.flowr != 0 && res_fits) rp.form = 9;
     else rp.form = p.xchg ? 2 : 1;
     rp.resting = rp.form >= 7 && c->flow_rest > 0;
     if (rp.resting) rp.form = 1;           // (forms 7 and 9 have no exchange)
@@ -1684,7 +1652,7 @@ static int launch_sampler(mbb_ctx *c, const RunPlan &rp, const SamplerLaunch &sl
     a.s_begin = sl.s_begin; a.c_begin = sl.c_begin; a.c_count = sl.c_count; a.m_count = sl.m_count; a.nw = sl.nw;
     a.step = sl.step; a.half = sl.half; a.stretch_a = sl.stretch_a; a.zpow = sl.zpow; a.seed = sl.seed; a.nw_src = sl.nw_src;
     a.persist = sl.persist; a.spec = sl.spec; a.flow_serial = sl.serial;   // (forms 1, 2: serial 0, the null `pars`)
-    const int spin = (int)((c->opt_flow_spin_log2 & 0x3f) << 24);
+    const int spin = (int)((c->opt.flow_spin_log2 & 0x3f) << 24);
     if (form == 7 || form == 9) {
         // the resident sampler forms, every workgroup resident (plan_sampler_run), each with its own LDS plan:
         //   form 7 (k_flowm): 2 n workgroups of (quadrature waves + 5), one per (walker, candidate)
@@ -1699,7 +1667,7 @@ static int launch_sampler(mbb_ctx *c, const RunPlan &rp, const SamplerLaunch &sl
         a.wpb = W;
         a.cov_in_lds = (c->has_cov && lds_of(true) <= std::min<size_t>(64 * 1024, dyn_limit)) ? 1 : 0;
         const size_t sm = lds_of(a.cov_in_lds != 0);
-        const bool stg = c->opt_stage != 0 && sm + table_bytes + 16 <= dyn_limit;
+        const bool stg = c->opt.stage != 0 && sm + table_bytes + 16 <= dyn_limit;
         const size_t sm_total = sm + (stg ? table_bytes + 16 : 0);
         if (sm_total > dyn_limit) return fail(MBB_ERR_ARG, "band tables too large for the LDS plan");
         c->last_wpb = W; c->last_threads = thr; c->last_grid = wgs; c->last_smem = (long)sm_total;
@@ -1766,7 +1734,7 @@ static int run_one_launch(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, S
             hipLaunchKernelGGL(k_flow_post, dim3(1), dim3(64), 0, c->stream, c->x.d_flowx.d(), (int)R, 1, fxh.run,
                                (const int *)s->d_err.d());
             hipLaunchKernelGGL(k_flow_wait_end, dim3(1), dim3(64), 0, c->stream, flow_view(mine, (int)R).endf, c->x.n, rank,
-                               fxh.run, c->x.spin_max, s->d_err.d());
+                               fxh.run, (long long)c->opt.xchg_spin_max, s->d_err.d());
             hipLaunchKernelGGL(k_flow_finish, dim3((unsigned)((R * 6 + 255) / 256)), dim3(256), 0, c->stream,
                                s->d_pos6, mine, (int)R, 2 * nt);
             HIPCHK(hipGetLastError());
@@ -1803,7 +1771,7 @@ static int run_train(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, Sample
         // and acceptance counts stay per rank (the caller gathers them if it wants them)
         if (c->x.seq)
             hipLaunchKernelGGL(k_xchg_wait, dim3(1), dim3(64), 0, c->stream, c->x.flags(c->x.rank), c->x.n,
-                               c->x.rank, c->x.seq, c->x.spin_max, s->d_err.d());
+                               c->x.rank, c->x.seq, (long long)c->opt.xchg_spin_max, s->d_err.d());
         HIPCHK(hipGetLastError());
     } else if (p.collective) {   // every rank ends up with the whole chain and all counts
         if (store && (rc = allgather_bytes(c, s->d_chain6.d(), (size_t)nsteps * 2 * nl * 6 * sizeof(double)))) return rc;
@@ -1854,7 +1822,7 @@ static int sampler_enqueue(mbb_ctx *c, mbb_sampler_state *s, const RunPlan &rp, 
         memset(&xa, 0, sizeof xa);
         for (int r = 0; r < c->x.n; ++r) { xa.xpos[r] = c->x.pos6(r); xa.xflag[r] = c->x.flags(r); }
         xa.xcount = c->x.count(); xa.xn = c->x.n; xa.xrank = c->x.rank;
-        xa.xseq0 = c->x.seq; xa.xspin_max = c->x.spin_max;
+        xa.xseq0 = c->x.seq; xa.xspin_max = c->opt.xchg_spin_max;
         HIPCHK(hipMemcpyAsync(c->x.d_args.d(), &xa, sizeof xa, hipMemcpyHostToDevice, c->stream));
     }
     SamplerLaunch sl;
@@ -3458,7 +3426,7 @@ static int pw_run(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nstep
     if ((rc = pw_check(c, nsrc, nw, nsteps, sp, o))) return rc;
     const int nb = c->nb;
     const size_t cells = (size_t)nsrc * nw * nsteps, ns = (size_t)nsrc, tab = ns * nb;
-    const long long budget = (c->opt_pw_budget_mb > 0 ? c->opt_pw_budget_mb : 0) * (1ll << 20);
+    const long long budget = (c->opt.pw_budget_mb > 0 ? c->opt.pw_budget_mb : 0) * (1ll << 20);
     const int group = (int)std::max<long long>(1, std::min<long long>(nb, budget / (long long)(2 * cells * sizeof(double))));
     PwArgs a;
     memset(&a, 0, sizeof a);
@@ -3831,8 +3799,8 @@ extern "C" int mbb_roof_probe(mbb_ctx *c, const double pars[5], int reps, double
     if (rc) return rc;
     if (!pars || reps <= 0 || !seconds || !lane_slots) return fail(MBB_ERR_ARG, "bad arguments");
     if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
-    const int threads = c->opt_roof_threads > 0 ? (int)c->opt_roof_threads : 512;
-    const int grid = (int)(c->opt_roof_wgs > 0 ? c->opt_roof_wgs : 2) * c->cu_count;
+    const int threads = c->opt.roof_threads > 0 ? (int)c->opt.roof_threads : 512;
+    const int grid = (int)(c->opt.roof_wgs > 0 ? c->opt.roof_wgs : 2) * c->cu_count;
     if ((rc = ensure_sed(c, 1, (size_t)grid * threads + 2))) return rc;
     if ((rc = run_prologue(c, pars, 1, c->opthin, c->noalpha, c->wavenorm, 0, nullptr))) return rc;
     unsigned long long *d_clk = reinterpret_cast<unsigned long long *>(c->sed.out.d() + (size_t)grid * threads);
@@ -3990,90 +3958,82 @@ extern "C" int mbb_set_option(mbb_ctx *c, const char *name, long value)
         if (rc) return rc;
     }
     c->srv_hot = 0;
-    if (!strcmp(name, "walkers_per_group")) c->opt_wpb = value;
-    else if (!strcmp(name, "block_threads")) c->opt_threads = value;
-    else if (!strcmp(name, "zero_copy")) c->opt_zero_copy = value;
-    else if (!strcmp(name, "seg_chunks")) c->opt_seg_chunks = value;
-    else if (!strcmp(name, "debug")) c->opt_debug = value;
-    else if (!strcmp(name, "stage_tables")) c->opt_stage = value;
-    else if (!strcmp(name, "spin_wait")) c->opt_spin = value;
-    else if (!strcmp(name, "spin_budget")) c->opt_spin_budget = value < 0 ? 0 : value;
-    else if (!strcmp(name, "pack_tails")) c->opt_pack_tails = value;
-    else if (!strcmp(name, "bar_params")) c->opt_bar_params = value;
-    else if (!strcmp(name, "serve_overlap")) c->opt_serve_overlap = value;
-    else if (!strcmp(name, "serve")) { c->opt_serve = value; c->srv_strikes = 0; c->srv_rest = 0; }
-    else if (!strcmp(name, "serve_after")) { c->opt_serve_after = value < 1 ? 1 : value; c->srv_need = 0; }
-    else if (!strcmp(name, "serve_idle_us")) c->opt_serve_idle_us = value;
-    else if (!strcmp(name, "serve_budget_us")) c->opt_serve_budget_us = value < 1 ? 1 : value;
-    else if (!strcmp(name, "serve_lease_us")) c->opt_serve_lease_us = value < 0 ? 0 : value;
-    else if (!strcmp(name, "serve_grid")) c->opt_serve_grid = value < 0 ? 0 : (int)std::min<long>(value, 1 << 20);
-    else if (!strcmp(name, "serve_prefetch")) c->opt_serve_prefetch = value < 0 ? 0 : (value > 256 ? 256 : (int)value);
-    else if (!strcmp(name, "prepass")) c->opt_prepass = value;
-    else if (!strcmp(name, "virtual_ranks")) c->opt_vranks = value;
-    else if (!strcmp(name, "xchg_spin_max")) c->x.spin_max = value;
-    else if (!strcmp(name, "lookahead_sampler")) c->opt_lookahead = value;
-    else if (!strcmp(name, "flow_sampler")) c->opt_flow = value;
-    else if (!strcmp(name, "merged_flow_sampler")) c->opt_flowm = value;
-    else if (!strcmp(name, "resident_sampler")) c->opt_flowr = value;
-    else if (!strcmp(name, "resident_walkers")) c->opt_flowr_walkers = value;
-    else if (!strcmp(name, "flow_spin_log2")) c->opt_flow_spin_log2 = value;
-    else if (!strcmp(name, "flow_min_steps")) c->opt_flow_min_steps = value;
-    else if (!strcmp(name, "sharded_flow_sampler")) c->opt_xflow = value;
-    else if (!strcmp(name, "roof_wgs_per_cu")) c->opt_roof_wgs = value;
-    else if (!strcmp(name, "roof_threads")) c->opt_roof_threads = value;
-    else if (!strcmp(name, "pointwise_budget_mb")) c->opt_pw_budget_mb = value < 0 ? 0 : value;
-    else return fail(MBB_ERR_ARG, "unknown option");
+    const mbbopt::OptionRow *row = mbbopt::set_option(c->opt, name, value);
+    if (!row) return fail(MBB_ERR_ARG, "unknown option");
+    if (row->field == &mbbopt::Options::serve) { c->srv_strikes = 0; c->srv_rest = 0; }
+    if (row->field == &mbbopt::Options::serve_after) c->srv_need = 0;
     return MBB_OK;
 }
+
+// What mbb_get_info answers, by name; the keys a sampler's run asks for at every call come first.
+struct InfoRow {
+    const char *name;
+    long (*get)(mbb_ctx *);
+};
+#define INFO(name, value) {name, [](mbb_ctx *c) -> long { return value; }}
+static const InfoRow kInfo[] = {
+    INFO("nranks", c->x.connected ? c->x.n : c->nranks),
+    INFO("rank", c->x.connected ? c->x.rank : c->rank),
+    INFO("flow_fallbacks", c->flow_fallbacks),
+    INFO("flow_resting", c->flow_rest),
+    INFO("nb", c->nb),
+    INFO("nseg", c->nseg),
+    INFO("nunit", c->nunit),
+    INFO("last_prep_ns", c->t_prep_ns),
+    INFO("serving", c->serving ? 1 : 0),
+    INFO("serve_requests", c->srv_requests),
+    INFO("serve_fallbacks", c->srv_fallbacks),
+    INFO("last_prepass", c->last_prepass),
+    INFO("serve_enabled", c->opt.serve),
+    INFO("device_peers", mbbh::registry_peers(c->reg_key, true)),
+    INFO("serve_peer_yields", c->srv_peer_yields),
+    INFO("serve_resizes", c->srv_resizes),
+    INFO("serve_rests", c->srv_rests),
+    INFO("serve_resting", c->srv_rest),
+    INFO("device_busy", c->srv_busy),
+    INFO("serve_grid", c->serving ? c->srv_grid : 0),
+    INFO("serve_lease_yields", c->srv_lease_yields),
+    INFO("last_launch_ns", c->t_launch_ns),
+    INFO("last_wait_ns", c->t_wait_ns),
+    INFO("last_watch_seen", c->last_watch_seen),
+    INFO("simd_chunks_max", *std::max_element(c->simd_chunks, c->simd_chunks + 4)),
+    INFO("simd_chunks_min", *std::min_element(c->simd_chunks, c->simd_chunks + 4)),
+    INFO("nchunk", c->nchunk),
+    INFO("nq", c->nq),
+    INFO("cu_count", c->cu_count),
+    INFO("last_wpb", c->last_wpb),
+    INFO("last_threads", c->last_threads),
+    INFO("last_grid", c->last_grid),
+    INFO("last_kernel_form", c->last_smode),     // k_lnlike's SMODE of the last launch
+    INFO("last_workgroups_ahead", c->last_ahead),
+    INFO("last_smem", c->last_smem),
+    INFO("last_stage", c->last_stage),
+    INFO("device", c->device),
+    INFO("xchg_launches", (long)c->x.seq),
+};
+#undef INFO
 
 extern "C" int mbb_get_info(mbb_ctx *c, const char *name, long *value)
 {
     if (!c || !name || !value) return fail(MBB_ERR_ARG, "null argument");
-    if (!strcmp(name, "nb")) *value = c->nb;
-    else if (!strcmp(name, "nseg")) *value = c->nseg;
-    else if (!strcmp(name, "nunit")) *value = c->nunit;
-    else if (!strcmp(name, "last_prep_ns")) *value = c->t_prep_ns;
-    else if (!strcmp(name, "serving")) *value = c->serving ? 1 : 0;
-    else if (!strcmp(name, "serve_requests")) *value = c->srv_requests;
-    else if (!strcmp(name, "serve_fallbacks")) *value = c->srv_fallbacks;
-    else if (!strcmp(name, "last_prepass")) *value = c->last_prepass;
-    else if (!strcmp(name, "serve_enabled")) *value = c->opt_serve;
-    else if (!strcmp(name, "device_peers")) *value = mbbh::registry_peers(c->reg_key, true);
-    else if (!strcmp(name, "serve_peer_yields")) *value = c->srv_peer_yields;
-    else if (!strcmp(name, "serve_resizes")) *value = c->srv_resizes;
-    else if (!strcmp(name, "serve_rests")) *value = c->srv_rests;
-    else if (!strcmp(name, "serve_resting")) *value = c->srv_rest;
-    else if (!strcmp(name, "device_busy")) *value = c->srv_busy;
-    else if (!strcmp(name, "serve_grid")) *value = c->serving ? c->srv_grid : 0;
-    else if (!strcmp(name, "serve_lease_yields")) *value = c->srv_lease_yields;
-    else if (!strcmp(name, "last_launch_ns")) *value = c->t_launch_ns;
-    else if (!strcmp(name, "last_wait_ns")) *value = c->t_wait_ns;
-    else if (!strcmp(name, "last_watch_seen")) *value = c->last_watch_seen;
-    else if (!strcmp(name, "simd_chunks_max")) *value = *std::max_element(c->simd_chunks, c->simd_chunks + 4);
-    else if (!strcmp(name, "simd_chunks_min")) *value = *std::min_element(c->simd_chunks, c->simd_chunks + 4);
-    else if (!strcmp(name, "nchunk")) *value = c->nchunk;
-    else if (!strcmp(name, "nq")) *value = c->nq;
-    else if (!strcmp(name, "cu_count")) *value = c->cu_count;
-    else if (!strcmp(name, "last_wpb")) *value = c->last_wpb;
-    else if (!strcmp(name, "last_threads")) *value = c->last_threads;
-    else if (!strcmp(name, "last_grid")) *value = c->last_grid;
-    else if (!strcmp(name, "flow_fallbacks")) *value = c->flow_fallbacks;
-    else if (!strcmp(name, "flow_resting")) *value = c->flow_rest;
-    else if (!strcmp(name, "last_kernel_form")) *value = c->last_smode;     // k_lnlike's SMODE of the last launch
-    else if (!strcmp(name, "last_workgroups_ahead")) *value = c->last_ahead;
-    else if (!strcmp(name, "last_smem")) *value = c->last_smem;
-    else if (!strcmp(name, "last_stage")) *value = c->last_stage;
-    else if (!strcmp(name, "device")) *value = c->device;
-    else if (!strcmp(name, "nranks")) *value = c->x.connected ? c->x.n : c->nranks;
-    else if (!strcmp(name, "rank")) *value = c->x.connected ? c->x.rank : c->rank;
-    else if (!strcmp(name, "xchg_launches")) *value = (long)c->x.seq;
-    else return fail(MBB_ERR_ARG, "unknown info key");
-    return MBB_OK;
+    for (const InfoRow &r : kInfo)
+        if (!strcmp(name, r.name)) {
+            *value = r.get(c);
+            return MBB_OK;
+        }
+    return fail(MBB_ERR_ARG, "unknown info key");
 }
 
 // ---- one-hop exchange between the ranks of a sharded sampler run ----------------
 // (the direct exchange on the xGMI mesh instead of a ring
 // collective for a 6 KB message.)  Replaces emcee's pool, mbb_fit.py:80-81.
+// "xchg_spin_max" is the exchange's: it goes back to its default with every close.
+static void xchg_close(mbb_ctx *c)
+{
+    c->x.close();
+    c->opt.xchg_spin_max = mbbopt::Options().xchg_spin_max;
+}
+
 extern "C" int mbb_xchg_open(mbb_ctx *c, int nranks, int rank, int max_rows, unsigned char handle[64])
 {
     int rc = use(c);
@@ -4093,7 +4053,7 @@ extern "C" int mbb_xchg_open(mbb_ctx *c, int nranks, int rank, int max_rows, uns
     const char *what = "hipMemset(c->x.base, 0, bytes)";
     if (e == hipSuccess) { e = hipDeviceSynchronize(); what = "hipDeviceSynchronize()"; }
     if (e == hipSuccess) { e = hipIpcGetMemHandle(&h, c->x.base.d()); what = "hipIpcGetMemHandle"; }
-    if (e != hipSuccess) { c->x.close(); return fail(MBB_ERR_HIP, what, e); }
+    if (e != hipSuccess) { xchg_close(c); return fail(MBB_ERR_HIP, what, e); }
     memcpy(handle, &h, 64);
     c->x.n = nranks; c->x.rank = rank; c->x.cap_rows = (size_t)max_rows; c->x.connected = 0; c->x.seq = 0;
     c->x.peer[rank] = c->x.base.d();
@@ -4128,7 +4088,7 @@ extern "C" int mbb_xchg_close(mbb_ctx *c)
     if (rc) return rc;
     if (c->x.users > 0) return fail(MBB_ERR_STATE, "a sampler still lives in the exchange buffer (mbb_sampler_destroy first)");
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->x.close();
+    xchg_close(c);
     return MBB_OK;
 }
 
@@ -4213,7 +4173,7 @@ extern "C" int mbb_lnlike_allgather(mbb_ctx *c, const double *pars, int n, doubl
         if ((rc = grow(c, c->gather.d, cap)) || (rc = grow(c, c->gather.h, cap))) return rc;
     }
     const size_t nbytes = (size_t)n * 5 * sizeof(double);
-    const bool push = c->opt_zero_copy && c->opt_bar_params && c->bnd.w_pars.d();
+    const bool push = c->opt.zero_copy && c->opt.bar_params && c->bnd.w_pars.d();
     double *dp;
     int32_t *ds;
     if (push) {
@@ -4222,18 +4182,18 @@ extern "C" int mbb_lnlike_allgather(mbb_ctx *c, const double *pars, int n, doubl
         dp = c->bnd.w_pars.d();
     } else {
         memcpy(c->bnd.h_pars.h(), pars, nbytes);
-        if (c->opt_zero_copy) dp = c->bnd.h_pars.dv();
+        if (c->opt.zero_copy) dp = c->bnd.h_pars.dv();
         else {
             HIPCHK(hipMemcpyAsync(c->bnd.d_pars.d(), c->bnd.h_pars.h(), nbytes, hipMemcpyHostToDevice, c->stream));
             dp = c->bnd.d_pars.d();
         }
     }
-    ds = c->opt_zero_copy ? c->bnd.h_status.dv() : c->bnd.d_status.d();
+    ds = c->opt.zero_copy ? c->bnd.h_status.dv() : c->bnd.d_status.d();
     double *mine = c->gather.d.d() + (size_t)rank * n;
     if ((rc = launch_rows(c, dp, n, mine, ds, nullptr))) return rc;
     if ((rc = mbb_allgather_f64(c, mine, c->gather.d.d(), n))) return rc;
     HIPCHK(hipMemcpyAsync(c->gather.h.h(), c->gather.d.d(), total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (!c->opt_zero_copy)
+    if (!c->opt.zero_copy)
         HIPCHK(hipMemcpyAsync(c->bnd.h_status.h(), c->bnd.d_status.d(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if ((rc = wait_stream(c))) return rc;
     memcpy(all, c->gather.h.h(), total * sizeof(double));

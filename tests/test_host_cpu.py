@@ -938,15 +938,69 @@ def test_resident_forms_protocol_model():
             FA.run(ix, lib, n2, 1, 10, random.Random(1), ahead=ahead, guard=False, partner=avoid0, stall=(0, 4, 20000))
 
 
-def test_every_option_is_documented_in_the_header():
-    """mbb_set_option's names (the strcmp chain in mbb_hip.hip) all appear in include/mbb_hip.h."""
+def test_every_option_is_documented_in_the_header(tmp_path):
+    """The option table of mbb_emcee_amd/csrc/mbb_options.h, held to its own rules by tests/options_main.cpp (a program of
+    its own built with AddressSanitizer and UBSan and run directly: defaults, a value into its field and no other, the
+    bounds, LONG_MIN and LONG_MAX, names that are not options), and the two tables of include/mbb_hip.h held to the code:
+    the header's options are the 32 the program prints, each with its default and its range; its info keys are the 38 of
+    mbb_get_info's table in mbb_hip.hip; every name is quoted in the header."""
     import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "mbb_emcee_amd", "csrc", "mbb_hip.hip")).read()
-    hdr = open(os.path.join(root, "include", "mbb_hip.h")).read()
-    opts = set(re.findall(r'!strcmp\(name, "([a-z_0-9]+)"\)\) c->opt', src))
-    assert len(opts) >= 20
-    assert [o for o in sorted(opts) if '"%s"' % o not in hdr] == []
+    import shutil
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    libs = [subprocess.check_output([gxx, "-print-file-name=" + n]).decode().strip() for n in ("libasan.so", "libubsan.so")]
+    if not all(os.path.isabs(p) and os.path.exists(p) for p in libs):
+        pytest.skip("g++'s sanitizer runtimes are not installed")
+    exe = str(tmp_path / "options_main")
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "options_main.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    text = out.stdout.decode(errors="replace")
+    assert out.returncode == 0 and "OPTIONS_OK 32 options" in text, text[-3000:]
+    # the table as the code has it: name -> (default, lowest, highest), None for no bound
+    printed = subprocess.run([exe, "table"], stdout=subprocess.PIPE, check=True, timeout=120).stdout.decode().splitlines()
+    code = {}
+    for line in printed:
+        name, default, low, high = line.split()
+        assert name not in code
+        code[name] = (int(default), None if low == "-" else int(low), None if high == "-" else int(high))
+    assert len(code) == len(printed) == 32
+    # the header's two tables: the lines between a table's heading and the next line that is not a row
+    hdr = open(os.path.join(ROOT, "include", "mbb_hip.h")).read()
+
+    def rows(heading, pattern):
+        body = hdr[hdr.index(heading):].split("\n")[1:]
+        assert re.fullmatch(r" \*\s*", body[0]) and re.fullmatch(r" \*   name +.*meaning", body[1]), body[:2]
+        got = []
+        for line in body[2:]:
+            if not line.startswith(' *   "'):
+                break
+            m = re.fullmatch(pattern, line)
+            assert m, line
+            got.append(m.groups())
+        return got
+    documented = {}
+    for name, default, rng, meaning in rows(" * tests/test_host_cpu.py holds this one to: csrc/mbb_options.h.",
+                                            r' \*   "([a-z_0-9]+)" +(-?\d+) +(any|>= -?\d+|-?\d+ \.\. -?\d+) +(\S.*)'):
+        assert name not in documented
+        low, high = (None, None) if rng == "any" else (int(rng[3:]), None) if rng.startswith(">=") else map(int, rng.split(" .. "))
+        documented[name] = (int(default), low, high)
+    assert sorted(set(code) - set(documented)) == [] and sorted(set(documented) - set(code)) == []
+    assert {n: (code[n], documented[n]) for n in code if code[n] != documented[n]} == {}
+    # the info keys: mbb_get_info's table in the source against the header's
+    src = open(os.path.join(ROOT, "mbb_emcee_amd", "csrc", "mbb_hip.hip")).read()
+    table = src[src.index("static const InfoRow kInfo[] = {"):]
+    table = table[:table.index("};")]
+    keys = re.findall(r'^    INFO\("([a-z_0-9]+)", ', table, re.M)
+    assert len(keys) == len(set(keys)) == 38 and len(keys) == table.count("INFO(")
+    info = [name for name, meaning in rows(" * Info keys (mbb_get_info); any other name is MBB_ERR_ARG.",
+                                           r' \*   "([a-z_0-9]+)" {2,}(\S.*)')]
+    assert len(info) == len(set(info))
+    assert sorted(set(keys) - set(info)) == [] and sorted(set(info) - set(keys)) == []
+    # and no row of either kind anywhere else in the header
+    assert len(re.findall(r'^ \*   "[a-z_0-9]+" ', hdr, re.M)) == 32 + 38
+    assert [n for n in sorted(set(code) | set(keys)) if '"%s"' % n not in hdr] == []
 
 
 def test_fastcall_extension_with_a_stand_in_for_the_native_call():
