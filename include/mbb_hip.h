@@ -46,7 +46,8 @@ enum mbb_row_status {
     MBB_ROW_BAD_ALPHA = 2,    /* alpha <= 0          modified_blackbody.py:219 */
     MBB_ROW_BAD_BETA = 3,     /* beta < 0            modified_blackbody.py:222 */
     MBB_ROW_NOCONV = 6,       /* merge / peak root not found                 */
-    MBB_ROW_NONFINITE = 7     /* NaN/inf parameter: lnL = NaN, as the reference */
+    MBB_ROW_NONFINITE = 7     /* NaN/inf parameter: lnL = NaN, as the reference; for the SED-level and chain
+                               * calls also a row whose h/kT or normalisation is not finite (T = 0)   */
 };
 
 const char *mbb_last_error(void);

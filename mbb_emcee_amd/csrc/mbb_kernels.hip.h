@@ -1445,6 +1445,12 @@ __global__ void k_prologue(const double *pars, int n, double nunorm, double lnun
     if (finite5(p5))
         st = sed_prologue<OPTHIN, NOALPHA, false>(T, beta, alpha, fnorm, m_log(T),
                                                   OPTHIN ? 0.0 : m_log(lambda0), nunorm, lnunorm, s);
+    // a row whose scalars come out non-finite is reported, not used (mbb_math.hip.h, m_div): T = 0 makes h/kT infinite,
+    // and the optically thin normalisation then comes out as 0 -- finite band fluxes of 0 with status 0 otherwise
+    if (st == ROW_OK && !(fabs(s.hokt9) <= 1.7976931348623157e308 && fabs(s.normfac) <= 1.7976931348623157e308)) {
+        st = ROW_NONFINITE;
+        s.normfac = s.xmerge = s.kappa = s.hcokt = nan;
+    }
     double peak = nan;
     WalkerK k;
     k.status = st;

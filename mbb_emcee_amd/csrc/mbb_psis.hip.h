@@ -33,6 +33,7 @@ constexpr int kTailMax = 4096;        // the longest tail one workgroup sorts in
 constexpr int kGridMax = 30 + 64;     // m = 30 + floor(sqrt(M)) at M = kTailMax
 constexpr double kDblMax = 1.7976931348623157e308;
 constexpr double kLn2Pi = 1.8378770664093454836;     // ln(2 pi)
+constexpr double kInv2PiHi = 0x1.45f306dc9c883p-3, kInv2PiLo = -0x1.6b01ec5417056p-57;     // 1 / (2 pi) = hi + lo
 constexpr double kSqrtHalf = 0.70710678118654752440;
 
 // why a call did without the Pareto fit (ps_combine's return; 0: it did not)
@@ -143,7 +144,13 @@ PS_HD void ps_lse_merge(double &m, double &s, double m2, double s2)
 PS_HD void ps_lse_add(double &m, double &s, double v) { ps_lse_merge(m, s, v, 1.0); }
 PS_HD double ps_lse_value(double m, double s) { return s == 0.0 ? -INFINITY : m + log(s); }
 
-// the pointwise term from g_b = (Lambda r)_b and Lambda_bb
-PS_HD double ps_ll(double g, double lam) { return 0.5 * (log(lam) - kLn2Pi) - 0.5 * (g * g) / lam; }
+// the pointwise term from g_b = (Lambda r)_b and Lambda_bb.  Its constant is log(lam / 2 pi) / 2 with the quotient kept to
+// twice the working precision (p + e), not log(lam) - log(2 pi): where Lambda_bb is next to 2 pi -- an uncertainty of 0.4 --
+// that difference cancels and keeps the absolute error of log(lam), hundreds of ulps of what is left.
+PS_HD double ps_ll(double g, double lam)
+{
+    const double p = lam * kInv2PiHi, e = fma(lam, kInv2PiHi, -p) + lam * kInv2PiLo;
+    return 0.5 * (log(p) + e / p) - 0.5 * (g * g) / lam;
+}
 
 }   // namespace mbbps

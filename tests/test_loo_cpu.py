@@ -192,6 +192,19 @@ def test_ll_is_the_definition(H):
     assert abs(H.ln2pi - np.log(2 * np.pi)) < 1e-15
 
 
+def test_ll_constant_where_lambda_is_next_to_2_pi(H):
+    """The constant of ll, log(Lambda / 2 pi) / 2, keeps its RELATIVE accuracy where it is small: _loo_ref.ll_bound
+    allows 2 eps of it, and formed as (log Lambda - log 2 pi) / 2 it kept log's absolute error instead -- 1e-15 of the
+    -0.0026 at Lambda = 6.25 on the host, 1.4e-14 on the device, where tests/test_domain_paths_gpu.py found it (an
+    uncertainty of 0.4 mJy).  Against mpmath at 40 digits."""
+    import mpmath
+    with mpmath.workdps(40):
+        for lam in (6.25, 6.0, 6.28, 6.2831853, 6.283185307179586, 6.3, 7.0, 1.0 / 0.41 ** 2, 3.2, 12.5):
+            want = mpmath.log(mpmath.mpf(lam) / (2 * mpmath.pi)) / 2
+            got = H.lib.ps_host_ll(0.0, lam)
+            assert abs(mpmath.mpf(got) - want) <= 2 * EPS * abs(want), (lam, got, float(want))
+
+
 # ---------------------------------------------------------------- 3. the reference on a toy of known answer
 def test_reference_on_a_linear_gaussian_toy():
     """y = a theta + e, e ~ N(0, C) with three correlated bands, a Gaussian prior on theta (so that no single band carries
