@@ -465,18 +465,23 @@ __device__ inline double sed_peak_wave(double T, double beta, double lx0, double
     return hcokt / xp;
 }
 
+// An exponent of the sample loop (WalkerK::beta, ::alpha) as every record carries it: beyond 1e80 it is held there.  The
+// sample loop multiplies it by a logarithm, and the product must stay below 1e90 for its exp (mbb_math.hip.h,
+// reduce_ln2_256) -- which gives 0, 1 or inf for such powers whatever the exponent's exact size.
+__device__ __forceinline__ double held_exponent(double e)
+{
+    return fmin(e, 1.0e80);
+}
+
 template <bool OPTHIN, bool NOALPHA>
 __device__ inline void make_walker_k(double beta, double alpha, const SedScalars &s, WalkerK &w)
 {
     w.hokt9 = s.hokt9;
     w.lhokt9 = s.lhokt9;
-    // (exponents beyond 1e80 are held there: the sample loop multiplies them by a logarithm, and the product must stay
-    // below 1e90 for its exp (mbb_math.hip.h, reduce_ln2_256) -- which gives 0, 1 or inf for such powers whatever the
-    // exponent's exact size)
-    w.beta = fmin(beta, 1.0e80);
+    w.beta = held_exponent(beta);
     w.bp3 = beta + 3.0;
     w.cq = s.normfac * (s.hokt9 * s.hokt9);
-    w.alpha = NOALPHA ? 0.0 : fmin(alpha, 1.0e80);
+    w.alpha = NOALPHA ? 0.0 : held_exponent(alpha);
     w.lx0 = OPTHIN ? 0.0 : s.lx0;
     w.xmerge = NOALPHA ? __builtin_inf() : s.xmerge;
     w.cbb = s.normfac;

@@ -176,8 +176,8 @@ __global__ void __launch_bounds__(1024) k_serve(const LikeArgs a)
                     WalkerK k0;
                     k0.hokt9 = m_div(1e9 * kH / kK, p[0]);
                     k0.lhokt9 = kLog1e9HoK - lT;
-                    k0.beta = p[1]; k0.bp3 = p[1] + 3.0; k0.cq = 0.0;
-                    k0.alpha = NOALPHA ? 0.0 : p[3];
+                    k0.beta = held_exponent(p[1]); k0.bp3 = p[1] + 3.0; k0.cq = 0.0;
+                    k0.alpha = NOALPHA ? 0.0 : held_exponent(p[3]);
                     k0.lx0 = OPTHIN ? 0.0 : k0.lhokt9 + kLogUmToGHz - lL;
                     k0.xmerge = __builtin_inf();
                     k0.cbb = k0.cpl = k0.kap = k0.peak = 0.0;

@@ -10,7 +10,12 @@ lir_reference) only: nothing here touches the device.
                     SED's two kinks, with its own error estimate
     RANGES          the three integration ranges [um]: rest-frame L_IR, the same seen at z = 2.3, and a narrow one
     device_rule     the device's fixed rule (csrc/mbb_kernels.hip.h, sed_integrate_row) restated in numpy
-tests/test_domain_paths_cpu.py asserts what the GPU tests of tests/test_domain_paths_gpu.py rely on.
+    make_like, make_oracle   the likelihood of either set (built without a device) and the oracle's of what it holds
+    huge_rows()     beta, alpha or both at 1e79 to 1e300 in three good rows
+    ensemble(name)  the frozen starting ensembles of the sampler tests: wide250, wide576, grid224
+    stretch_draws, proposals, accept_margin, emulate   the device sampler's draws, proposal and accept rule in numpy
+tests/test_domain_paths_cpu.py asserts what the GPU tests of tests/test_domain_paths_gpu.py rely on,
+tests/test_domain_sampler_cpu.py what tests/test_domain_sampler_gpu.py and tests/test_domain_boundary_gpu.py do.
 """
 import numpy as np
 
@@ -77,6 +82,180 @@ def with_bad_rows():
     rows[is_bad] = bad
     rows[~is_bad] = wide
     return rows, np.flatnonzero(~is_bad)
+
+
+# ---------------------------------------------------------------- the boundary call and the sampler forms
+LOWLIM = np.array([1.0, 0.1, 1.0, 0.1, 1e-3])     # the likelihood's default lower limits: a row below one has lnprob -inf
+PEAK_PRIOR = (120.0, 40.0)                         # the lambda_peak Gaussian prior of the wide test: (mean, sigma)
+GRID_LAMBDA0_UPLIM = 5000.0
+HUGE = (1e79, 1e80, 1e81, 1e100, 1e300)
+SOURCE_SCALES = (1.0, 0.3, 4.0)                    # the multi-source call's three sources: WIDE_FLUX (GRID_FLUX) times these
+SEED = 77
+STEPS = (8, 3, 2)                                  # stored, then unstored, then stored again
+GOLDEN_GAMMA = 0x9E3779B97F4A7C15                  # the step's number times this is added to the seed: the step's key
+
+
+def make_like(mbb, which, opthin, noalpha, cov=None, prior=None, scale=1.0):
+    """The likelihood of the wide test's five bands or of the grid test's six (`which` wide or grid), response=True,
+    the data of those tests: the grid with lambda0's upper limit at 5000 um, the wide set with the lambda_peak prior
+    unless `prior` says otherwise; `cov` a full covariance or None; `scale` times the fluxes (and unc_of those).  No device
+    is touched until it is evaluated."""
+    names, flux = (GRID_BANDS, GRID_FLUX * scale) if which == "grid" else (WIDE_BANDS, WIDE_FLUX * scale)
+    like = mbb.likelihood(opthin=opthin, noalpha=noalpha, response=True)
+    like.set_phot(names, flux, unc_of(flux))
+    if which == "grid":
+        like.set_uplim("lambda0", GRID_LAMBDA0_UPLIM)                  # (3 x max wavelength would cut the grid short)
+    if which != "grid" if prior is None else prior:
+        like.set_gaussian_prior("lambda_peak", *PEAK_PRIOR)
+    if cov is not None:
+        like.set_cov(cov)
+    return like
+
+
+def make_oracle(oracle, like, flux=None):
+    """The oracle's likelihood of what `like` holds: its passband tables, limits, priors and covariance; `flux` another
+    source's data through the same bands (with unc_of its uncertainties; diagonal only)."""
+    bands = [(r.wavelength, r._sedmult, r._normfac) for r in like._responses]
+    has_g = [int(b) for b in like._has_gprior]
+    kw = dict(bands=bands, opthin=like.opthin, noalpha=like.noalpha, wavenorm=like.wavenorm, lowlim=like.lowlims,
+              has_uplim=[int(b) for b in like.has_uplims], uplim=like.uplims, has_gprior=has_g,
+              gprior_mean=list(like._gprior_mean), gprior_sigma=[s if h else 1.0 for s, h in zip(like._gprior_sigma, has_g)])
+    if flux is not None:
+        return oracle.OracleLikelihood(flux, unc_of(flux), **kw)
+    cov = like._covmatrix if like._has_covmatrix else None
+    return oracle.OracleLikelihood(like._flux, like._flux_unc, cov=cov, **kw)
+
+
+# Good rows to put the huge exponents into.  What (x_norm / x0)^beta = (lambda0 / wavenorm)^beta does at the normalisation
+# decides whether an optically thick SED with such a beta can be built at all: 0 below the normalisation wavelength of
+# 500 um (no SED: the normalisation divides by it), infinite above it (a SED: 1 - e^-y is 1 there, and the optical-depth
+# factor a step at lambda0).  The optically thin normalisation has x_norm^-(3 + beta), x_norm = 28.78 K / T: both sides
+# of T = 28.78 K.  So: lambda0 on both sides of 500 um, T on both sides of 28.78 K.
+HUGE_BASE = np.array([[25.0, 1.7, 180.0, 2.2, 35.0], [25.0, 1.7, 600.0, 2.2, 35.0], [40.0, 1.7, 600.0, 2.2, 35.0]])
+
+
+def huge_rows():
+    """Each row of HUGE_BASE with beta, alpha, or both at each of HUGE: 45 rows, and what was set in each."""
+    rows, what = [], []
+    for good in HUGE_BASE:
+        for v in HUGE:
+            for name, cols in (("beta", [1]), ("alpha", [3]), ("beta and alpha", [1, 3])):
+                r = good.copy()
+                r[cols] = v
+                rows.append(r)
+                what.append("T %g, lambda0 %g: %s = %g" % (good[0], good[2], name, v))
+    return np.ascontiguousarray(rows), what
+
+
+def wide_finite(n):
+    """The first n wide rows at or above every lower limit: the rows whose lnprob is finite, whatever the model (the
+    gate reads all five columns; tests/test_domain_sampler_cpu.py asserts that the oracle agrees, model by model)."""
+    rows = wide_rows()
+    keep = np.flatnonzero(~(rows < LOWLIM).any(axis=1))
+    assert keep.size >= n, (keep.size, n)
+    return np.ascontiguousarray(rows[keep[:n]])
+
+
+def ensemble(name):
+    """The frozen starting ensembles of the sampler tests: `wide250`, `wide576`, `grid224`."""
+    if name.startswith("wide"):
+        return wide_finite(int(name[4:]))
+    assert name == "grid224"
+    return np.ascontiguousarray(grid_rows()[:224])
+
+
+def zpow_of(p0):
+    """The exponent of z in the accept test: the columns the ensemble spans, less one (a column that is constant over
+    the ensemble stays so exactly under the stretch move and does not count: mbb_sampler_set_state).  4 for the wide
+    ensembles, 2 for the grid's, whose alpha and fnorm are one value each."""
+    return float(max(int(np.count_nonzero(np.ptp(p0, axis=0) != 0.0)) - 1, 0))
+
+
+_DRAWS = {}
+
+
+def stretch_draws(seed, step_no, nw, a=2.0):
+    """What the device draws for step number `step_no` of the sampler's life (1 for the first step) -- csrc/mbb_stretch.hip.h
+    restated with the arithmetic of tests/test_gpu_parity.py::_host_stretch_step --: for each half (0: the first half moves)
+    z [half], the partner's index in the other half [half], ln u [half].  The draws do not depend on the model: made once."""
+    key = (int(seed), int(step_no), int(nw), float(a))
+    if key not in _DRAWS:
+        from test_gpu_parity import _philox4x32
+        half = nw // 2
+        k = (seed + GOLDEN_GAMMA * step_no) & 0xFFFFFFFFFFFFFFFF
+        out = []
+        for h in range(2):
+            s_begin = half if h else 0
+            zz, pj, lu = np.empty(half), np.empty(half, dtype=np.int64), np.empty(half)
+            for w in range(half):
+                r = _philox4x32([s_begin + w, h, 0, 0], k & 0xFFFFFFFF, k >> 32)
+                u1 = ((r[0] >> 5) * 67108864.0 + (r[1] >> 6)) / 9007199254740992.0
+                u2 = r[2] / 4294967296.0
+                u3 = (r[3] + 0.5) / 4294967296.0
+                zz[w] = ((a - 1.0) * u1 + 1.0) ** 2 / a
+                pj[w] = min(int(u2 * half), half - 1)
+                lu[w] = np.log(u3)
+            for x in (zz, pj, lu):
+                x.setflags(write=False)
+            out.append((zz, pj, lu))
+        _DRAWS[key] = out
+    return _DRAWS[key]
+
+
+def proposals(prev, now_first, seed, step_no):
+    """The stretch move's proposals of one step from positions that are given, not emulated: `prev` [nw, 5] the ensemble
+    before the step, `now_first` [nw / 2, 5] its first half after the step's first half-step (the second half draws its
+    partners there).  With the device's one rounding: it forms fma(-z, c - s, c), so c - s is rounded to double and the
+    product and the sum are carried in long double (two roundings in double are 1.7e-13 off where c and z (c - s) nearly
+    cancel).  Returns (q [nw, 5], z [nw], ln u [nw])."""
+    nw = prev.shape[0]
+    half = nw // 2
+    LD = np.longdouble
+    (z0, j0, u0), (z1, j1, u1) = stretch_draws(seed, step_no, nw)
+    q = np.empty((nw, 5))
+    for mine, c, z in ((slice(0, half), prev[half + j0], z0), (slice(half, nw), now_first[j1], z1)):
+        d = c - prev[mine]
+        q[mine] = (c.astype(LD) - z[:, None].astype(LD) * d.astype(LD)).astype(np.float64)
+    return q, np.concatenate([z0, z1]), np.concatenate([u0, u1])
+
+
+def accept_margin(zpow, z, lnu, new, old):
+    """(m, decidable): m = zpow ln z + new - old - ln u, the move is made iff m > 0; decidable where |m| exceeds
+    2e-10 (max(1, |new|) + max(1, |old|)), twice the bound lnprob is held to on each side.  A proposal at -inf is
+    decidable: it is rejected."""
+    with np.errstate(invalid="ignore"):
+        m = zpow * np.log(z) + new - old - lnu
+        tol = 2e-10 * (np.maximum(1.0, np.abs(new)) + np.maximum(1.0, np.abs(old)))
+        decidable = np.isneginf(new) | (np.abs(m) > tol)
+    return m, decidable
+
+
+def emulate(lnprob, p0, seed, nsteps, steps_done=0):
+    """The stretch-move sampler on the host with the device's draws and `lnprob` (rows -> values) as the likelihood.
+    Returns the chain [nw, nsteps, 5], its lnprob [nw, nsteps], which moves were made [nw, nsteps] and which of them
+    were decidable [nw, nsteps]."""
+    nw = p0.shape[0]
+    half = nw // 2
+    zpow = zpow_of(p0)
+    pos, lnp = p0.copy(), lnprob(p0)
+    assert np.all(np.isfinite(lnp))
+    chain, lnps = np.empty((nw, nsteps, 5)), np.empty((nw, nsteps))
+    moved, decid = np.zeros((nw, nsteps), dtype=bool), np.zeros((nw, nsteps), dtype=bool)
+    for t in range(nsteps):
+        draws = stretch_draws(seed, steps_done + t + 1, nw)
+        for h, (zz, pj, lu) in enumerate(draws):
+            mine = slice(half, nw) if h else slice(0, half)
+            c = pos[(0 if h else half) + pj]
+            q = c - zz[:, None] * (c - pos[mine])
+            new = lnprob(q)
+            assert not np.isnan(new).any(), q[np.isnan(new)]
+            m, d = accept_margin(zpow, zz, lu, new, lnp[mine])
+            acc = m > 0
+            pos[mine] = np.where(acc[:, None], q, pos[mine])
+            lnp[mine] = np.where(acc, new, lnp[mine])
+            moved[mine, t], decid[mine, t] = acc, d
+        chain[:, t], lnps[:, t] = pos, lnp
+    return chain, lnps, moved, decid
 
 
 def lir_rows():

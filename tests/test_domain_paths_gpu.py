@@ -29,7 +29,8 @@ Bounds, and where they come from:
   * dust mass: relative 1e-13 of oracle.post_dustmass; a row beyond it is decided by 50 digits
     (_summary_ref.dustmass_mp), as tests/test_summary_derived_gpu.py::_check_dust_entries does;
   * status words, NaN places and everything said to be "the same bits": exact.
-No sampler, no served call and no resident kernel is used here."""
+No sampler, no served call and no resident kernel is used here: the boundary call's three ways and the multi-source call
+over the same rows are tests/test_domain_boundary_gpu.py's, the device sampler's forms tests/test_domain_sampler_gpu.py's."""
 import numpy as np
 import pytest
 
