@@ -670,6 +670,79 @@ int mbb_chain_evidence(mbb_ctx *ctx, const double *chain, const double *lnprob, 
                        const mbb_evidence_spec *spec, const mbb_evidence_out *out);
 int mbb_sampler_evidence(mbb_ctx *ctx, void *sampler, const mbb_evidence_spec *spec, const mbb_evidence_out *out);
 
+/* ---- a chain reweighted under another density: Pareto-smoothed importance weights and weighted statistics ---- */
+/* New: the reference has nothing comparable.  What the posterior of a chain would look like under the density of
+ * another context, the TARGET -- other priors or limits, a measurement more or less, another model variant -- without
+ * running the sampler again (csrc/mbb_reweight.hip.h; the step logic is csrc/mbb_psis.hip.h and csrc/mbb_rwsteps.hip.h).
+ * Per source over a summary's window: steps burn, burn + thin, ... of every walker, entries j = 0 .. n - 1 in
+ * [walker][step] order, n = nw nkept <= MBB_PW_MAX_WINDOW (a larger window is MBB_ERR_ARG, as for the out-of-sample fit).
+ *   densities  lp_j is the chain's stored lnprob; lq_j the target's lnprob of row theta_j, mbb_lnlike_batch_device's bit
+ *              for bit; r_j = lq_j - lp_j, one IEEE subtraction.
+ *   classes    an entry is USED when r_j is finite; ZERO when lp_j is finite and lq_j = -inf (the target excludes the
+ *              point: weight 0, counted in n_zero); LEFT OUT otherwise (lp_j not finite, lq_j NaN or +inf, a row the SED
+ *              constructor fails on: counted in n_left_out, MBB_SUM_HAS_NAN, and the row's status bit from
+ *              MBB_SUM_ROW_SHIFT on).  S = used entries, N = S + n_zero.
+ *   weights    lw is the out-of-sample fit's PSIS recipe with -r in the place of ll: lw = r - max r over the used
+ *              entries, M = ceil(min(0.2 S, 3 sqrt S)), the cutoff by the summary's exact select, the M tail entries in
+ *              (lw, window index) order, the generalised Pareto fit and the smoothed tail capped at 0, the fallbacks
+ *              MBB_RW_TAIL_SHORT and MBB_RW_TAIL_FLAT (raw weights, k^ = +inf).  smooth == 0 keeps the raw weights of
+ *              every entry; k^ is still the fit's.
+ *   scalars    khat, tail_len = M;  ess = (sum e^lw)^2 / sum e^2lw;
+ *              lnz_ratio = max r + ln sum e^lw - ln N, an estimate of ln(Z_target / Z_run): added to an evidence's lnz
+ *              it gives the target's.  -inf when every entry is zero.
+ *   integers   u_j = floor(e^lw_j 2^32 + 1/2) in [0, MBB_RW_WEIGHT_ONE], 0 for an entry that is not used; U = sum u_j
+ *              < 2^53, exact as an integer and as a double.  Every accumulation of weights is an integer one.
+ *   columns    per column slot 0 .. 7 of a summary (the derived columns by the summary's own fill, from spec->summary,
+ *              with the TARGET's model):  mean = sum u_j x_j / U;  the weighted quantile at percent p is the smallest
+ *              sample value x with sum_{x_j <= x} u_j >= t, t = (uint64) ceil((p / 100.0) (double) U) clamped to
+ *              [1, U] -- the "inverted CDF" (Hyndman & Fan 1) with weights, NOT the summary's "linear" rule; with equal
+ *              weights it is numpy.quantile(..., method="inverted_cdf").  It is found by a weighted radix select: eight
+ *              passes of 256-bin histograms of sums of u.  A column holding a NaN among its used entries has NaN mean
+ *              and quantiles and MBB_SUM_HAS_NAN in col_status.
+ *   per source cov = sum u_j d d^T / U about the weighted means, d the five parameters: no ddof correction (the weights
+ *              are not counts).  best: the used entry of largest lq, the first in [walker][step] order among equals.
+ * With no used entry the statistics are NaN and best_index -1 (MBB_SUM_EMPTY; MBB_RW_ALL_ZERO when every entry that
+ * is not left out is zero).  Every floating-point sum has a fixed order: the same chain gives the same bits.
+ * The target's number of sources is the chain's, or 1 (one density for all).  Its model variant may differ from the
+ * run's: the five columns keep their meaning.  The summary spec's clips are ignored.  Every work buffer is the target's.
+ * Refused before anything is allocated, uploaded or launched: null arguments, a target on another device, a sharded
+ * context (MBB_ERR_STATE), wrong sources, a window above MBB_PW_MAX_WINDOW, more than MBB_SUMMARY_MAX_PCT percentiles,
+ * bad burn / thin, no resident chain (MBB_ERR_STATE). */
+#define MBB_RW_WEIGHT_ONE 4294967296ll     /* u of lw = 0: 2^32                                                 */
+enum mbb_reweight_status {                 /* [nsrc]; beside the mbb_summary_status bits EMPTY, HAS_NAN (entries left out), ROW_SHIFT */
+    MBB_RW_K_HIGH = 16,                    /* k^ > 0.7 (a fallback's +inf included)                            */
+    MBB_RW_TAIL_SHORT = 32,
+    MBB_RW_TAIL_FLAT = 64,
+    MBB_RW_HAS_ZERO = 128,                 /* n_zero > 0                                                       */
+    MBB_RW_ALL_ZERO = 65536                /* no used entry and n_zero > 0: the statistics are NaN, lnz_ratio -inf */
+};
+typedef struct mbb_reweight_spec {
+    int32_t smooth;                        /* 0: raw weights                                                   */
+    const mbb_summary_spec *summary;       /* the window, the percentiles, the derived columns and redshifts   */
+} mbb_reweight_spec;
+/* Where the results go: host memory of the caller's.  The four per-entry arrays may be NULL. */
+typedef struct mbb_reweight_out {
+    int64_t *n_used, *n_zero, *n_left_out, *weight_sum;     /* [nsrc]; weight_sum = U                          */
+    double *khat, *ess, *lnz_ratio;        /* [nsrc]                                                          */
+    double *mean;                          /* [nsrc][8]                                                       */
+    double *pct;                           /* [nsrc][8][npct]                                                 */
+    double *cov;                           /* [nsrc][5][5]                                                    */
+    double *best;                          /* [nsrc][6]: the parameters and lq                                */
+    int32_t *tail_len, *status;            /* [nsrc]                                                          */
+    int32_t *col_status;                   /* [nsrc][8]: mbb_summary_status bits                              */
+    int32_t *best_index;                   /* [nsrc][2]: walker, step                                         */
+    double *target_lnprob, *log_ratio, *log_weight;         /* [nsrc][n] in window order, or NULL; lw is -inf where not used */
+    int64_t *weight;                       /* [nsrc][n] u_j, or NULL                                          */
+} mbb_reweight_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5] with its lnprob [nsrc][nw][nsteps]. */
+int mbb_chain_reweight(mbb_ctx *target, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                       const mbb_reweight_spec *spec, const mbb_reweight_out *out);
+/* The same of the chain the sampler's last stored or summarised run left on the device.  ctx owns the sampler and the
+ * chain; target may be ctx or another context of this process on the same device.  ctx's stream is synchronised before
+ * the target's first launch, the target's before the call returns. */
+int mbb_sampler_reweight(mbb_ctx *ctx, void *sampler, mbb_ctx *target, const mbb_reweight_spec *spec,
+                         const mbb_reweight_out *out);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

@@ -21,6 +21,7 @@ from .goodness import chain_goodness, ChainGoodness
 from .optimize import map_fit, MapFit
 from .evidence import chain_evidence, ChainEvidence
 from .loo import chain_loo, loo_rows, ChainLoo
+from .reweight import chain_reweight, ChainReweight
 
 __version__ = "0.1.0"
 __all__ = ["response", "response_set", "modified_blackbody", "alpha_merge_eqn", "isiterable", "likelihood",
@@ -28,4 +29,5 @@ __all__ = ["response", "response_set", "modified_blackbody", "alpha_merge_eqn", 
            "chain_diagnostics", "ChainDiagnostics", "chain_marginals", "ChainMarginals",
            "chain_predictions", "ChainPredictions", "chain_draws", "draw_indices", "ChainDraws",
            "chain_goodness", "ChainGoodness", "map_fit", "MapFit",
-           "chain_evidence", "ChainEvidence", "chain_loo", "loo_rows", "ChainLoo"]
+           "chain_evidence", "ChainEvidence", "chain_loo", "loo_rows", "ChainLoo",
+           "chain_reweight", "ChainReweight"]

@@ -120,6 +120,23 @@ class PointwiseOut(C.Structure):
                 ("elpd_loo", _dp), ("p_loo", _dp), ("khat", _dp), ("loo_pit", _dp)]
 
 
+RW_WEIGHT_ONE = 1 << 32
+RW_K_HIGH, RW_TAIL_SHORT, RW_TAIL_FLAT, RW_HAS_ZERO, RW_ALL_ZERO = 16, 32, 64, 128, 65536
+
+
+class ReweightSpec(C.Structure):
+    """mbb_reweight_spec (include/mbb_hip.h)"""
+    _fields_ = [("smooth", C.c_int32), ("summary", C.POINTER(SummarySpec))]
+
+
+class ReweightOut(C.Structure):
+    """mbb_reweight_out (include/mbb_hip.h)"""
+    _fields_ = [("n_used", _lp), ("n_zero", _lp), ("n_left_out", _lp), ("weight_sum", _lp),
+                ("khat", _dp), ("ess", _dp), ("lnz_ratio", _dp), ("mean", _dp), ("pct", _dp), ("cov", _dp), ("best", _dp),
+                ("tail_len", _ip), ("status", _ip), ("col_status", _ip), ("best_index", _ip),
+                ("target_lnprob", _dp), ("log_ratio", _dp), ("log_weight", _dp), ("weight", _lp)]
+
+
 MAP_MAX_STARTS, MAP_MAX_ITER = 64, 1000
 MAP_CONVERGED_F, MAP_CONVERGED_X, MAP_MAXITER, MAP_START_INVALID, MAP_COV_SINGULAR, MAP_ALL_FIXED = 1, 2, 4, 8, 16, 32
 MAP_STENCIL_FAILED = 64
@@ -225,6 +242,9 @@ SIGNATURES = {
     "mbb_chain_evidence": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(EvidenceSpec),
                                      C.POINTER(EvidenceOut)]),
     "mbb_sampler_evidence": (C.c_int, [_vp, _vp, C.POINTER(EvidenceSpec), C.POINTER(EvidenceOut)]),
+    "mbb_chain_reweight": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(ReweightSpec),
+                                     C.POINTER(ReweightOut)]),
+    "mbb_sampler_reweight": (C.c_int, [_vp, _vp, _vp, C.POINTER(ReweightSpec), C.POINTER(ReweightOut)]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

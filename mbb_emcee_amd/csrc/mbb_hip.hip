@@ -38,6 +38,7 @@
 #include "mbb_map.hip.h"
 #include "mbb_evidence.hip.h"
 #include "mbb_pointwise.hip.h"
+#include "mbb_reweight.hip.h"
 #include "mbb_draws.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
@@ -347,6 +348,9 @@ struct mbb_ctx {
     } map;
     struct EvWork { DevBuf mom, ints, slab, l1, l2, postq, neff, outbuf; } ev;  // the evidence of a chain (evidence_run)
     struct PwWork { DevBuf cols, part, state, sel, status, outbuf; } pw;        // the out-of-sample fit of a chain (pw_run)
+    struct RwWork {                                                             // a chain reweighted under this context's density (rw_run)
+        DevBuf slab, cols, count, state, sel, status, wpart, wstate, whist, covpart, entries, outbuf;
+    } rw;
     mbbopt::Options opt;                       // what mbb_set_option sets: every field, default and bound in mbb_options.h
     long last_prepass = 0;                     // whether the last likelihood launch was preceded by k_walker_pre (launch_rows)
     Dev<double> pre;                           // ... its records
@@ -3529,6 +3533,187 @@ extern "C" int mbb_pointwise_rows(mbb_ctx *c, const double *pars, int n, double 
         HIPCHK(hipMemcpyAsync(ll + off * nb, d_ll, (size_t)m * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(status + off, d_status, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         return MBB_OK;
+    });
+}
+
+// ---- a chain reweighted under another density (mbb_reweight.hip.h) -------------
+static_assert(mbbrw::kStKHigh == MBB_RW_K_HIGH && mbbrw::kStTailShort == MBB_RW_TAIL_SHORT &&
+              mbbrw::kStTailFlat == MBB_RW_TAIL_FLAT && mbbrw::kStHasZero == MBB_RW_HAS_ZERO &&
+              mbbrw::kStAllZero == MBB_RW_ALL_ZERO, "the header's status bits are the kernels'");
+static_assert(mbbrw::kStKHigh == mbbpw::kStKHigh && mbbrw::kStTailShort == mbbpw::kStTailShort &&
+              mbbrw::kStTailFlat == mbbpw::kStTailFlat, "the Pareto bits are the out-of-sample fit's");
+static_assert(mbbrw::kMaxPct == MBB_SUMMARY_MAX_PCT && mbbrw::kCols == MBB_SUMMARY_COLS, "the summary's sizes");
+static_assert((long long)mbbrws::kUnit == MBB_RW_WEIGHT_ONE &&(double)MBB_PW_MAX_WINDOW * (double)MBB_RW_WEIGHT_ONE < 9007199254740992.0,
+              "a window's weights sum below 2^53");
+static_assert(mbbps::kTailMax == MBB_PW_TAIL_MAX, "the tail one workgroup sorts");
+
+// The argument checks of a reweighting: before anything is allocated, uploaded or launched.  c is the target.
+static int rw_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_reweight_spec *sp, const mbb_reweight_out *o)
+{
+    if (!sp || !o || !sp->summary || !o->n_used || !o->n_zero || !o->n_left_out || !o->weight_sum || !o->khat || !o->ess ||
+        !o->lnz_ratio || !o->mean || !o->pct || !o->cov || !o->best || !o->tail_len || !o->status || !o->col_status ||
+        !o->best_index)
+        return fail(MBB_ERR_ARG, "null reweight argument");
+    if (sharded_context(c))
+        return fail(MBB_ERR_STATE, "a sharded context cannot reweight a chain: a rank holds only its own walkers' chain");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    if (c->nb <= 0) return fail(MBB_ERR_STATE, "bands not set (mbb_set_bands)");
+    if (c->data_nb != c->nb) return fail(MBB_ERR_STATE, "data not set or band count mismatch");
+    if (nsrc != c->nsrc && c->nsrc != 1)
+        return fail(MBB_ERR_ARG, "the chain's sources must be the target's, or the target hold one source for all");
+    const mbb_summary_spec *ss = sp->summary;
+    int rc;
+    if ((rc = check_percentiles(ss->npct, ss->pct, "1 to 8 percentiles per reweighting"))) return rc;
+    if ((rc = check_window(ss, nsteps))) return rc;
+    const long long n = (long long)nw * kept_steps(ss->burn, ss->thin, nsteps);
+    if (n > MBB_PW_MAX_WINDOW)
+        return fail(MBB_ERR_ARG, "the window's weights would not sum below 2^53, nor its tail fit one workgroup (MBB_PW_MAX_WINDOW entries per source)");
+    if ((rc = check_derived_settings(ss, nsrc))) return rc;
+    if ((unsigned long long)nsrc * (unsigned long long)n / mbbrw::kThreads > 0x7fffffffull) return fail(MBB_ERR_ARG, "too many sources");
+    return check_grid((size_t)nsrc * mbbrw::kCols);
+}
+
+// The chain on the device in emcee's layout, with its lnprob, reweighted under the density of c, the target: every work
+// buffer is c's, every launch on c's stream.  Synchronous; the results land in the caller's arrays.
+static int rw_run(mbb_ctx *c, const double *d_chain, const double *d_lnprob, int nsrc, int nw, int nsteps,
+                  const mbb_reweight_spec *sp, const mbb_reweight_out *o)
+{
+    using namespace mbbrw;
+    int rc;
+    if ((rc = rw_check(c, nsrc, nw, nsteps, sp, o))) return rc;
+    if (!d_lnprob) return fail(MBB_ERR_ARG, "a reweighting needs the chain's lnprob");
+    const mbb_summary_spec *ss = sp->summary;
+    RwArgs a;
+    memset(&a, 0, sizeof a);
+    fill_chain_view(a, d_chain, nsrc, nw, nsteps, ss, 16384);
+    a.lnprob = d_lnprob;
+    a.smooth = sp->smooth != 0;
+    a.npct = ss->npct;
+    for (int k = 0; k < ss->npct; ++k) a.pct[k] = ss->pct[k];
+    const size_t cells = (size_t)nsrc * nw * nsteps, ns = (size_t)nsrc, n = (size_t)a.n, sc = ns * kCols;
+    const size_t ncolumns = ns * a.ncol, np = (size_t)ss->npct;
+    // a slab: entries [k m, (k + 1) m) of every source, [nsrc][m][5] -- the likelihood's multi-source row grouping
+    const size_t m = std::min<size_t>(n, std::max<size_t>(1, (size_t)kSumChunkRows / ns));
+    const size_t srows = ns * m;
+    mbb_ctx::RwWork &w = c->rw;
+    ResultBlock rb;                              // 64-bit counts, doubles, 32-bit words
+    rb.add(&a.o_nused, ns, o->n_used); rb.add(&a.o_nzero, ns, o->n_zero); rb.add(&a.o_nleft, ns, o->n_left_out);
+    rb.add(&a.o_wsum, ns, o->weight_sum);
+    rb.add(&a.o_khat, ns, o->khat); rb.add(&a.o_ess, ns, o->ess); rb.add(&a.o_lnz, ns, o->lnz_ratio);
+    rb.add(&a.o_mean, sc, o->mean); rb.add(&a.o_pct, sc * np, o->pct);
+    rb.add(&a.o_cov, ns * 25, o->cov); rb.add(&a.o_best, ns * 6, o->best);
+    rb.add(&a.o_tail, ns, o->tail_len); rb.add(&a.o_status, ns, o->status); rb.add(&a.o_colstatus, sc, o->col_status);
+    rb.add(&a.o_bestidx, ns * 2, o->best_index);
+    const bool entries = o->target_lnprob || o->log_ratio || o->log_weight || o->weight;
+    if ((rc = grow(c, w.slab, srows * (6 * sizeof(double) + sizeof(int32_t))))) return rc;
+    if ((rc = grow(c, w.cols, cells * 3 * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.count, ns * a.splits * kCountWords * sizeof(unsigned long long)))) return rc;
+    if ((rc = grow(c, w.state, ns * sizeof(RwState)))) return rc;
+    if ((rc = grow(c, w.sel, ns * sizeof(mbbs::ColState)))) return rc;
+    if ((rc = grow_select(c, ns, a.splits))) return rc;
+    if ((rc = grow(c, w.status, ns * sizeof(int)))) return rc;
+    if ((rc = grow(c, w.wpart, ncolumns * a.splits * kWStatWords * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.wstate, ncolumns * sizeof(WColState)))) return rc;
+    if ((rc = grow(c, w.whist, ncolumns * a.splits * kMaxPct * 256 * sizeof(unsigned long long)))) return rc;
+    if ((rc = grow(c, w.covpart, ns * a.splits * kCovWords * sizeof(double)))) return rc;
+    if (entries && (rc = grow(c, w.entries, ns * n * sizeof(double)))) return rc;
+    if ((rc = place(c, w.outbuf, rb))) return rc;
+    a.lqcol = (double *)w.cols.p; a.lwcol = a.lqcol + cells;
+    a.ucol = (unsigned long long *)(a.lwcol + cells);
+    a.count = (unsigned long long *)w.count.p;
+    a.state = (RwState *)w.state.p; a.sel = (mbbs::ColState *)w.sel.p;
+    a.gstatus = (int *)w.status.p;
+    a.wpart = (double *)w.wpart.p; a.wstate = (WColState *)w.wstate.p; a.whist = (unsigned long long *)w.whist.p;
+    a.covpart = (double *)w.covpart.p;
+    Carve sb{(char *)w.slab.p};
+    a.s_rows = sb.take<double>(srows * 5);
+    double *const s_lnl = sb.take<double>(srows);
+    int32_t *const s_status = sb.take<int32_t>(srows);
+    a.s_lnl = s_lnl; a.s_status = s_status;
+    HIPCHK(hipMemsetAsync(w.status.p, 0, ns * sizeof(int), c->stream));
+    // the target's lnprob of the window's rows, a slab at a time
+    for (size_t i0 = 0; i0 < n; i0 += m) {
+        const size_t mm = std::min(m, n - i0), rows = ns * mm;
+        a.i0 = (long long)i0; a.m = (int)mm;
+        const dim3 grid((unsigned)((rows + kThreads - 1) / kThreads));
+        hipLaunchKernelGGL(k_rw_gather, grid, dim3(kThreads), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_rows(c, a.s_rows, (int)rows, s_lnl, s_status, nullptr))) return rc;
+        hipLaunchKernelGGL(k_rw_ratio, grid, dim3(kThreads), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    // the log weights
+    const dim3 gsrc((unsigned)nsrc, (unsigned)a.splits);
+    hipLaunchKernelGGL(k_rw_count, gsrc, dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rw_begin, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rw_shift, gsrc, dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    {
+        // the cutoff, by the summary's select: the lw column as its first derived column
+        mbbs::SumArgs s;
+        memset(&s, 0, sizeof s);
+        static_cast<mbbc::ChainView &>(s) = static_cast<const mbbc::ChainView &>(a);
+        s.ncol = 1; s.col[0] = 5; s.der[0] = a.lwcol; s.der[1] = s.der[2] = nullptr;
+        s.state = a.sel;
+        s.hist = (unsigned int *)c->stat.hist.p;
+        launch_select(c, s, ns);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_rw_tail, dim3((unsigned)nsrc), dim3(kThreads), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    // the weighted statistics of the summary's columns
+    if ((rc = summary_fill_derived(c, ss, a))) return rc;
+    a.colstatus = (const int *)c->der.colstatus.p;
+    const dim3 gcol((unsigned)ncolumns, (unsigned)a.splits);
+    hipLaunchKernelGGL(k_rw_wstats, gcol, dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rw_wbegin, dim3((unsigned)((ncolumns + 63) / 64)), dim3(64), 0, c->stream, a);
+    for (int pass = 0; pass < 8; ++pass) {
+        hipLaunchKernelGGL(k_rw_whist, gcol, dim3(kThreads), 0, c->stream, a, pass);
+        hipLaunchKernelGGL(k_rw_wpick, dim3((unsigned)ncolumns), dim3(kThreads), 0, c->stream, a);
+    }
+    hipLaunchKernelGGL(k_rw_cov, gsrc, dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_rw_finish, dim3((unsigned)((sc + 63) / 64)), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    if ((rc = fetch_image(c, w.outbuf, rb)) || (rc = derived_sync(c))) return rc;
+    rb.scatter();
+    // the per-entry outputs asked for, one after the other through one block
+    void *const dst[4] = {o->target_lnprob, o->log_ratio, o->log_weight, o->weight};
+    for (int what = 0; what < 4; ++what) {
+        if (!dst[what]) continue;
+        hipLaunchKernelGGL(k_rw_entries, dim3((unsigned)((ns * n + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
+                           a, what, (double *)w.entries.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(dst[what], w.entries.p, ns * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_reweight(mbb_ctx *target, const double *chain, const double *lnprob, int nsrc, int nw, int nsteps,
+                                  const mbb_reweight_spec *spec, const mbb_reweight_out *out)
+{
+    return analyse_chain(target, chain, lnprob, nsrc, nw, nsteps, [&] {
+        if (!chain || !lnprob) return fail(MBB_ERR_ARG, "bad arguments: a reweighting needs the chain and its lnprob");
+        return rw_check(target, nsrc, nw, nsteps, spec, out);
+    }, [&](const double *d, const double *dl) { return rw_run(target, d, dl, nsrc, nw, nsteps, spec, out); });
+}
+
+// c owns the sampler and the resident chain; target, the same context or another of this process and device, owns the
+// work.  c's stream is brought to rest before target's first launch; rw_run leaves target's at rest.
+extern "C" int mbb_sampler_reweight(mbb_ctx *c, void *sp, mbb_ctx *target, const mbb_reweight_spec *spec,
+                                    const mbb_reweight_out *out)
+{
+    if (!target) return fail(MBB_ERR_ARG, "null reweight argument");
+    return analyse_sampler(c, sp, spec && out, "reweighted", true,
+                           [&](const double *d, const double *dl, int nsrc, int nw, int nsteps) -> int {
+        int rc;
+        if (target->device != c->device) return fail(MBB_ERR_ARG, "the target context is on another device than the chain");
+        if (sharded_context(c))
+            return fail(MBB_ERR_STATE, "a sharded context cannot reweight a chain: a rank holds only its own walkers' chain");
+        if ((rc = rw_check(target, nsrc, nw, nsteps, spec, out))) return rc;
+        if (target != c && (rc = use(target))) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return rw_run(target, d, dl, nsrc, nw, nsteps, spec, out);
     });
 }
 

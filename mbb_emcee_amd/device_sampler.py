@@ -88,6 +88,11 @@ def _request_draws(s, kw):
     return draws._Request(nsources=s.nsources, **kw)
 
 
+def _request_reweight(s, kw):
+    from . import reweight
+    return reweight._Request(nsources=s.nsources, **kw)
+
+
 def _request_convergence(s, kw):
     from . import diagnostics
     return diagnostics._Request(**kw)
@@ -133,14 +138,16 @@ _ANALYSES = {
     "marginals": _Analysis(None, None, _DERIVED, None, _request_marginals, _check_steps, "binned", "marginals_",
                            "marginals"),
     "draws": _Analysis("n", None, _DERIVED, None, _request_draws, _check_steps, "drawn from", "draws_", "draws"),
+    "reweight": _Analysis("target", "reweight= needs a target: the likelihood the chain is reweighted to", _DERIVED, None,
+                          _request_reweight, _check_loo, "reweighted", "reweight_", "reweight"),
     "convergence": _Analysis(None, None, (), None, _request_convergence, _check_steps, "diagnosed", "convergence_",
                              "convergence"),
 }
 # three orders, each as run_mcmc has always had it: requests are made and checked, a sharded run is refused, and the
 # results are made after the run
-_REQUEST_ORDER = ("predict", "loo", "goodness", "evidence", "marginals", "draws", "convergence")
-_SHARDED_ORDER = ("convergence", "marginals", "predict", "loo", "goodness", "evidence", "draws")
-_RESULT_ORDER = ("convergence", "marginals", "predict", "draws", "goodness", "evidence", "loo")
+_REQUEST_ORDER = ("predict", "loo", "goodness", "evidence", "marginals", "draws", "convergence", "reweight")
+_SHARDED_ORDER = ("convergence", "marginals", "predict", "loo", "goodness", "evidence", "draws", "reweight")
+_RESULT_ORDER = ("convergence", "marginals", "predict", "draws", "goodness", "evidence", "loo", "reweight")
 
 
 class DeviceEnsembleSampler(object):
@@ -188,7 +195,7 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_``, ``loo_``, ``evidence_`` or ``predictions_``, nothing resident for ``convergence()`` or
+        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_``, ``loo_``, ``evidence_``, ``reweight_`` or ``predictions_``, nothing resident for ``convergence()`` or
         ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
@@ -317,6 +324,22 @@ class DeviceEnsembleSampler(object):
         raw = self._analyse("pointwise", req, loo._Raw(self.nsources, req.ndata))
         return loo.ChainLoo(req, raw, self.nsources > 1, self.k, nkept)
 
+    def reweight(self, target, **kw):
+        """``reweight.ChainReweight`` (Pareto-smoothed importance weights and the weighted statistics of the chain under
+        the density of ``target``, another ``likelihood``: k-hat, ess, ln(Z_target / Z_run), weighted means, quantiles,
+        covariance and best entry) of the chain the last run left on the device -- a run with storechain=True or with
+        summary= --; the keywords are ``reweight.chain_reweight``'s.  ``target`` may be this sampler's own likelihood
+        or another of this process on the same device.  No chain crosses the bus."""
+        from . import reweight
+        req = reweight._Request(target, nsources=self.nsources, **kw)
+        nkept = req.check_steps(self._resident_steps("reweight"), self.k)
+        ctx, h = self._handle()
+        tctx = _native.analysis_context(target)
+        raw = reweight._Raw(self.nsources, len(req.qs), self.k * nkept, req.keep)
+        spec, out = req.spec(), raw.out()
+        _native.check_arg(ctx.lib.mbb_sampler_reweight(ctx.h, h, tctx.h, C.byref(spec), C.byref(out)), ctx)
+        return reweight.ChainReweight(req, raw, self.nsources > 1, self.k, nkept)
+
     def evidence(self, n2=None, fixed=None, neff="auto", seed=None, burn=0, thin=1, tol=None, maxiter=None, keep=False):
         """``evidence.ChainEvidence`` (bridge-sampled ln Z per source with its error) of the chain the last run left on
         the device -- a run with storechain=True or with summary= --; the keywords are ``evidence.chain_evidence``'s,
@@ -374,7 +397,8 @@ class DeviceEnsembleSampler(object):
         return self._analyse("predict", req, predict._Raw(self.nsources, len(req.keys), len(req.qs)))
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
-                 marginals=None, predict=None, draws=None, goodness=None, evidence=None, loo=None, **unused):
+                 marginals=None, predict=None, draws=None, goodness=None, evidence=None, loo=None, reweight=None,
+                 **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -429,13 +453,18 @@ class DeviceEnsembleSampler(object):
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
         with summary=.
 
+        reweight=target, or a dict of ``reweight()``'s keywords with ``target`` among them: the chain of this run is
+        reweighted under the target likelihood's density on the device and ``sampler.reweight_`` is the
+        ``reweight.ChainReweight`` of it (None again after reset() and at the start of the next run).  Window and
+        derived-column keywords default to summary='s.
+
         evidence=True, or a dict of ``evidence()``'s keywords: ln Z of the chain of this run is bridge-sampled on the
         device and ``sampler.evidence_`` is the ``evidence.ChainEvidence`` of it (None again after reset() and at the
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
         with summary=."""
         self._retire()
         return self._run(pos0, N, lnprob0, storechain, summary, convergence=convergence, marginals=marginals,
-                         predict=predict, draws=draws, goodness=goodness, evidence=evidence, loo=loo)
+                         predict=predict, draws=draws, goodness=goodness, evidence=evidence, loo=loo, reweight=reweight)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""

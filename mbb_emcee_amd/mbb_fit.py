@@ -190,7 +190,7 @@ class mbb_fitter(object):
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
     def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None,
-            draws=None, goodness=None, evidence=None, loo=None):
+            draws=None, goodness=None, evidence=None, loo=None, reweight=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
@@ -211,7 +211,12 @@ class mbb_fitter(object):
         per band, ``mbb_fitter.loo``.
         evidence (device sampler only): True or a dict of ``evidence.chain_evidence``'s keywords -- the main chain's
         bridge-sampled ln Z per source, ``mbb_fitter.evidence``; the fitter's own fixed parameters are passed on as
-        ``fixed`` unless the dict names others."""
+        ``fixed`` unless the dict names others.
+        reweight (device sampler only): a target ``likelihood`` (or a ``mbb_fitter``, whose likelihood is meant), or a
+        dict of ``reweight.chain_reweight``'s keywords (``target`` among them) -- the main chain reweighted under the
+        target's density, ``mbb_fitter.reweight``."""
+        if reweight is not None and reweight is not False and not hasattr(self.sampler, "reweight"):
+            raise ValueError("reweight= needs sampler=\"device\"")
         if evidence is not None and evidence is not False and not hasattr(self.sampler, "evidence"):
             raise ValueError("evidence= needs sampler=\"device\"")
         if loo is not None and loo is not False and not hasattr(self.sampler, "loo"):
@@ -274,6 +279,11 @@ class mbb_fitter(object):
             extra["goodness"] = goodness
         if loo is not None and loo is not False:
             extra["loo"] = loo
+        if reweight is not None and reweight is not False:
+            rkw = dict(reweight) if isinstance(reweight, dict) else dict(target=reweight)
+            if isinstance(rkw.get("target"), mbb_fitter):
+                rkw["target"] = rkw["target"].like
+            extra["reweight"] = rkw
         if evidence is not None and evidence is not False:
             ekw = {} if evidence is True else dict(evidence)
             ekw.setdefault("fixed", [bool(f) for f in self._fixed])
@@ -327,6 +337,8 @@ mbb_fitter.loo = property(lambda self: getattr(self.sampler, "loo_", None),
                           doc="loo.ChainLoo of the main chain when run() was given loo=, else None")
 mbb_fitter.evidence = property(lambda self: getattr(self.sampler, "evidence_", None),
                                doc="evidence.ChainEvidence of the main chain when run() was given evidence=, else None")
+mbb_fitter.reweight = property(lambda self: getattr(self.sampler, "reweight_", None),
+                               doc="reweight.ChainReweight of the main chain when run() was given reweight=, else None")
 mbb_fitter.draws = property(lambda self: getattr(self.sampler, "draws_", None),
                             doc="draws.ChainDraws from the main chain when run() was given draws=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,

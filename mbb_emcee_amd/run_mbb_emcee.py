@@ -66,6 +66,12 @@ def build_parser():
                    help="the evidence ln Z of the fit, bridge-sampled from the chain on the device with N2 proposal draws "
                         "(default: as many as posterior samples; needs --sampler device): printed, and added to the "
                         ".npz as evidence_*")
+    p.add_argument("--reweight-prior", dest="reweight_prior", nargs=3, action="append", default=None,
+                   metavar=("NAME", "MEAN", "SIGMA"),
+                   help="reweight the chain on the device under the same fit with a Gaussian prior MEAN, SIGMA on parameter "
+                        "NAME set in addition (repeatable; needs --sampler device): Pareto k-hat, effective sample size, "
+                        "ln(Z_target / Z_run) and the weighted means and intervals printed, and added to the .npz as "
+                        "reweight_*")
     p.add_argument("--map-init", dest="map_init", type=int, nargs="?", const=8, default=0, metavar="NSTART",
                    help="find the maximum of the posterior on the device first, from NSTART (default 8) points of the "
                         "initial ball: the optimum with its Laplace errors is printed and added to the .npz as map_*, and "
@@ -99,10 +105,8 @@ def parse_predict(text):
     return specs
 
 
-def main(argv=None):
-    a = build_parser().parse_args(argv)
-    if a.nwalkers <= 0:
-        raise ValueError("Invalid (non-positive) nwalkers: %d" % a.nwalkers)
+def make_fitter(a, more_priors=()):
+    """The fitter the arguments describe, with the Gaussian priors (name, mean, sigma) of more_priors set in addition."""
     fit = mbb_fitter(nwalkers=a.nwalkers, photfile=a.photfile, wavenorm=a.wavenorm,
                      noalpha=a.noalpha, opthin=a.opthin, nthreads=a.threads, response=a.response,
                      responsefile=a.responsefile, responsedir=a.responsedir, sampler=a.sampler,
@@ -124,6 +128,19 @@ def main(argv=None):
         fit.set_uplim("lambda_peak", a.upLambdaPeak)
     if a.priorLambdaPeak is not None:
         fit.set_gaussian_prior("lambda_peak", a.priorLambdaPeak[0], a.priorLambdaPeak[1])
+    for nm, mean, sigma in more_priors:
+        fit.set_gaussian_prior(nm.lower(), mean, sigma)
+    return fit
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.nwalkers <= 0:
+        raise ValueError("Invalid (non-positive) nwalkers: %d" % a.nwalkers)
+    fit = make_fitter(a)
+    target = None
+    if a.reweight_prior:
+        target = make_fitter(a, [(nm, float(mean), float(sigma)) for nm, mean, sigma in a.reweight_prior])
 
     p0init = np.array([getattr(a, "init" + nm) for nm in NAMES])
     initsigma = np.array([2, 0.2, 100, 0.3, 5.0])
@@ -151,6 +168,9 @@ def main(argv=None):
         extra["loo"] = True
     if a.evidence is not None:
         extra["evidence"] = dict(n2=None if a.evidence < 0 else a.evidence)
+    if target is not None:
+        extra["reweight"] = dict(target=target, percentile=(68.3, 95.4),
+                                 derived=("peaklambda",) if a.get_peaklambda else ())
     if a.draws:
         extra["draws"] = dict(n=a.draws, derived=("peaklambda",) if a.get_peaklambda else ())
     fit.run(a.burn, a.nsteps, p0, verbose=a.verbose, summary=summary, **extra)
@@ -184,6 +204,9 @@ def main(argv=None):
     if a.evidence is not None:
         out.update(fit.evidence.arrays())
         print(fit.evidence)
+    if target is not None:
+        out.update(fit.reweight.arrays())
+        print(fit.reweight)
     if a.draws:
         out.update(fit.draws.arrays())
         print(fit.draws)
