@@ -743,6 +743,84 @@ int mbb_chain_reweight(mbb_ctx *target, const double *chain, const double *lnpro
 int mbb_sampler_reweight(mbb_ctx *ctx, void *sampler, mbb_ctx *target, const mbb_reweight_spec *spec,
                          const mbb_reweight_out *out);
 
+/* ---- the population of a catalogue: the hyper-likelihood of its sources' chains under Gaussian candidates ---- */
+/* New: the reference has nothing comparable.  Every other analysis answers a question about one source; this one asks
+ * how chosen parameters are distributed OVER the sources, by the importance-sampling form of a hierarchical model
+ * (Hogg, Myers & Bovy 2010): each source's chain was sampled under the run's own "interim" prior pi0, and for a
+ * population density phi(. | h) the catalogue's likelihood is prod_n mean_j phi(x_nj | h) / pi0(x_nj) over the source's
+ * window (csrc/mbb_population.hip.h; the step logic is csrc/mbb_popsteps.hip.h).
+ *   columns    d of the five parameters (T, beta, lambda0, alpha, fnorm: 0 .. 4), 1 <= d <= 5, each at most once, with a
+ *              transform g each: MBB_POP_IDENTITY or MBB_POP_LOG10.  The derived columns (peak wavelength, L_IR, dust
+ *              mass) cannot be chosen: their interim prior density is not known in closed form.
+ *   entries    source n has the entries j = 0 .. n - 1 of the window, steps burn, burn + thin, ... of every walker in
+ *              [walker][step] order (csrc/mbb_chain_view.hip.h);  x_j = g(theta_j[columns]).
+ *   interim    ln pi0(x_j) is the sum over the chosen columns of the likelihood's own separable prior factor of that
+ *              parameter, unnormalised: 0 up to the upper limit, -1/2 ((theta - uplim) / (0.02 (uplim - lowlim)))^2
+ *              beyond it where the parameter has one, plus -1/2 givar (theta - gmean)^2 where it has a Gaussian prior,
+ *              plus for a log10 column the Jacobian ln(theta ln 10).  The limits and priors are the spec's, not the
+ *              context's.  b_j = -ln pi0(x_j).  (A limit or prior on the peak wavelength is not separable and has no
+ *              place here.)
+ *   used       an entry is USED when every chosen theta is finite, every log10 column has theta > 0 and b_j is finite;
+ *              otherwise it is LEFT OUT (n_left_out, MBB_SUM_HAS_NAN).  No lnprob is needed.
+ *   candidate  h = (mu[d], L): L the lower Cholesky factor of the covariance, row by row, d (d + 1) / 2 values.  A
+ *              candidate with a value that is not finite or an L_ii <= 0 is bad: MBB_POP_CAND_BAD, NaN results, and the
+ *              other candidates of the call are unaffected.
+ *              a_j(h) = -1/2 |L^-1 (x_j - mu)|^2 - sum_i ln L_ii - (d / 2) ln 2 pi + b_j, by forward substitution.
+ *   per (candidate, source), with A = sum_j e^a_j over the used entries, every sum kept as a pair (max, sum e^(. - max)):
+ *              lnl_src = ln A - ln n_used;   ess = A^2 / sum_j e^(2 a_j);
+ *              with moments: mean = sum e^a_j x_j / A and cov = sum e^a_j (x_j - mean)(x_j - mean)^T / A, the source's
+ *              posterior shrunk by that population.
+ *              When every a_j is below -745 (e^a_j is below the smallest float64): lnl_src = -inf, ess and the moments
+ *              NaN, MBB_POP_CAND_UNDERFLOW.  A source with no used entry: lnl_src NaN, MBB_SUM_EMPTY in its status and
+ *              MBB_POP_CAND_HAS_EMPTY in every candidate's; it is left out of the total.
+ *   per candidate  lnl = sum_n lnl_src over the sources used, in source order; n_src_used their number.
+ * The population Gaussian is NOT renormalised over the hard lower limits: results mean little where its mass below a
+ * limit is not small (population.py reports it as mass_below).
+ * The arithmetic of one (candidate, source) depends on neither the other candidates or sources of a call nor on the
+ * candidate's place in it: the same bits alone and in company.
+ * mbb_*_population_build turns the window into a compact block [nsrc][n][d] of x and [nsrc][n] of b that the CONTEXT
+ * keeps (one block per context: the next build replaces it, mbb_population_drop or the context's end frees it), and
+ * hands back a serial number that every build increases; mbb_population_eval of another serial than the current block's
+ * is MBB_ERR_STATE.  Refused before anything is allocated: null arguments, an empty chain or window, d outside 1 .. 5, a
+ * repeated or unknown column or transform, H outside 1 .. MBB_POP_MAX_CAND, a sharded context (MBB_ERR_STATE).  A block
+ * that cannot be allocated fails with the allocator's status; thin the window then. */
+#define MBB_POP_MAX_CAND 1024
+enum mbb_population_transform { MBB_POP_IDENTITY = 0, MBB_POP_LOG10 = 1 };
+enum mbb_population_cand_status {          /* cand_status [H]                                                   */
+    MBB_POP_CAND_BAD = 1,                  /* a value not finite or an L_ii <= 0: NaN results                   */
+    MBB_POP_CAND_UNDERFLOW = 2,            /* a source's lnl_src is -inf, and so is lnl                         */
+    MBB_POP_CAND_HAS_EMPTY = 4             /* a source without a used entry was left out of lnl                 */
+};
+typedef struct mbb_population_spec {
+    int32_t d;                             /* 1 .. 5 columns                                                    */
+    int32_t col[5], transform[5];          /* [d]: the parameter 0 .. 4 and its transform                       */
+    int32_t burn, thin;                    /* the window                                                        */
+    int32_t has_uplim[5], has_gprior[5];   /* by parameter: the likelihood's limits and priors                  */
+    double lowlim[5], uplim[5], gmean[5], givar[5];
+} mbb_population_spec;
+typedef struct mbb_population_build_out {
+    int64_t *n_used, *n_left_out;          /* [nsrc]                                                            */
+    int32_t *status;                       /* [nsrc]: MBB_SUM_EMPTY, MBB_SUM_HAS_NAN (entries left out)         */
+    int64_t *serial;                       /* [1]: the block's serial number                                    */
+} mbb_population_build_out;
+typedef struct mbb_population_eval_out {
+    double *lnl;                           /* [H]                                                               */
+    int32_t *n_src_used, *cand_status;     /* [H]                                                               */
+    double *lnl_src, *ess;                 /* [H][nsrc], or NULL                                                */
+    double *mean, *cov;                    /* [H][nsrc][d], [H][nsrc][d][d]: both given with moments, else unused */
+} mbb_population_eval_out;
+/* A host chain in emcee's layout [nsrc][nw][nsteps][5]. */
+int mbb_chain_population_build(mbb_ctx *ctx, const double *chain, int nsrc, int nw, int nsteps,
+                               const mbb_population_spec *spec, const mbb_population_build_out *out);
+/* The same of the chain the sampler's last stored or summarised run left on the device. */
+int mbb_sampler_population_build(mbb_ctx *ctx, void *sampler, const mbb_population_spec *spec,
+                                 const mbb_population_build_out *out);
+/* H candidates [H][d + d (d + 1) / 2] against the block of that serial. */
+int mbb_population_eval(mbb_ctx *ctx, int64_t serial, const double *hyper, int H, int moments,
+                        const mbb_population_eval_out *out);
+/* Frees the context's block; a serial handed out before is MBB_ERR_STATE from then on. */
+int mbb_population_drop(mbb_ctx *ctx);
+
 /* ---- SED-level entry points (parity + the modified_blackbody class) ----- */
 /* Replaces: modified_blackbody.__init__ (modified_blackbody.py:168-337) and
  * max_wave (:581-637) for n parameter rows.

@@ -22,6 +22,7 @@ from .optimize import map_fit, MapFit
 from .evidence import chain_evidence, ChainEvidence
 from .loo import chain_loo, loo_rows, ChainLoo
 from .reweight import chain_reweight, ChainReweight
+from .population import chain_population, Population, PopulationEval, PopulationFit
 
 __version__ = "0.1.0"
 __all__ = ["response", "response_set", "modified_blackbody", "alpha_merge_eqn", "isiterable", "likelihood",
@@ -30,4 +31,4 @@ __all__ = ["response", "response_set", "modified_blackbody", "alpha_merge_eqn", 
            "chain_predictions", "ChainPredictions", "chain_draws", "draw_indices", "ChainDraws",
            "chain_goodness", "ChainGoodness", "map_fit", "MapFit",
            "chain_evidence", "ChainEvidence", "chain_loo", "loo_rows", "ChainLoo",
-           "chain_reweight", "ChainReweight"]
+           "chain_reweight", "ChainReweight", "chain_population", "Population", "PopulationEval", "PopulationFit"]

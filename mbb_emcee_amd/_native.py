@@ -137,6 +137,31 @@ class ReweightOut(C.Structure):
                 ("target_lnprob", _dp), ("log_ratio", _dp), ("log_weight", _dp), ("weight", _lp)]
 
 
+POP_MAX_CAND = 1024
+POP_IDENTITY, POP_LOG10 = 0, 1
+POP_CAND_BAD, POP_CAND_UNDERFLOW, POP_CAND_HAS_EMPTY = 1, 2, 4
+
+
+class PopulationSpec(C.Structure):
+    """mbb_population_spec (include/mbb_hip.h)"""
+    _fields_ = [("d", C.c_int32), ("col", C.c_int32 * 5), ("transform", C.c_int32 * 5),
+                ("burn", C.c_int32), ("thin", C.c_int32),
+                ("has_uplim", C.c_int32 * 5), ("has_gprior", C.c_int32 * 5),
+                ("lowlim", C.c_double * 5), ("uplim", C.c_double * 5), ("gmean", C.c_double * 5),
+                ("givar", C.c_double * 5)]
+
+
+class PopulationBuildOut(C.Structure):
+    """mbb_population_build_out (include/mbb_hip.h)"""
+    _fields_ = [("n_used", _lp), ("n_left_out", _lp), ("status", _ip), ("serial", _lp)]
+
+
+class PopulationEvalOut(C.Structure):
+    """mbb_population_eval_out (include/mbb_hip.h)"""
+    _fields_ = [("lnl", _dp), ("n_src_used", _ip), ("cand_status", _ip), ("lnl_src", _dp), ("ess", _dp),
+                ("mean", _dp), ("cov", _dp)]
+
+
 MAP_MAX_STARTS, MAP_MAX_ITER = 64, 1000
 MAP_CONVERGED_F, MAP_CONVERGED_X, MAP_MAXITER, MAP_START_INVALID, MAP_COV_SINGULAR, MAP_ALL_FIXED = 1, 2, 4, 8, 16, 32
 MAP_STENCIL_FAILED = 64
@@ -245,6 +270,11 @@ SIGNATURES = {
     "mbb_chain_reweight": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(ReweightSpec),
                                      C.POINTER(ReweightOut)]),
     "mbb_sampler_reweight": (C.c_int, [_vp, _vp, _vp, C.POINTER(ReweightSpec), C.POINTER(ReweightOut)]),
+    "mbb_chain_population_build": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(PopulationSpec),
+                                             C.POINTER(PopulationBuildOut)]),
+    "mbb_sampler_population_build": (C.c_int, [_vp, _vp, C.POINTER(PopulationSpec), C.POINTER(PopulationBuildOut)]),
+    "mbb_population_eval": (C.c_int, [_vp, C.c_int64, _dp, C.c_int, C.c_int, C.POINTER(PopulationEvalOut)]),
+    "mbb_population_drop": (C.c_int, [_vp]),
     "mbb_sampler_advance_async": (C.c_int, [_vp, _vp, C.c_int, C.c_double]),
     "mbb_sampler_flow_counters": (C.c_int, [_vp, _vp, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -55,6 +55,8 @@ DEPS = [SRC, SRC_HOST, SRC_FLOW, SRC_REG, os.path.join(HERE, "csrc", "mbb_host_t
         os.path.join(HERE, "csrc", "mbb_pointwise.hip.h"),
         os.path.join(HERE, "csrc", "mbb_rwsteps.hip.h"),
         os.path.join(HERE, "csrc", "mbb_reweight.hip.h"),
+        os.path.join(HERE, "csrc", "mbb_popsteps.hip.h"),
+        os.path.join(HERE, "csrc", "mbb_population.hip.h"),
         os.path.join(os.path.dirname(HERE), "include", "mbb_hip.h")]
 LIB = os.path.join(HERE, "libmbb_hip.so")
 ARCH = "gfx950"

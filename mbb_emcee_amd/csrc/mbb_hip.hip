@@ -39,6 +39,7 @@
 #include "mbb_evidence.hip.h"
 #include "mbb_pointwise.hip.h"
 #include "mbb_reweight.hip.h"
+#include "mbb_population.hip.h"
 #include "mbb_draws.hip.h"
 
 // SMODE 6 is instantiated in mbb_flow.hip (its own compiler flags)
@@ -351,6 +352,12 @@ struct mbb_ctx {
     struct RwWork {                                                             // a chain reweighted under this context's density (rw_run)
         DevBuf slab, cols, count, state, sel, status, wpart, wstate, whist, covpart, entries, outbuf;
     } rw;
+    struct PopBlock {                                                           // the population block of a chain (pop_build) and
+        DevBuf x, b, count, hyper, part, lsrc, outbuf;                          // the work of its evaluations (pop_eval)
+        long long serial = 0, n = 0, per_split = 0;                             // serial: of the last build, never handed out twice
+        int nsrc = 0, d = 0, splits = 0;
+        bool live = false;                                                      // a block of that serial is there
+    } pop;
     mbbopt::Options opt;                       // what mbb_set_option sets: every field, default and bound in mbb_options.h
     long last_prepass = 0;                     // whether the last likelihood launch was preceded by k_walker_pre (launch_rows)
     Dev<double> pre;                           // ... its records
@@ -3715,6 +3722,190 @@ extern "C" int mbb_sampler_reweight(mbb_ctx *c, void *sp, mbb_ctx *target, const
         HIPCHK(hipStreamSynchronize(c->stream));
         return rw_run(target, d, dl, nsrc, nw, nsteps, spec, out);
     });
+}
+
+// ---- the population of a catalogue (mbb_population.hip.h) ----------------------
+static_assert(mbbpop::kStEmpty == MBB_SUM_EMPTY && mbbpop::kStHasNan == MBB_SUM_HAS_NAN &&
+              mbbpop::kCandBad == MBB_POP_CAND_BAD && mbbpop::kCandUnderflow == MBB_POP_CAND_UNDERFLOW &&
+              mbbpop::kCandHasEmpty == MBB_POP_CAND_HAS_EMPTY, "the header's status bits are the kernels'");
+static_assert(mbbpop::kMaxCand == MBB_POP_MAX_CAND && mbbpops::kIdentity == MBB_POP_IDENTITY &&
+              mbbpops::kLog10 == MBB_POP_LOG10, "the header's constants are the kernels'");
+static_assert(mbbpop::kChunk % mbbpop::kTile == 0 && mbbpop::kChunk % mbbpop::kTileMom == 0 &&
+              mbbpop::kChunk % mbbpop::kTileMomWide == 0, "a launch holds whole tiles");
+
+// The argument checks of a population build: before anything is allocated, uploaded or launched.
+static int pop_check(const mbb_ctx *c, int nsrc, int nw, int nsteps, const mbb_population_spec *sp,
+                     const mbb_population_build_out *o)
+{
+    if (!sp || !o || !o->n_used || !o->n_left_out || !o->status || !o->serial)
+        return fail(MBB_ERR_ARG, "null population argument");
+    if (sharded_context(c))
+        return fail(MBB_ERR_STATE, "a sharded context cannot pool a chain into a population: a rank holds only its own walkers' chain");
+    if (nsrc < 1 || nw < 1 || nsteps < 1) return fail(MBB_ERR_ARG, "empty chain");
+    if (sp->d < 1 || sp->d > mbbpops::kMaxD) return fail(MBB_ERR_ARG, "a population has 1 to 5 columns");
+    unsigned seen = 0;
+    for (int i = 0; i < sp->d; ++i) {
+        if (sp->col[i] < 0 || sp->col[i] > 4) return fail(MBB_ERR_ARG, "unknown population column: the five parameters are 0 to 4");
+        if ((seen >> sp->col[i]) & 1u) return fail(MBB_ERR_ARG, "a population column is given twice");
+        seen |= 1u << sp->col[i];
+        if (sp->transform[i] != MBB_POP_IDENTITY && sp->transform[i] != MBB_POP_LOG10)
+            return fail(MBB_ERR_ARG, "unknown population transform");
+    }
+    if (const int rc = check_burn_thin(sp->burn, sp->thin, nsteps)) return rc;
+    const unsigned long long n = (unsigned long long)nw * (unsigned long long)kept_steps(sp->burn, sp->thin, nsteps);
+    const unsigned long long bps = (n + mbbpop::kThreads - 1) / mbbpop::kThreads;
+    if (bps * (unsigned long long)nsrc > 0x7fffffffull) return fail(MBB_ERR_ARG, "too many sources");
+    return check_grid((size_t)nsrc);
+}
+
+// A population block that cannot be made: the allocator's status, and what to do about it.
+static int pop_alloc_failed(mbb_ctx *c, int rc)
+{
+    c->pop.x.release(); c->pop.b.release();
+    g_err = "the population block cannot be allocated (" + g_err + "): thin the window";
+    return rc;
+}
+
+// The window of the chain on the device into the context's block.  Synchronous.
+static int pop_build(mbb_ctx *c, const double *d_chain, int nsrc, int nw, int nsteps, const mbb_population_spec *sp,
+                     const mbb_population_build_out *o)
+{
+    using namespace mbbpop;
+    int rc;
+    if ((rc = pop_check(c, nsrc, nw, nsteps, sp, o))) return rc;
+    mbb_ctx::PopBlock &w = c->pop;
+    w.live = false;
+    const long long serial = ++w.serial;
+    PopBuildArgs a;
+    memset(&a, 0, sizeof a);
+    fill_window(a, d_chain, nsrc, nw, nsteps, sp->burn, sp->thin);
+    a.d = sp->d;
+    for (int i = 0; i < sp->d; ++i) { a.pcol[i] = sp->col[i]; a.transform[i] = sp->transform[i]; }
+    for (int k = 0; k < 5; ++k) {
+        a.prior.has_uplim[k] = sp->has_uplim[k] != 0; a.prior.has_gprior[k] = sp->has_gprior[k] != 0;
+        a.prior.lowlim[k] = sp->lowlim[k]; a.prior.uplim[k] = sp->uplim[k];
+        a.prior.gmean[k] = sp->gmean[k]; a.prior.givar[k] = sp->givar[k];
+    }
+    const size_t ns = (size_t)nsrc, n = (size_t)a.n;
+    if ((rc = grow(c, w.x, ns * n * sp->d * sizeof(double))) || (rc = grow(c, w.b, ns * n * sizeof(double))))
+        return pop_alloc_failed(c, rc);
+    if ((rc = grow(c, w.count, ns * sizeof(unsigned long long)))) return rc;
+    ResultBlock rb;
+    rb.add(&a.o_nused, ns, o->n_used); rb.add(&a.o_nleft, ns, o->n_left_out); rb.add(&a.o_status, ns, o->status);
+    if ((rc = place(c, w.outbuf, rb))) return rc;
+    a.x = (double *)w.x.p; a.b = (double *)w.b.p; a.count = (unsigned long long *)w.count.p;
+    a.blocks_per_src = (unsigned)((n + kThreads - 1) / kThreads);
+    HIPCHK(hipMemsetAsync(w.count.p, 0, ns * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_pop_build, dim3((unsigned)(ns * a.blocks_per_src)), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_pop_status, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    if ((rc = fetch_home(c, w.outbuf, rb))) return rc;
+    w.nsrc = nsrc; w.d = sp->d; w.n = a.n;
+    // the splits of a source's entries: a function of n alone
+    w.splits = (int)std::min<long long>(kMaxSplits, (a.n + kSplitEntries - 1) / kSplitEntries);
+    w.per_split = (a.n + w.splits - 1) / w.splits;
+    w.live = true;
+    *o->serial = serial;
+    return MBB_OK;
+}
+
+extern "C" int mbb_chain_population_build(mbb_ctx *c, const double *chain, int nsrc, int nw, int nsteps,
+                                          const mbb_population_spec *spec, const mbb_population_build_out *out)
+{
+    return analyse_chain(c, chain, nullptr, nsrc, nw, nsteps, [&] { return pop_check(c, nsrc, nw, nsteps, spec, out); },
+                         [&](const double *d, const double *) { return pop_build(c, d, nsrc, nw, nsteps, spec, out); });
+}
+
+extern "C" int mbb_sampler_population_build(mbb_ctx *c, void *sp, const mbb_population_spec *spec,
+                                            const mbb_population_build_out *out)
+{
+    return analyse_sampler(c, sp, spec && out, "pooled into a population", false,
+                           [&](const double *d, const double *, int nsrc, int nw, int nsteps) {
+        return pop_build(c, d, nsrc, nw, nsteps, spec, out);
+    });
+}
+
+template <int D, bool MOM> static void pop_launch(mbb_ctx *c, const mbbpop::PopEvalArgs &a)
+{
+    using namespace mbbpop;
+    constexpr int TILE = pop_tile(D, MOM);
+    const dim3 grid((unsigned)a.nsrc, (unsigned)a.splits, (unsigned)((a.hn + TILE - 1) / TILE));
+    hipLaunchKernelGGL((k_pop_eval<D, MOM>), grid, dim3(kThreads), 0, c->stream, a);
+    const long long pairs = (long long)a.hn * a.nsrc;
+    hipLaunchKernelGGL((k_pop_merge<D, MOM>), dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, c->stream, a);
+}
+
+template <int D> static void pop_launch_d(mbb_ctx *c, const mbbpop::PopEvalArgs &a)
+{
+    if (a.moments) pop_launch<D, true>(c, a); else pop_launch<D, false>(c, a);
+}
+
+extern "C" int mbb_population_eval(mbb_ctx *c, int64_t serial, const double *hyper, int H, int moments,
+                                   const mbb_population_eval_out *o)
+{
+    using namespace mbbpop;
+    int rc = use(c);
+    if (rc) return rc;
+    if (!hyper || !o || !o->lnl || !o->n_src_used || !o->cand_status || (moments && (!o->mean || !o->cov)))
+        return fail(MBB_ERR_ARG, "null population argument");
+    if (H < 1 || H > MBB_POP_MAX_CAND) return fail(MBB_ERR_ARG, "a population evaluation takes 1 to MBB_POP_MAX_CAND (1024) candidates");
+    if (sharded_context(c))
+        return fail(MBB_ERR_STATE, "a sharded context cannot pool a chain into a population: a rank holds only its own walkers' chain");
+    mbb_ctx::PopBlock &w = c->pop;
+    if (!w.live || serial != (int64_t)w.serial)
+        return fail(MBB_ERR_STATE, "no population block of this serial in the context: it was replaced by a later build, or dropped");
+    const int d = w.d, hl = mbbpops::pop_hyper_len(d);
+    const size_t ns = (size_t)w.nsrc, nh = (size_t)H, pairs = nh * ns;
+    const int words = 3 + (moments ? d + mbbpops::pop_tri(d) : 0);
+    PopEvalArgs a;
+    memset(&a, 0, sizeof a);
+    ResultBlock rb;
+    rb.add(&a.o_lnl, nh, o->lnl);
+    rb.add(&a.lnl_src, pairs, o->lnl_src); rb.add(&a.ess, pairs, o->ess);
+    rb.add(&a.mean, moments ? pairs * d : 0, moments ? o->mean : nullptr);
+    rb.add(&a.cov, moments ? pairs * d * d : 0, moments ? o->cov : nullptr);
+    rb.add(&a.o_nsrc_used, nh, o->n_src_used); rb.add(&a.o_cand_status, nh, o->cand_status);
+    const size_t chunk = std::min<size_t>(nh, kChunk);
+    if ((rc = grow(c, w.hyper, nh * hl * sizeof(double)))) return rc;
+    if ((rc = grow(c, w.part, chunk * ns * w.splits * words * sizeof(double)))) return rc;
+    if ((rc = place(c, w.lsrc, rb))) return rc;
+    HIPCHK(hipMemcpyAsync(w.hyper.p, hyper, nh * hl * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    a.x = (const double *)w.x.p; a.b = (const double *)w.b.p; a.count = (const unsigned long long *)w.count.p;
+    a.hyper = (const double *)w.hyper.p;
+    a.nsrc = w.nsrc; a.d = d; a.H = H; a.n = w.n; a.per_split = w.per_split; a.splits = w.splits; a.moments = moments != 0;
+    a.part = (double *)w.part.p;
+    for (int h0 = 0; h0 < H; h0 += kChunk) {
+        a.h0 = h0; a.hn = std::min(kChunk, H - h0);
+        switch (d) {
+        case 1: pop_launch_d<1>(c, a); break;
+        case 2: pop_launch_d<2>(c, a); break;
+        case 3: pop_launch_d<3>(c, a); break;
+        case 4: pop_launch_d<4>(c, a); break;
+        default: pop_launch_d<5>(c, a); break;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pop_total, dim3((unsigned)H), dim3(64), 0, c->stream, a);
+    HIPCHK(hipGetLastError());
+    // what the caller asked for goes home, entry by entry: the [H][nsrc] tables stay on the device when it did not
+    rc = rb.each([&](void *dst, size_t off, size_t bytes) -> int {
+        HIPCHK(hipMemcpyAsync(dst, (const char *)w.lsrc.p + off, bytes, hipMemcpyDeviceToHost, c->stream));
+        return MBB_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MBB_OK;
+}
+
+extern "C" int mbb_population_drop(mbb_ctx *c)
+{
+    int rc = use(c);
+    if (rc) return rc;
+    if ((rc = sync_stream(c))) return rc;
+    mbb_ctx::PopBlock &w = c->pop;
+    w.live = false;
+    w.x.release(); w.b.release(); w.count.release(); w.hyper.release(); w.part.release(); w.lsrc.release(); w.outbuf.release();
+    return MBB_OK;
 }
 
 // ---- the maximum of the posterior (mbb_map.hip.h) ------------------------------

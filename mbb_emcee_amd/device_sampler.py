@@ -93,6 +93,11 @@ def _request_reweight(s, kw):
     return reweight._Request(nsources=s.nsources, **kw)
 
 
+def _request_population(s, kw):
+    from . import population
+    return population._Request(s.lnprobfn, **kw)
+
+
 def _request_convergence(s, kw):
     from . import diagnostics
     return diagnostics._Request(**kw)
@@ -142,12 +147,14 @@ _ANALYSES = {
                           _request_reweight, _check_loo, "reweighted", "reweight_", "reweight"),
     "convergence": _Analysis(None, None, (), None, _request_convergence, _check_steps, "diagnosed", "convergence_",
                              "convergence"),
+    "population": _Analysis(None, None, _WINDOW, {"columns", "transform", "burn", "thin", "fixed"}, _request_population,
+                            _check_steps, "pooled into a population", "population_", "population"),
 }
 # three orders, each as run_mcmc has always had it: requests are made and checked, a sharded run is refused, and the
 # results are made after the run
-_REQUEST_ORDER = ("predict", "loo", "goodness", "evidence", "marginals", "draws", "convergence", "reweight")
-_SHARDED_ORDER = ("convergence", "marginals", "predict", "loo", "goodness", "evidence", "draws", "reweight")
-_RESULT_ORDER = ("convergence", "marginals", "predict", "draws", "goodness", "evidence", "loo", "reweight")
+_REQUEST_ORDER = ("predict", "loo", "goodness", "evidence", "marginals", "draws", "convergence", "population", "reweight")
+_SHARDED_ORDER = ("convergence", "marginals", "predict", "loo", "goodness", "evidence", "draws", "population", "reweight")
+_RESULT_ORDER = ("convergence", "marginals", "predict", "draws", "goodness", "evidence", "loo", "population", "reweight")
 
 
 class DeviceEnsembleSampler(object):
@@ -195,7 +202,7 @@ class DeviceEnsembleSampler(object):
 
     def reset(self):
         """Forget the chain: an empty ``chain`` / ``lnprobability``, ``naccepted`` zeros of the ensemble's leading
-        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_``, ``loo_``, ``evidence_``, ``reweight_`` or ``predictions_``, nothing resident for ``convergence()`` or
+        shape, ``iterations`` 0, no ``summary``, ``convergence_``, ``marginals_``, ``draws_``, ``goodness_``, ``loo_``, ``evidence_``, ``reweight_``, ``population_`` or ``predictions_``, nothing resident for ``convergence()`` or
         ``marginals()``, and no
         state -- ``run_mcmc(None, n)`` raises until a run has been given positions.  The sampler's life goes on: the
         random stream does not start again (a step's draws are keyed by its number in the sampler's life), so that
@@ -340,6 +347,14 @@ class DeviceEnsembleSampler(object):
         _native.check_arg(ctx.lib.mbb_sampler_reweight(ctx.h, h, tctx.h, C.byref(spec), C.byref(out)), ctx)
         return reweight.ChainReweight(req, raw, self.nsources > 1, self.k, nkept)
 
+    def population(self, **kw):
+        """``population.Population`` (the block of x = g(theta[columns]) and of the interim prior's weights that the
+        hyper-likelihood of Gaussian population candidates is evaluated against) of the chain the last run left on the
+        device -- a run with storechain=True or with summary= --; the keywords are ``population.chain_population``'s.
+        No chain crosses the bus.  The context keeps one block: the next build replaces it."""
+        from . import population
+        return population.sampler_population(self, **kw)
+
     def evidence(self, n2=None, fixed=None, neff="auto", seed=None, burn=0, thin=1, tol=None, maxiter=None, keep=False):
         """``evidence.ChainEvidence`` (bridge-sampled ln Z per source with its error) of the chain the last run left on
         the device -- a run with storechain=True or with summary= --; the keywords are ``evidence.chain_evidence``'s,
@@ -398,7 +413,7 @@ class DeviceEnsembleSampler(object):
 
     def run_mcmc(self, pos0, N, rstate0=None, lnprob0=None, storechain=True, summary=None, convergence=None,
                  marginals=None, predict=None, draws=None, goodness=None, evidence=None, loo=None, reweight=None,
-                 **unused):
+                 population=None, **unused):
         """N stretch-move steps from pos0 [nw, 5] ([nsources, nw, 5]); returns (pos, lnprob, rstate).
 
         One trajectory: after the first call that was given positions, calls of run_mcmc and sample() with
@@ -458,13 +473,19 @@ class DeviceEnsembleSampler(object):
         ``reweight.ChainReweight`` of it (None again after reset() and at the start of the next run).  Window and
         derived-column keywords default to summary='s.
 
+        population=True, or a dict of ``population()``'s keywords: the chain of this run is pooled into a population
+        block on the device and ``sampler.population_`` is the ``population.Population`` of it (None again after reset()
+        and at the start of the next run).  With storechain=False it needs summary= too; burn and thin default to those
+        given with summary=.
+
         evidence=True, or a dict of ``evidence()``'s keywords: ln Z of the chain of this run is bridge-sampled on the
         device and ``sampler.evidence_`` is the ``evidence.ChainEvidence`` of it (None again after reset() and at the
         start of the next run).  With storechain=False it needs summary= too; burn and thin default to those given
         with summary=."""
         self._retire()
         return self._run(pos0, N, lnprob0, storechain, summary, convergence=convergence, marginals=marginals,
-                         predict=predict, draws=draws, goodness=goodness, evidence=evidence, loo=loo, reweight=reweight)
+                         predict=predict, draws=draws, goodness=goodness, evidence=evidence, loo=loo, reweight=reweight,
+                         population=population)
 
     def _retire(self):
         """End the suspended sample() generator's hold on the attributes (run_mcmc's docstring)."""

@@ -190,7 +190,7 @@ class mbb_fitter(object):
 
     # ---- run (mbb_fit.py:481-563) ------------------------------------------------
     def run(self, nburn, nsteps, p0, verbose=False, summary=None, convergence=None, marginals=None, predict=None,
-            draws=None, goodness=None, evidence=None, loo=None, reweight=None):
+            draws=None, goodness=None, evidence=None, loo=None, reweight=None, population=None):
         """Burn in for nburn steps, reset, then sample nsteps steps per walker.
         summary (device sampler only): True or a dict of ``results.chain_summary``'s keywords -- the main chain is
         summarised on the device as well, ``mbb_fitter.summary`` (DeviceEnsembleSampler.run_mcmc); for a catalogue
@@ -214,7 +214,12 @@ class mbb_fitter(object):
         ``fixed`` unless the dict names others.
         reweight (device sampler only): a target ``likelihood`` (or a ``mbb_fitter``, whose likelihood is meant), or a
         dict of ``reweight.chain_reweight``'s keywords (``target`` among them) -- the main chain reweighted under the
-        target's density, ``mbb_fitter.reweight``."""
+        target's density, ``mbb_fitter.reweight``.
+        population (device sampler only): True or a dict of ``population.chain_population``'s keywords -- the main chain
+        pooled into a population block, ``mbb_fitter.population_``; the fitter's own fixed parameters are passed on as
+        ``fixed`` unless the dict names others."""
+        if population is not None and population is not False and not hasattr(self.sampler, "population"):
+            raise ValueError("population= needs sampler=\"device\"")
         if reweight is not None and reweight is not False and not hasattr(self.sampler, "reweight"):
             raise ValueError("reweight= needs sampler=\"device\"")
         if evidence is not None and evidence is not False and not hasattr(self.sampler, "evidence"):
@@ -284,6 +289,10 @@ class mbb_fitter(object):
             if isinstance(rkw.get("target"), mbb_fitter):
                 rkw["target"] = rkw["target"].like
             extra["reweight"] = rkw
+        if population is not None and population is not False:
+            pkw = {} if population is True else dict(population)
+            pkw.setdefault("fixed", [bool(f) for f in self._fixed])
+            extra["population"] = pkw
         if evidence is not None and evidence is not False:
             ekw = {} if evidence is True else dict(evidence)
             ekw.setdefault("fixed", [bool(f) for f in self._fixed])
@@ -339,6 +348,20 @@ mbb_fitter.evidence = property(lambda self: getattr(self.sampler, "evidence_", N
                                doc="evidence.ChainEvidence of the main chain when run() was given evidence=, else None")
 mbb_fitter.reweight = property(lambda self: getattr(self.sampler, "reweight_", None),
                                doc="reweight.ChainReweight of the main chain when run() was given reweight=, else None")
+mbb_fitter.population_ = property(lambda self: getattr(self.sampler, "population_", None),
+                                  doc="population.Population of the main chain when run() was given population=, else None")
+
+
+def _fitter_population(self, **kw):
+    """``population.Population`` of the main chain the last run left on the device (device sampler only); the keywords
+    are ``population.chain_population``'s, ``fixed`` defaulting to the fitter's own fixed parameters."""
+    if not hasattr(self.sampler, "population"):
+        raise ValueError("population() needs sampler=\"device\"")
+    kw.setdefault("fixed", [bool(f) for f in self._fixed])
+    return self.sampler.population(**kw)
+
+
+mbb_fitter.population = _fitter_population
 mbb_fitter.draws = property(lambda self: getattr(self.sampler, "draws_", None),
                             doc="draws.ChainDraws from the main chain when run() was given draws=, else None")
 mbb_fitter.response_integrate = property(lambda self: self.like.response_integrate,
